@@ -17,5 +17,5 @@ done
 fail=0
 for p in "${pids[@]}"; do wait "$p" || fail=1; done
 [ $fail = 0 ] || { echo "build_asan.sh: a translation unit failed to compile" >&2; exit 1; }
-$HIPCC --offload-arch=gfx950 -shared -fPIC -fsanitize=address,undefined -shared-libsan obj_asan/*.o -o ../libbalf_hip_asan.so
+$HIPCC --offload-arch=gfx950 -shared -fPIC -fsanitize=address,undefined -fno-gpu-sanitize -shared-libsan obj_asan/*.o -o ../libbalf_hip_asan.so
 echo "built $(cd .. && pwd)/libbalf_hip_asan.so (host code instrumented; preload $($HIPCC -print-file-name=libclang_rt.asan-x86_64.so))"

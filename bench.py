@@ -7,13 +7,19 @@ already resident in HBM (gray replicated to 3 channels, /255, padded to 1088x192
 Workload = BASELINE.json configs[3] divided over the node: 32 images per GPU (256 over 8 GPUs), top-2000,
 border 15, nms 15; weak scaling.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--precision fp16|fp32]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--precision fp16|fp32] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 --precision fp16 (default, and the module default) = f16 MFMA with split (hi+lo) operands, three products per
 MAC, fp32 accumulate/LayerNorm/GELU/softmax/NMS: score map within 1e-4 of the CPU reference (the north-star bar;
-measured 4e-6 ... 6e-6 -- `index_match.prob_max_abs_err` in the line says what this run measured).
---precision fp32 = exact fp32 MFMA.  The other precision is timed too and reported under "other_precision".
+measured 4e-6 ... 6e-6 -- `index_match.prob_max_abs_err` in a --full line says what that run measured).
+--precision fp32 = exact fp32 MFMA.  With --full the other precision is timed too and reported under "other_precision".
+
+A plain run sets up, warms up, times K steps and prints the line: `value`, `ms_per_step` and the fields derived from the
+same timed steps (roofline, kernels_ms_per_step, ...).  Every other leg below (other_precision, with_logits,
+allgather_device_us, gathered_slabs_identical, index_match, cpu_baseline, other_configs, batch1_latency,
+power_state_under_load, sustained, host_fed) runs only with --full; without it those fields are null.
+--dump-outputs DIR writes what the last timed step returned (see dump_outputs) for output-for-output comparison of builds.
 
 Rank 0 prints ONE JSON line.  `value` = images/s over all GPUs; `keypoints_per_s` rides along.
   roofline      the dominant kernel (per-kernel device time from hipEvent pairs on the launch stream over the timed
@@ -137,6 +143,25 @@ def pmc_profile(precision: str, mb: int, hp: int, wp: int):
 def synthetic_batch(h, w, lo, b):
     """uint8 gray images lo .. lo+b-1 of the bench (alternating blur: smooth and noisy score maps)."""
     return np.stack([synth.synthetic_gray_u8(h, w, lo + i, blur=5 if i % 2 == 0 else 1) for i in range(b)])
+
+
+DUMP_PROB_SAMPLE = 1 << 22      # score-map values --dump-outputs writes (16 MB): the whole map is 267 MB at 32 x 1088x1920
+
+
+def dump_outputs(path, out):
+    """--dump-outputs: what the caller of the timed step receives from its last step -- the gathered keypoint slabs
+    (keypoint_index / keypoint_count in float64, which holds every int32 exactly; keypoint_score) and this rank's score
+    map (prob_sample: the values at a fixed, seeded, sorted set of flat positions of the [B,Hp,Wp] map, the whole map
+    when it is smaller than the sample)."""
+    gi, gs, gc, (_, _, _, prob) = out
+    flat = prob.reshape(-1)
+    if flat.numel() > DUMP_PROB_SAMPLE:
+        pos = torch.randint(0, flat.numel(), (DUMP_PROB_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+        flat = flat.index_select(0, pos.to(flat.device))
+    os.makedirs(path, exist_ok=True)
+    for name, t in (("keypoint_index", gi.double()), ("keypoint_score", gs.float()), ("keypoint_count", gc.double()),
+                    ("prob_sample", flat.float())):
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
 
 
 def cpu_baseline(gray, k, state, threads=0, batch=1):
@@ -666,8 +691,15 @@ def main():
                     help="at N = 1 skip the single-rank RCCL group (then the step has no collective)")
     ap.add_argument("--allow-diagnostic-build", action="store_true",
                     help="time a library built with a switch of csrc/diag.h (BALF_HIP_LIB=...); its metric field says INVALID")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline (other precision and configurations, CPU baseline and index "
+                         "match, logits-on step, collective timing and slab check, batch-1 latency, power, sustained, host-fed)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--stub-step", action="store_true", help=argparse.SUPPRESS)   # launcher test on the CPU (gloo), see stub_main
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # the driver's plain `python bench.py --gpus N`: this process becomes the launcher and never touches the GPU
@@ -894,16 +926,21 @@ def main():
     kp_per_image = float(counts.float().mean().item())
     head = summarize(args.precision, dt, prof, args.steps)
     per_rank = {"min": b * args.steps / rank_dt[0], "max": b * args.steps / rank_dt[1]}
-    # the same step with the logits written too (the reference's forward always returns them; the headline step skips the
-    # 272 MB store nobody reads): a few steps, reported beside the headline
-    dt_l, _, _ = timed_run(make_step(x, h, w, k, want_logits=True), max(args.steps // 2, 2), 1)
-    logits_on = {"images_per_s": world * b * max(args.steps // 2, 2) / dt_l, "steps": max(args.steps // 2, 2)}
-    logits_on["ratio_to_headline"] = logits_on["images_per_s"] / head["images_per_s"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)     # before any further step can reuse a buffer of the last timed one
+    # everything from here to the line is --full only: a plain run reports the timed steps and nothing else
+    logits_on = None
+    if args.full:
+        # the same step with the logits written too (the reference's forward always returns them; the headline step skips the
+        # 272 MB store nobody reads): a few steps, reported beside the headline
+        dt_l, _, _ = timed_run(make_step(x, h, w, k, want_logits=True), max(args.steps // 2, 2), 1)
+        logits_on = {"images_per_s": world * b * max(args.steps // 2, 2) / dt_l, "steps": max(args.steps // 2, 2)}
+        logits_on["ratio_to_headline"] = logits_on["images_per_s"] / head["images_per_s"]
 
     # the collective by itself: device time of pack + all_gather_into_tensor + unpack on this rank's slabs, events on the
     # stream it runs on (RCCL is stream-ordered on torch's current stream)
     allgather_us = None
-    if have_group:
+    if args.full and have_group:
         i_, s_, c_ = out[3][0], out[3][1], out[3][2]
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         for _ in range(3):
@@ -917,7 +954,7 @@ def main():
         allgather_us = e0.elapsed_time(e1) * 1e3 / 20
     # every rank must end up with the SAME gathered slabs, its own shard at rows [rank * b, (rank + 1) * b)
     slabs_identical = None
-    if have_group:
+    if args.full and have_group:
         gi_, gs_, gc_ = out[0], out[1], out[2]
         own = (torch.equal(gi_[rank * b:(rank + 1) * b], out[3][0]) and torch.equal(gc_[rank * b:(rank + 1) * b], out[3][2])
                and gi_.shape[0] == world * b)
@@ -930,14 +967,15 @@ def main():
         if not slabs_identical:
             raise SystemExit(f"[bench] rank {rank}: the gathered keypoint slabs differ between ranks (or a shard is misplaced)")
     # the CPU sample: images spread over the whole batch, so that both micro-batches of the forward are looked at
-    n_cpu = min(max(args.cpu_images, 1), b)
-    cpu_pick = sorted(set(int(round(i * (b - 1) / max(n_cpu - 1, 1))) for i in range(n_cpu)))
-    pick_t = torch.tensor(cpu_pick, device=dev)
-    gpu_sample = tuple(t.index_select(0, pick_t).clone() for t in out[3])
+    if args.full:
+        n_cpu = min(max(args.cpu_images, 1), b)
+        cpu_pick = sorted(set(int(round(i * (b - 1) / max(n_cpu - 1, 1))) for i in range(n_cpu)))
+        pick_t = torch.tensor(cpu_pick, device=dev)
+        gpu_sample = tuple(t.index_select(0, pick_t).clone() for t in out[3])
 
     other = None
     other_prec = "fp32" if args.precision == "fp16" else "fp16"
-    if args.other_steps > 0:
+    if args.full and args.other_steps > 0:
         model.precision = other_prec
         dt2, prof2, _ = timed_run(step, args.other_steps, 1)
         other = summarize(other_prec, dt2, prof2, args.other_steps)
@@ -948,7 +986,7 @@ def main():
     # own dominant kernel and -- rank 0 -- a CPU baseline on two of its images (north_star: "throughput on synthetic
     # VGA/720p/1080p ... as absolute numbers and as fraction of the HBM/MFMA roofline, next to the reference CPU path")
     other_cfgs = None
-    if world == 1 and args.other_configs and (h, w, b) == (1080, 1920, 32):
+    if args.full and world == 1 and args.other_configs and (h, w, b) == (1080, 1920, 32):
         other_cfgs = []
         del x
         cpu_done = {}
@@ -984,7 +1022,7 @@ def main():
     # batch-1 latency: the only way the reference ever calls the model (/root/reference/demo/demo_match.py:29,
     # balf/utils/train_utils.py:428) -- one uint8 image in, keypoints out, a synchronisation per call
     latency = power = None
-    if world == 1 and args.other_configs and (h, w, b) == (1080, 1920, 32):
+    if args.full and world == 1 and args.other_configs and (h, w, b) == (1080, 1920, 32):
         power = power_state_under_load(step, dev)
         if power is not None:
             # the forward is bound by the package power limit: joule per image is the figure a kernel change has
@@ -995,7 +1033,7 @@ def main():
 
     sustained = host_fed = natural = None
     rccl_ranks = dist.get_world_size() if have_group else 0
-    if world == 1 and not rehearsal:
+    if args.full and world == 1 and not rehearsal:
         if args.sustained_seconds > 0:
             sustained = sustained_run(step, dev, b, args.sustained_seconds)
             sustained["ratio_to_timed_steps"] = sustained["images_per_s"] / head["images_per_s"]
@@ -1059,7 +1097,7 @@ def main():
             "power_state_under_load": power,
             "library_build": build_flags,
         }
-        if world == 1 and args.cpu_images > 0:
+        if args.full and world == 1 and args.cpu_images > 0:
             res["cpu_baseline"], cpu_probs, cpu_dets = cpu_baseline(gray[cpu_pick], k, state, args.cpu_threads)
             res["cpu_baseline"]["sample"] = res["cpu_baseline"]["sample"].replace("(the first of the GPU batch)", f"(images {cpu_pick} of the GPU batch)")
             res["index_match"] = index_match(gpu_sample, cpu_probs, cpu_dets, h, w, k, top, left)

@@ -152,3 +152,38 @@ def test_global_batch_that_does_not_divide():
                        env=_env(WORLD_SIZE="2", RANK="0", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port())),
                        capture_output=True, text=True, timeout=300)
     assert r.returncode != 0 and "does not divide" in r.stderr, r.stderr[-2000:]
+
+
+def test_steps_must_be_positive():
+    """--steps sets the number of timed steps: zero of them is refused before anything is imported or launched"""
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "0"], env=_env(), capture_output=True, text=True,
+                       timeout=60)
+    assert r.returncode != 0 and r.stdout.strip() == "" and "--steps must be >= 1" in r.stderr, r.stderr[-1500:]
+
+
+def test_dump_outputs_writes_the_step_outputs_as_floats(tmp_path, monkeypatch):
+    """--dump-outputs: the gathered slabs exactly (int32 indices and counts in float64), the scores in float32, and the score map
+    as a fixed, seeded sample of flat positions once it is larger than the sample (whole otherwise)"""
+    import numpy as np
+    import torch
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    import bench
+    bench._import_product()
+    idx = torch.tensor([[2 ** 31 - 1, 7, -1], [0, -1, -1]], dtype=torch.int32)
+    score = torch.tensor([[0.5, 0.25, 0.0], [1e-7, 0.0, 0.0]])
+    count = torch.tensor([2, 1], dtype=torch.int32)
+    prob = torch.arange(2 * 4 * 6, dtype=torch.float32).view(2, 4, 6)
+    out = (idx, score, count, (idx, score, count, prob))
+    monkeypatch.setattr(bench, "DUMP_PROB_SAMPLE", 1000)
+    bench.dump_outputs(str(tmp_path / "whole"), out)
+    got = {n: np.load(tmp_path / "whole" / f"{n}.npy") for n in ("keypoint_index", "keypoint_score", "keypoint_count", "prob_sample")}
+    assert {n: a.dtype for n, a in got.items()} == {"keypoint_index": np.float64, "keypoint_score": np.float32,
+                                                     "keypoint_count": np.float64, "prob_sample": np.float32}
+    assert np.array_equal(got["keypoint_index"], idx.numpy()) and np.array_equal(got["keypoint_count"], count.numpy())
+    assert np.array_equal(got["keypoint_score"], score.numpy()) and np.array_equal(got["prob_sample"], prob.numpy().ravel())
+    monkeypatch.setattr(bench, "DUMP_PROB_SAMPLE", 10)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), out)
+    a, b = np.load(tmp_path / "a" / "prob_sample.npy"), np.load(tmp_path / "b" / "prob_sample.npy")
+    assert a.shape == (10,) and np.array_equal(a, b) and np.all(np.diff(a) >= 0)   # prob = its flat position: sorted positions

@@ -91,7 +91,7 @@ def test_allgather_two_ranks():
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--other-configs", "0", "--other-steps", "0", "--cpu-images", "0"], env=env, capture_output=True,
+                        "--other-configs", "0", "--other-steps", "0", "--cpu-images", "0", "--full"], env=env, capture_output=True,
                        text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -114,7 +114,7 @@ def test_two_ranks_on_one_gpu_rehearsal():
     env["BALF_BENCH_REHEARSAL"] = "1"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
                         "--batch-per-gpu", "3", "--height", "480", "--width", "640", "--topk", "1000",
-                        "--other-configs", "0", "--other-steps", "0", "--cpu-images", "0"], env=env, capture_output=True,
+                        "--other-configs", "0", "--other-steps", "0", "--cpu-images", "0", "--full"], env=env, capture_output=True,
                        text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -137,7 +137,7 @@ def test_four_ranks_on_one_gpu_rehearsal_at_the_real_shard():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     env["BALF_BENCH_REHEARSAL"] = "1"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1",
-                        "--other-configs", "0", "--other-steps", "0", "--cpu-images", "0"], env=env, capture_output=True,
+                        "--other-configs", "0", "--other-steps", "0", "--cpu-images", "0", "--full"], env=env, capture_output=True,
                        text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]

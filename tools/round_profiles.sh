@@ -1,6 +1,6 @@
 #!/bin/bash
 # Everything profiles/rN_* is made from, in one GPU call: tools/round_profiles.sh <outdir under gpurun_out> [pmc]
-#   bench.json            python bench.py --steps 20 --warmup 3 (the driver's form)
+#   bench.json            python bench.py --full --steps 20 --warmup 3 (the driver's form with every leg)
 #   kernel_stats.csv      rocprofv3 --kernel-trace --stats of a short bench run (same command line as rounds 3-5)
 #   demo_bench_*.json     tools/bench_demo.py at 1080p and VGA;  greedy_bench.json  tools/bench_greedy.py
 #   pmc/ (+ <out>/pmc.json with the `pmc` argument)   tools/pmc_profile.sh
@@ -8,7 +8,7 @@ root="$(cd "$(dirname "$0")/.." && pwd)"
 out=$1
 mkdir -p "$root/$out"
 cd "$root"
-timeout -k 10 900 python bench.py --steps 20 --warmup 3 > "$out/bench.json" 2> "$out/bench.err" || { echo "bench failed"; tail -5 "$out/bench.err"; exit 1; }
+timeout -k 10 900 python bench.py --full --steps 20 --warmup 3 > "$out/bench.json" 2> "$out/bench.err" || { echo "bench failed"; tail -5 "$out/bench.err"; exit 1; }
 echo "bench done"
 (cd /tmp && export TMPDIR=/tmp && BALF_FP16_CHECK=0 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$root/$out/kstats" -- python3 "$root/bench.py" --steps 3 --warmup 1 --cpu-images 0 --other-configs 0 --other-steps 0 --no-single-rank-collective --sustained-seconds 0 --host-fed-steps 0 > "$root/$out/kstats_bench.json" 2> "$root/$out/kstats.err") || { echo "kernel stats failed"; exit 1; }
 find "$out/kstats" -name "*kernel_stats.csv" -exec cp {} "$out/kernel_stats.csv" \;
