@@ -15,6 +15,8 @@ LIB_PATH = os.environ.get("BALF_HIP_LIB", os.path.join(_HERE, "libbalf_hip.so"))
 OK = 0
 PREC_FP32, PREC_FP16 = 0, 1
 MAX_NMS_SIZE, MAX_TOPK = 32, 16384
+PYR_SRC_U8, PYR_SRC_F32, PYR_SRC_LEVEL = 0, 1, 2                   # include/balf_hip.h: balf_pyramid_level
+PYR_MAX_RADIUS, MAX_PYRAMID_LEVELS = 8, 32
 STATUS_SCORE, STATUS_RANGE, STATUS_SE, STATUS_WORDS = 0, 1, 2, 4      # include/balf_hip.h: balf_forward_status
 
 # name -> (restype, argtypes); kept in step with include/balf_hip.h (tests/test_abi.py checks)
@@ -41,6 +43,9 @@ PROTOTYPES = {
     "balf_nms_topk_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "balf_nms_topk": (_i, [_fp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _fp, _vp, _vp, _sz, _vp]),
     "balf_nms_threshold": (_i, [_fp, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.c_float, _i, _vp, _fp, _vp, _vp, _sz, _vp]),
+    "balf_pyramid_level": (_i, [_vp, _i, _i, _i, _i, _i, C.c_double, _i, _i, _fp, _vp]),
+    "balf_nms_topk_budget": (_i, [_fp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _fp, _vp, _vp, _sz, _vp]),
+    "balf_multiscale_merge": (_i, [_vp, _fp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "balf_greedy_nms_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "balf_greedy_nms": (_i, [_fp, _i, _i, _i, _i, _i, _i, _i, _i, C.c_float, _i, _i, _i, _vp, _fp, _fp, _vp, _vp, _vp,
                             _sz, _vp]),

@@ -42,7 +42,7 @@
 
 int balf_topk_select_launch(const int2 *surv, const int *counts, long cap, int B, int K, int zero_fallback,
                             int32_t *idx_dev, float *score_dev, int32_t *count_dev, hipStream_t st,
-                            unsigned thr_explicit);
+                            unsigned thr_explicit, int32_t *taken_dev = nullptr, int cum_budget = 0);
 
 namespace {
 

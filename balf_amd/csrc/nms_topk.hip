@@ -479,7 +479,8 @@ __device__ unsigned radix_select(int n, int rank, bool cached, const int2 (&ent)
 __global__ __launch_bounds__(SEL_THREADS) void topk_select_kernel(const int2 *surv_all, const int *surv_count,
                                                                   long cap, int K, int npow2, int zero_fallback,
                                                                   unsigned thr_explicit, int32_t *idx_out,
-                                                                  float *score_out, int32_t *count_out) {
+                                                                  float *score_out, int32_t *count_out,
+                                                                  int32_t *taken, int cum_budget) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned long long *keys = reinterpret_cast<unsigned long long *>(smem);       // [npow2]
     unsigned *s_hist = reinterpret_cast<unsigned *>(keys + npow2);                 // [256]
@@ -489,19 +490,39 @@ __global__ __launch_bounds__(SEL_THREADS) void topk_select_kernel(const int2 *su
     const int b = blockIdx.x;
     const int2 *surv = surv_all + (long)b * cap;
     const int n = surv_count[b];
-    int32_t *idx_o = idx_out + (long)b * K;
-    float *sc_o = score_out + (long)b * K;
+    const int K_row = K;           // output row length; the selection's K differs from it only under a budget
+    int32_t *idx_o = idx_out + (long)b * K_row;
+    float *sc_o = score_out + (long)b * K_row;
+    if (taken) {
+        // budgeted form (balf_nms_topk_budget): K = min(cum_budget - taken[b], H*W), decided here per image; taken[b] grows
+        // by this image's count at the end.  Read by one thread and broadcast: thread 0 stores the new value before the
+        // slower waves would otherwise have read the old one.
+        if (threadIdx.x == 0) {
+            long kb = (long)cum_budget - taken[b];
+            kb = kb < cap ? kb : cap;
+            *s_cnt = kb > 0 ? (int)kb : 0;
+        }
+        __syncthreads();
+        K = *s_cnt;
+        __syncthreads();
+        int p = 1;
+        while (p < K) p <<= 1;
+        npow2 = p;                 // <= the host's next_pow2(K_row): the LDS holds it
+    }
 
-    if (n == 0 && (!zero_fallback || thr_explicit)) {     // greedy-NMS caller / explicit threshold: no candidates, no points
-        for (int i = threadIdx.x; i < K; i += SEL_THREADS) { idx_o[i] = -1; sc_o[i] = 0.0f; }
+    if (K == 0 || (n == 0 && (!zero_fallback || thr_explicit))) {   // greedy-NMS caller / explicit threshold / no budget left
+        for (int i = threadIdx.x; i < K_row; i += SEL_THREADS) { idx_o[i] = -1; sc_o[i] = 0.0f; }
         if (threadIdx.x == 0) count_out[b] = 0;
-        return;
+        return;                    // (taken[b] += 0)
     }
     if (n == 0) {
         // No positive NMS score: the reference's threshold falls back to 0.0 and `map >= 0` holds
         // everywhere, so it returns the first K pixels in raster order (test_utils.py:84-95).
-        for (int i = threadIdx.x; i < K; i += SEL_THREADS) { idx_o[i] = i; sc_o[i] = 0.0f; }
-        if (threadIdx.x == 0) count_out[b] = K;
+        for (int i = threadIdx.x; i < K_row; i += SEL_THREADS) { idx_o[i] = i < K ? i : -1; sc_o[i] = 0.0f; }
+        if (threadIdx.x == 0) {
+            count_out[b] = K;
+            if (taken) taken[b] += K;
+        }
         return;
     }
 
@@ -593,7 +614,7 @@ __global__ __launch_bounds__(SEL_THREADS) void topk_select_kernel(const int2 *su
             __syncthreads();
         }
     }
-    for (int i = threadIdx.x; i < K; i += SEL_THREADS) {
+    for (int i = threadIdx.x; i < K_row; i += SEL_THREADS) {
         if (i < cnt) {
             const unsigned long long kv = keys[i];
             idx_o[i] = (int32_t)(unsigned)(kv & 0xffffffffull);
@@ -603,7 +624,10 @@ __global__ __launch_bounds__(SEL_THREADS) void topk_select_kernel(const int2 *su
             sc_o[i] = 0.0f;
         }
     }
-    if (threadIdx.x == 0) count_out[b] = cnt;
+    if (threadIdx.x == 0) {
+        count_out[b] = cnt;
+        if (taken) taken[b] += cnt;
+    }
 }
 
 int launch_nms_tiles(const NmsArgs &a, int B, hipStream_t stream) {
@@ -653,9 +677,10 @@ int balf_fill_u32(void *dst_dev, unsigned value, size_t n_words, hipStream_t str
 }
 
 // shared by balf_nms_topk and balf_greedy_nms (nms_fast.hip)
+// taken_dev != NULL: the budgeted selection of balf_nms_topk_budget (K is then the output row length K_max)
 int balf_topk_select_launch(const int2 *surv, const int *counts, long cap, int B, int K, int zero_fallback,
                             int32_t *idx_dev, float *score_dev, int32_t *count_dev, hipStream_t st,
-                            unsigned thr_explicit) {
+                            unsigned thr_explicit, int32_t *taken_dev, int cum_budget) {
     const int npow2 = next_pow2(K);
     const size_t smem = (size_t)npow2 * 8 + 256 * 4 + 8 * 4;
     if (smem > 48 * 1024 &&
@@ -664,7 +689,7 @@ int balf_topk_select_launch(const int2 *surv, const int *counts, long cap, int B
         return BALF_ERR_LAUNCH;
     BALF_PROF(balf_prof::kTopkSelect, st,
               hipLaunchKernelGGL(topk_select_kernel, dim3(B), dim3(SEL_THREADS), smem, st, surv, counts, cap, K, npow2,
-                                 zero_fallback, thr_explicit, idx_dev, score_dev, count_dev));
+                                 zero_fallback, thr_explicit, idx_dev, score_dev, count_dev, taken_dev, cum_budget));
     BALF_LAUNCH_CHECK();
     return BALF_OK;
 }
@@ -686,14 +711,16 @@ extern "C" size_t balf_nms_topk_workspace_bytes(int B, int H, int W, int K) {
 }
 
 namespace {
+// taken_dev != NULL: K is K_max, the row length, and each image's K is decided on the device (balf_nms_topk_budget)
 int nms_select(const float *prob_dev, int B, int Hp, int Wp, int crop_y, int crop_x, int H, int W, int border,
                int nms_size, int K, unsigned thr_explicit, int32_t *idx_dev, float *score_dev, int32_t *count_dev,
-               void *workspace_dev, size_t workspace_bytes, void *stream) {
+               void *workspace_dev, size_t workspace_bytes, void *stream, int32_t *taken_dev = nullptr,
+               int cum_budget = 0) {
     if (!prob_dev || !idx_dev || !score_dev || !count_dev || !workspace_dev) return BALF_ERR_ARG;
     if (B <= 0 || H <= 0 || W <= 0 || K <= 0 || border < 0) return BALF_ERR_ARG;
     if (nms_size < 1 || nms_size > BALF_MAX_NMS_SIZE || K > BALF_MAX_TOPK) return BALF_ERR_ARG;
     if (crop_y < 0 || crop_x < 0 || crop_y + H > Hp || crop_x + W > Wp) return BALF_ERR_SHAPE;
-    if ((long)H * W > 0x7fffffffL || (long)K > (long)H * W) return BALF_ERR_SHAPE;
+    if ((long)H * W > 0x7fffffffL || (!taken_dev && (long)K > (long)H * W)) return BALF_ERR_SHAPE;
     if (workspace_bytes < balf_nms_topk_workspace_bytes(B, H, W, K)) return BALF_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
 
@@ -706,7 +733,7 @@ int nms_select(const float *prob_dev, int B, int Hp, int Wp, int crop_y, int cro
     if (rc != BALF_OK) return rc;
 
     return balf_topk_select_launch(surv, counts, (long)H * W, B, K, /*zero_fallback=*/1, idx_dev, score_dev, count_dev, st,
-                                   thr_explicit);
+                                   thr_explicit, taken_dev, cum_budget);
 }
 }  // namespace
 
@@ -724,4 +751,13 @@ extern "C" int balf_nms_threshold(const float *prob_dev, int B, int Hp, int Wp, 
     const unsigned bits = __builtin_bit_cast(unsigned, threshold);
     return nms_select(prob_dev, B, Hp, Wp, crop_y, crop_x, H, W, border, nms_size, K, bits, idx_dev, score_dev, count_dev,
                       workspace_dev, workspace_bytes, stream);
+}
+
+extern "C" int balf_nms_topk_budget(const float *prob_dev, int B, int Hp, int Wp, int crop_y, int crop_x, int H, int W,
+                                    int border, int nms_size, int cum_budget, int K_max, int32_t *taken_dev,
+                                    int32_t *idx_dev, float *score_dev, int32_t *count_dev, void *workspace_dev,
+                                    size_t workspace_bytes, void *stream) {
+    if (!taken_dev || cum_budget < 0 || cum_budget > K_max) return BALF_ERR_ARG;
+    return nms_select(prob_dev, B, Hp, Wp, crop_y, crop_x, H, W, border, nms_size, K_max, 0u, idx_dev, score_dev, count_dev,
+                      workspace_dev, workspace_bytes, stream, taken_dev, cum_budget);
 }

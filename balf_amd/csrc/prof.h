@@ -21,7 +21,9 @@ enum Slot {
     kMatchMutual = 27,
     kGreedyKeep = 28,       // greedy NMS of the demo path
     kGreedyKill = 29,
-    kNumSlots = 30,
+    kMsPyramid = 30,        // multi-scale extraction: pyramid level, merge of the level lists
+    kMsMerge = 31,
+    kNumSlots = 32,
 };
 extern bool g_on;
 void before(int slot, hipStream_t st);

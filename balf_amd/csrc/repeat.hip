@@ -17,13 +17,13 @@
 //                      accumulated in the reference's order
 // The candidate count is data dependent, so balf_repeatability synchronises the stream once to read it.
 #include "common.h"
+#include "homography.h"
 
 namespace balf {
 namespace {
 
 constexpr double kPi = 3.141592653589793;
 constexpr double kEpsF64 = 2.220446049250313e-16;          // np.finfo(float).eps
-constexpr double kEpsF32 = 1.1920928955078125e-07;         // np.finfo(np.float32).eps
 constexpr int kMaxPoints = 65536;                          // visited bitmaps live in LDS
 
 struct RepParams {
@@ -180,14 +180,7 @@ __global__ __launch_bounds__(64) void rep_greedy_kernel(const unsigned long long
 __global__ void homography_kernel(const double *pts, int n, const double *h, double *out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const double x = pts[4 * i], y = pts[4 * i + 1], r = pts[4 * i + 2];
-    const double den = h[6] * x + h[7] * y + h[8];
-    const double nx = h[0] * x + h[1] * y + h[2], ny = h[3] * x + h[4] * y + h[5];
-    const double fxdx = h[0] / den - nx * h[6] / (den * den), fxdy = h[1] / den - nx * h[7] / (den * den);
-    const double fydx = h[3] / den - ny * h[6] / (den * den), fydy = h[4] / den - ny * h[7] / (den * den);
-    const double tmp = r * r + kEpsF32;
-    out[4 * i] = nx / den; out[4 * i + 1] = ny / den;
-    out[4 * i + 2] = sqrt(tmp * fabs(fxdx * fydy - fxdy * fydx));
+    homography_point(h, pts[4 * i], pts[4 * i + 1], pts[4 * i + 2], &out[4 * i], &out[4 * i + 1], &out[4 * i + 2]);
     out[4 * i + 3] = pts[4 * i + 3];
 }
 

@@ -5,9 +5,11 @@ from __future__ import annotations
 import ctypes as C
 from typing import Dict, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
+from .arch import padded_hw
 from ._lib import BalfHipError, check, current_stream_ptr, lib, require_gpu_tensor
 
 _workspaces: Dict[Tuple[str, int, int], torch.Tensor] = {}      # insertion order = least recently used first
@@ -241,3 +243,106 @@ def match_smnn_batch(desc1: torch.Tensor, n1: torch.Tensor, desc2: torch.Tensor,
                                           float(th), idx.data_ptr(), dist.data_ptr(), count.data_ptr(), ws.data_ptr(),
                                           ws.numel(), current_stream_ptr(dev)), "balf_match_smnn_batch")
     return dist, idx, count
+
+
+# ---- multi-scale extraction (balf_amd/multiscale.py drives these) ----------------------------------------------------------
+def pyramid_level(src: torch.Tensor, kind: int, channels: int, h_in: int, w_in: int, sigma: float, h_out: int,
+                  w_out: int) -> torch.Tensor:
+    """One pyramid level -> the zero-padded [B,3,Hp,Wp] fp32 batch the forward takes (balf_pyramid_level in
+    include/balf_hip.h).  ``src``: uint8 [B,H,W(,3)] (kind PYR_SRC_U8), fp32 [B,H,W,3] (PYR_SRC_F32) or a level this
+    function returned (PYR_SRC_LEVEL, ``channels`` 1 for a gray pyramid); ``sigma > 0`` blurs before resampling."""
+    require_gpu_tensor(src, "src")
+    b = src.shape[0]
+    hp, wp = padded_hw(h_out, w_out)[:2]
+    dev = src.device
+    out = torch.empty((b, 3, hp, wp), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().balf_pyramid_level(src.data_ptr(), int(kind), int(channels), b, int(h_in), int(w_in), float(sigma),
+                                       int(h_out), int(w_out), out.data_ptr(), current_stream_ptr(dev)),
+              "balf_pyramid_level")
+    return out
+
+
+def build_pyramid(images: torch.Tensor, shapes, upsampled_levels: int, sigma: float):
+    """uint8 gray [B,H,W] / RGB [B,H,W,3] or float [B,H,W,3] images on the GPU -> one padded [B,3,Hp_i,Wp_i] fp32 batch per
+    level of ``shapes`` (level ``upsampled_levels`` is the input itself): level U is the input as the forward's prepared
+    input, the levels below it are level U resized without blur, each level above it is the one before blurred (``sigma``)
+    and resized.  Stream-ordered, nothing read back."""
+    require_gpu_tensor(images, "images")
+    u = int(upsampled_levels)
+    if images.dtype == torch.uint8:
+        if images.dim() not in (3, 4) or (images.dim() == 4 and images.shape[-1] != 3):
+            raise ValueError("uint8 images must be [B,H,W] (gray) or [B,H,W,3] (RGB)")
+        kind, ch = _lib.PYR_SRC_U8, (1 if images.dim() == 3 else 3)
+    else:
+        if images.dim() != 4 or images.shape[-1] != 3 or not images.is_floating_point():
+            raise ValueError("float images must be [B,H,W,3]")
+        images = images.to(torch.float32).contiguous()
+        kind, ch = _lib.PYR_SRC_F32, 3
+    h, w = images.shape[1], images.shape[2]
+    if tuple(shapes[u]) != (h, w):
+        raise ValueError(f"level {u} must have the input's shape {(h, w)}, got {tuple(shapes[u])}")
+    levels = [None] * len(shapes)
+    levels[u] = pyramid_level(images, kind, ch, h, w, 0.0, h, w)
+    for i in range(u - 1, -1, -1):
+        levels[i] = pyramid_level(levels[u], _lib.PYR_SRC_LEVEL, ch, h, w, 0.0, *shapes[i])
+    for i in range(u + 1, len(shapes)):
+        levels[i] = pyramid_level(levels[i - 1], _lib.PYR_SRC_LEVEL, ch, *shapes[i - 1], float(sigma), *shapes[i])
+    return levels
+
+
+def nms_topk_budget(prob: torch.Tensor, crop_y: int, crop_x: int, h: int, w: int, border: int, nms_size: int,
+                    cum_budget: int, k_max: int, taken: torch.Tensor, idx: torch.Tensor = None, score: torch.Tensor = None,
+                    count: torch.Tensor = None):
+    """:func:`nms_topk` with each image's K decided on the device: K_b = min(cum_budget - taken[b], h*w), then
+    ``taken[b] += count[b]`` (balf_nms_topk_budget).  ``taken`` [B] int32 on the GPU, zero before the first level.
+    Returns (idx [B,k_max], score [B,k_max], count [B]); pass ``idx`` / ``score`` / ``count`` to write into given rows."""
+    require_gpu_tensor(prob, "prob")
+    require_gpu_tensor(taken, "taken")
+    if prob.dtype != torch.float32 or prob.dim() != 3:
+        raise BalfHipError("prob must be a [B,Hp,Wp] float32 tensor")
+    b, hp, wp = prob.shape
+    if taken.dtype != torch.int32 or taken.shape != (b,):
+        raise BalfHipError("taken must be a [B] int32 tensor")
+    dev = prob.device
+    idx = torch.empty((b, k_max), dtype=torch.int32, device=dev) if idx is None else idx
+    score = torch.empty((b, k_max), dtype=torch.float32, device=dev) if score is None else score
+    count = torch.empty((b,), dtype=torch.int32, device=dev) if count is None else count
+    for t, shape, dt in ((idx, (b, k_max), torch.int32), (score, (b, k_max), torch.float32), (count, (b,), torch.int32)):
+        require_gpu_tensor(t, "output")
+        if t.shape != shape or t.dtype != dt:
+            raise BalfHipError(f"output must be {dt} {shape}, got {t.dtype} {tuple(t.shape)}")
+    ws = _workspace("nms", dev, lib().balf_nms_topk_workspace_bytes(b, h, w, 1))
+    with torch.cuda.device(dev):
+        check(lib().balf_nms_topk_budget(prob.data_ptr(), b, hp, wp, int(crop_y), int(crop_x), int(h), int(w), int(border),
+                                         int(nms_size), int(cum_budget), int(k_max), taken.data_ptr(), idx.data_ptr(),
+                                         score.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel(),
+                                         current_stream_ptr(dev)), "balf_nms_topk_budget")
+    return idx, score, count
+
+
+def multiscale_merge(idx: torch.Tensor, score: torch.Tensor, count: torch.Tensor, widths, homographies, n: int,
+                     order_yx: bool = False):
+    """Level lists idx / score [L,B,K_max], count [L,B] -> (pts [B,n,4] float64, count [B] int32): every entry's
+    (x, y, 1.0, score) mapped through its level's 3x3 homography, ordered by (score desc, level asc, index asc), the
+    first n kept; (y, x, ...) with ``order_yx`` (balf_multiscale_merge)."""
+    for t, name in ((idx, "idx"), (score, "score"), (count, "count")):
+        require_gpu_tensor(t, name)
+    if idx.dim() != 3 or score.shape != idx.shape or count.shape != idx.shape[:2]:
+        raise BalfHipError("idx / score must be [L,B,K_max] and count [L,B]")
+    if idx.dtype != torch.int32 or score.dtype != torch.float32 or count.dtype != torch.int32:
+        raise BalfHipError("idx / count must be int32 and score float32")
+    nl, b, k_max = idx.shape
+    w_host = (C.c_int32 * nl)(*[int(v) for v in widths])
+    hs = [float(v) for hm in homographies for v in list(np.asarray(hm, dtype=np.float64).reshape(9))]
+    if len(widths) != nl or len(hs) != 9 * nl:
+        raise BalfHipError(f"{nl} levels need {nl} widths and {nl} homographies")
+    h_host = (C.c_double * (9 * nl))(*hs)
+    dev = idx.device
+    pts = torch.empty((b, n, 4), dtype=torch.float64, device=dev)
+    cnt = torch.empty((b,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().balf_multiscale_merge(idx.data_ptr(), score.data_ptr(), count.data_ptr(), nl, b, k_max, w_host, h_host,
+                                          int(n), int(bool(order_yx)), pts.data_ptr(), cnt.data_ptr(),
+                                          current_stream_ptr(dev)), "balf_multiscale_merge")
+    return pts, cnt

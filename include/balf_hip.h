@@ -172,6 +172,53 @@ int balf_nms_threshold(const float *prob_dev, int B, int Hp, int Wp, int crop_y,
                        int border, int nms_size, float threshold, int K, int32_t *idx_dev, float *score_dev,
                        int32_t *count_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
 
+/* ---- multi-scale extraction over an image pyramid (balf_amd/multiscale.py states the protocol) --------------------------
+ * The Key.Net-style protocol that balf/configs/config_hpatches.py:50-80 configures (scale_factor_levels r, pyramid_levels P,
+ * upsampled_levels U, num_points N): levels of scale r^(i-U), each run through balf_forward, a share of N points per level
+ * chosen on the device, the level lists merged into one list in original-image coordinates with a scale column.
+ *
+ * balf_pyramid_level: one level into dst_dev [B,3,Hp,Wp] fp32, the zero-padded NCHW batch balf_forward takes (Hp, Wp, and
+ * the image offset as in balf_forward_u8: H_out, W_out rounded up to even, then to a multiple of 64, centred); every
+ * padded pixel is written (0 outside the image).  The source is
+ *   BALF_PYR_SRC_U8     uint8 [B,H_in,W_in,channels], channels 1 (gray: replicated to the three planes) or 3; value / 255
+ *   BALF_PYR_SRC_F32    fp32 [B,H_in,W_in,3]
+ *   BALF_PYR_SRC_LEVEL  a level an earlier call wrote: fp32 [B,3,Hp_in,Wp_in] padded from H_in x W_in; channels = 1 reads
+ *                       plane 0 only (a gray level's planes are equal)
+ * sigma > 0: Gaussian blur first, taps exp(-k^2/2 sigma^2) for |k| <= R = int(4 sigma + 0.5) <= BALF_PYR_MAX_RADIUS,
+ * normalised, half-sample symmetric border (scipy.ndimage mode='reflect'), separable; sigma <= 0: no blur.  Then bilinear
+ * resampling to H_out x W_out with half-pixel centres: src = (o + 0.5) * in/out - 0.5 clamped below at 0, the upper
+ * neighbour clamped to in - 1 (F.interpolate(mode='bilinear', align_corners=False)).  H_out = H_in, W_out = W_in without
+ * blur is a copy: the level is then bit-identical to what balf_forward_u8 / pad_batch prepare.  fp32 arithmetic, the
+ * sampling positions in float64. */
+#define BALF_PYR_SRC_U8 0
+#define BALF_PYR_SRC_F32 1
+#define BALF_PYR_SRC_LEVEL 2
+#define BALF_PYR_MAX_RADIUS 8
+#define BALF_MAX_PYRAMID_LEVELS 32
+int balf_pyramid_level(const void *src_dev, int src_kind, int channels, int B, int H_in, int W_in, double sigma, int H_out,
+                       int W_out, float *dst_dev, void *stream);
+
+/* balf_nms_topk with the K of each image decided ON THE DEVICE from a point budget: K_b = min(cum_budget - taken_dev[b], H*W)
+ * (0 if negative), then taken_dev[b] += count_b.  Called once per level with cum_budget = the budget of the levels so far, a
+ * level that finds fewer points than its share passes the rest down -- nothing is read back.  taken_dev [B] int32, zeroed by
+ * the caller before the first level.  Rows are K_max long (idx_dev / score_dev [B,K_max], -1 / 0 past count_dev[b]);
+ * 0 <= cum_budget <= K_max <= BALF_MAX_TOPK; K_max may exceed H*W.  Selection as balf_nms_topk, its <= 0 fallback included
+ * (the first K_b raster pixels); K_b = 0 gives count 0.  Workspace: balf_nms_topk_workspace_bytes(B, H, W, 1). */
+int balf_nms_topk_budget(const float *prob_dev, int B, int Hp, int Wp, int crop_y, int crop_x, int H, int W, int border,
+                         int nms_size, int cum_budget, int K_max, int32_t *taken_dev, int32_t *idx_dev, float *score_dev,
+                         int32_t *count_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+
+/* The L level lists -> one list per image in original-image coordinates.  idx_dev / score_dev [L,B,K_max] and count_dev
+ * [L,B] as balf_nms_topk_budget writes them (flat index y * w + x in level l, w = level_w_host[l]).  Every entry is ordered
+ * by (score descending, level ascending, flat index ascending); row r < count_out_dev[b] = min(total, N) of pts_dev
+ * [B,N,4] float64 is the r-th entry's point (x, y, 1.0, score) mapped through h_host[9 l .. 9 l + 8] (row-major, HOST
+ * memory) with the arithmetic of balf_apply_homography: (x', y', radius, score), or (y', x', radius, score) with order_yx.
+ * Rows past the count are 0.  The entries of an image must fit min(L * K_max, BALF_MAX_TOPK) (budgeted lists sum to at most
+ * N): an image whose lists hold more gets count -1 and zero rows.  L <= BALF_MAX_PYRAMID_LEVELS, N <= BALF_MAX_TOPK. */
+int balf_multiscale_merge(const int32_t *idx_dev, const float *score_dev, const int32_t *count_dev, int L, int B, int K_max,
+                          const int32_t *level_w_host, const double *h_host, int N, int order_yx, double *pts_dev,
+                          int32_t *count_out_dev, void *stream);
+
 /* ---- greedy "SuperPoint" NMS of the demo path --------------------------------------
  * Replaces get_points_direct_from_score_map + nms_fast (+ soft_argmax_points), balf/utils/test_utils.py:97-215,
  * as called by demo/demo_match.py:45-57.  The score map of image b is prob[b, crop_y:+H, crop_x:+W] with a
