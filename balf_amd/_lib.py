@@ -72,6 +72,10 @@ PROTOTYPES = {
                                _vp, _sz, _vp]),
     "balf_apply_homography": (_i, [_vp, _i, _vp, _vp, _vp]),
     "balf_common_region_masks": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "balf_common_points_batch": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "balf_repeatability_batch_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "balf_repeatability_batch": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, C.c_double, C.c_double, C.c_double,
+                                     C.c_double, _i, _vp, _vp, _vp, _sz, _vp]),
     "balf_profile_num_slots": (_i, []),
     "balf_profile_slot_name": (C.c_char_p, [_i]),
     "balf_profile_begin": (_i, []),

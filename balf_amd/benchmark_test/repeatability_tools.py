@@ -2,16 +2,19 @@
 /root/reference/balf/benchmark_test/repeatability_tools.py:379-490 (callers: train_utils.py:189,257,
 dataset_utils.py:332).  The reference's Ns x Nd Python double loop, two dense overlap matrices and their argsorts
 become one call into ``balf_repeatability`` (include/balf_hip.h); float64 throughout.  No CPU path.
+``compute_repeatability_batch`` is the same for P pairs in one stream-ordered call (``balf_repeatability_batch``).
 
 ``apply_nms`` of the same reference module (:19-23) is the window-max NMS: use ``balf_amd.utils.test_utils.apply_nms``.
 """
 from __future__ import annotations
 
+from typing import NamedTuple
+
 import numpy as np
 import torch
 
 from .. import ops
-from .._lib import BalfHipError, check, current_stream_ptr, lib
+from .._lib import BalfHipError, check, current_stream_ptr, lib, require_gpu_tensor
 
 MAX_EDGES = 1 << 22
 
@@ -66,6 +69,66 @@ def compute_repeatability(src_indexes, dst_indexes, overlap_err=0.4, eps=1e-6, d
             'num_points_multi_scale': found[1], 'error_overlap_single_scale': err_s,
             'error_overlap_multi_scale': err_m, 'total_num_points': points,
             'correspondences': corr[0], 'possible_matches': possible, 'correspondences_m': corr[1]}
+
+
+class RepeatabilityBatch(NamedTuple):
+    """Per-pair results of :func:`compute_repeatability_batch`, device tensors ``[P]``: the fields of
+    :func:`compute_repeatability`'s dict (float64 / int32) plus the candidate counts of the two scales."""
+    rep_single_scale: torch.Tensor
+    rep_multi_scale: torch.Tensor
+    error_overlap_single_scale: torch.Tensor
+    error_overlap_multi_scale: torch.Tensor
+    num_points_single_scale: torch.Tensor
+    num_points_multi_scale: torch.Tensor
+    possible_matches: torch.Tensor
+    total_num_points: torch.Tensor
+    candidates_single_scale: torch.Tensor
+    candidates_multi_scale: torch.Tensor
+
+
+def _counts(c, p, dev, name):
+    if not isinstance(c, torch.Tensor) or c.dim() != 1 or c.shape[0] != p or c.device != dev:
+        raise BalfHipError(f"{name} must be a [{p}] tensor on {dev}")
+    return c if c.dtype == torch.int32 else c.to(torch.int32)
+
+
+def compute_repeatability_batch(src, ns, dst, nd, overlap_err=0.4, eps=1e-6, dist_match_thresh=3, radious_size=30.,
+                                max_edges=None) -> RepeatabilityBatch:
+    """:func:`compute_repeatability` for P independent pairs in one stream-ordered call (``balf_repeatability_batch``,
+    include/balf_hip.h), bit-identical to it per pair.  ``src`` [P,Ns,C] / ``dst`` [P,Nd,C] float64 rows starting with
+    (x, y, radius) on the GPU, ``ns`` / ``nd`` [P] int32 on the GPU (rows past a pair's count are ignored).  Returns device
+    tensors and reads nothing back: capturable with ``torch.cuda.graph``.  A pair with a zero count gets rep NaN (the
+    reference's 0 / 0.0) and is what the reference's caller skips.  ``max_edges`` bounds the candidate pairs of each scale
+    summed over all pairs (default: ``min(P Ns Nd, MAX_EDGES)``); a pair whose candidates do not fit reports
+    ``num_points_* = -1`` with NaN rep / error, and ``candidates_*`` says what it needed."""
+    for t, name in ((src, "src"), (dst, "dst")):
+        require_gpu_tensor(t, name)
+        if t.dtype != torch.float64 or t.dim() != 3 or t.shape[2] < 3:
+            raise BalfHipError(f"{name} must be a [P,N,C>=3] float64 tensor")
+    p, ns_max, nd_max = src.shape[0], src.shape[1], dst.shape[1]
+    if dst.shape[0] != p or p == 0:
+        raise BalfHipError(f"src and dst must hold the same number (> 0) of pairs, got {p} and {dst.shape[0]}")
+    dev = src.device
+    ns, nd = _counts(ns, p, dev, "ns"), _counts(nd, p, dev, "nd")
+    if ns.stride(0) != nd.stride(0):
+        ns, nd = ns.contiguous(), nd.contiguous()
+    if max_edges is None:
+        max_edges = max(1, min(p * ns_max * nd_max, MAX_EDGES))
+    rep = torch.empty((p, 4), dtype=torch.float64, device=dev)
+    cnt = torch.empty((p, 6), dtype=torch.int32, device=dev)
+    l = lib()
+    nbytes = l.balf_repeatability_batch_workspace_bytes(p, ns_max, nd_max, int(max_edges))
+    if nbytes == 0:
+        raise BalfHipError(f"balf_repeatability_batch: unsupported sizes P={p}, Ns={ns_max}, Nd={nd_max}, max_edges={max_edges}")
+    ws = ops._workspace("repeat_batch", dev, nbytes)
+    with torch.cuda.device(dev):
+        check(l.balf_repeatability_batch(src.data_ptr(), ns.data_ptr(), ns_max, src.shape[2], dst.data_ptr(), nd.data_ptr(),
+                                         nd_max, dst.shape[2], ns.stride(0), p, float(overlap_err), float(eps),
+                                         float(dist_match_thresh), float(radious_size), int(max_edges), rep.data_ptr(),
+                                         cnt.data_ptr(), ws.data_ptr(), ws.numel(), current_stream_ptr(dev)),
+              "balf_repeatability_batch")
+    return RepeatabilityBatch(rep[:, 0], rep[:, 1], rep[:, 2], rep[:, 3], cnt[:, 0], cnt[:, 1], cnt[:, 2], cnt[:, 3],
+                              cnt[:, 4], cnt[:, 5])
 
 
 def check_common_points(kpts, mask):

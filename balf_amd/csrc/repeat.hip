@@ -15,45 +15,15 @@
 //   rep_sort_kernel    stable LSD radix sort, descending by overlap => equal overlaps stay in flat-index order
 //   rep_greedy_kernel  one wave walks the sorted candidates 64 at a time; visited bitmaps in LDS; the error sum is
 //                      accumulated in the reference's order
-// The candidate count is data dependent, so balf_repeatability synchronises the stream once to read it.
+// The candidate count is data dependent and stays on the device.  The overlaps, the sort and the greedy walk are in
+// repeat_core.h, shared with the batched entry of repeat_batch.hip.
 #include "common.h"
+#include "common_mask.h"
 #include "homography.h"
+#include "repeat_core.h"
 
 namespace balf {
 namespace {
-
-constexpr double kPi = 3.141592653589793;
-constexpr double kEpsF64 = 2.220446049250313e-16;          // np.finfo(float).eps
-constexpr int kMaxPoints = 65536;                          // visited bitmaps live in LDS
-
-struct RepParams {
-    double thr, eps, dist_match, radius, max_dist;
-};
-
-__device__ __forceinline__ double inter_area(double R, double r, double d) {
-    if (d <= fabs(R - r)) { const double m = fmin(R, r); return kPi * (m * m); }
-    if (d >= r + R) return 0.0;
-    const double r2 = r * r, R2 = R * R, d2 = d * d;
-    const double alpha = acos((d2 + r2 - R2) / (2 * d * r));
-    const double beta = acos((d2 + R2 - r2) / (2 * d * R));
-    return r2 * alpha + R2 * beta - 0.5 * (r2 * sin(2 * alpha) + R2 * sin(2 * beta));
-}
-
-__device__ __forceinline__ void pair_overlaps(double sx, double sy, double sr, double tx, double ty, double tr,
-                                              const RepParams &p, double &single, double &multi, bool &possible) {
-    const double dx = sx - tx, dy = sy - ty;
-    const double dist = sqrt(dx * dx + dy * dy);
-    possible = dist <= p.dist_match;
-    single = 0.0; multi = 0.0;
-    if (dist > p.max_dist) return;
-    const double f = p.radius / (fmax(sr, tr) + kEpsF64);
-    double I = inter_area(f * sr, f * tr, dist);
-    double U = kPi * ((f * sr) * (f * sr)) + kPi * ((f * tr) * (f * tr)) - I + p.eps;
-    multi = I / U;
-    I = inter_area(p.radius, p.radius, dist);
-    U = kPi * (p.radius * p.radius) + kPi * (p.radius * p.radius) - I + p.eps;
-    single = I / U;
-}
 
 __global__ __launch_bounds__(256) void rep_count_kernel(const double *src, int ns, const double *dst, int nd, RepParams p,
                                                         int *cnt_s, int *cnt_m, int *poss) {
@@ -147,32 +117,9 @@ __global__ __launch_bounds__(64) void rep_greedy_kernel(const unsigned long long
         for (int k = lane; k < cap; k += 64) { corr[2 * k] = -1; corr[2 * k + 1] = -1; }
         return;
     }
-    for (int k = lane; k < kMaxPoints / 32; k += 64) { vis_x[k] = 0u; vis_y[k] = 0u; }
-    __syncthreads();
-    int found = 0;
-    double err = 0.0;
-    for (int base = 0; base < n_edges; base += 64) {
-        const int e = base + lane;
-        unsigned idx = 0; double w = 0.0;
-        if (e < n_edges) { idx = vals[e]; w = __longlong_as_double((long long)keys[e]); }
-        const int yi = (int)(idx / (unsigned)nd), xj = (int)(idx % (unsigned)nd);
-        const int lim = n_edges - base < 64 ? n_edges - base : 64;
-        for (int l = 0; l < lim; ++l) {
-            const int y = __shfl(yi, l), x = __shfl(xj, l);
-            const double wl = __shfl(w, l);
-            const bool taken = ((vis_x[x >> 5] >> (x & 31)) & 1u) || ((vis_y[y >> 5] >> (y & 31)) & 1u);
-            if (!taken) {
-                if (lane == 0) {
-                    vis_x[x >> 5] |= 1u << (x & 31);
-                    vis_y[y >> 5] |= 1u << (y & 31);
-                    if (found < cap) { corr[2 * found] = x; corr[2 * found + 1] = y; }
-                }
-                found += 1;
-                err += 1.0 - wl;
-            }
-            __syncthreads();        // single wave: orders lane 0's LDS update before the next read
-        }
-    }
+    int found;
+    double err;
+    rep_greedy_walk(keys, vals, n_edges, nd, vis_x, vis_y, kMaxPoints / 32, kMaxPoints / 32, corr, cap, found, err);
     if (lane == 0) { *found_out = found; *err_out = err; }
     for (int k = found + lane; k < cap; k += 64) { corr[2 * k] = -1; corr[2 * k + 1] = -1; }
 }
@@ -184,80 +131,16 @@ __global__ void homography_kernel(const double *pts, int n, const double *h, dou
     out[4 * i + 3] = pts[4 * i + 3];
 }
 
-// Stable LSD radix sort of (key, value) pairs, DESCENDING by the 64-bit key, 4 bits per pass, one workgroup of 16
-// waves.  Wave w owns the contiguous range [w * per, (w + 1) * per) of the input and walks it 64 elements at a time, so
-// "input order" is (wave, row, lane) and a pass keeps it among equal digits: per row the lane's rank among the lanes with
-// its digit comes from a ballot, per wave the digit counts go through a [digit][wave] table in LDS whose exclusive scan
-// (digit-major) gives every wave its output cursor per digit.  Passes whose digit is the same for all keys are skipped
-// (overlaps lie in [1 - overlap_err, 1]: the sign, exponent and leading mantissa digits agree), so the 16 possible passes
-// are ~11 in practice.  The pairs ping-pong between (k0, v0) and (k1, v1); the result always ends in (k1, v1).
+// Stable LSD radix sort of the candidate list, descending by overlap => equal overlaps stay in flat-index order
+// (rep_sort_pairs, repeat_core.h), one workgroup of 16 waves.  The result always ends in (k1, v1).
 // (Round 2 called hipcub::DeviceRadixSort here; the library now has no third-party device code.)
-constexpr int kSortWaves = 16;
 __global__ __launch_bounds__(kSortWaves * 64) void rep_sort_kernel(unsigned long long *k0, unsigned *v0, unsigned long long *k1,
                                                                   unsigned *v1, const int *n_dev, int max_edges) {
     __shared__ int hist[16][kSortWaves];
     __shared__ int uniform_digit;
     const int n = *n_dev;
     if (n <= 0 || n > max_edges) return;                          // nothing to sort / overflow (reported by rep_greedy_kernel)
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int per = ((n + kSortWaves - 1) / kSortWaves + 63) / 64 * 64;
-    const int lo = wave * per < n ? wave * per : n, hi = lo + per < n ? lo + per : n;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    unsigned long long *kin = k0, *kout = k1;
-    unsigned *vin = v0, *vout = v1;
-    for (int shift = 0; shift < 64; shift += 4) {
-        int cnt[16];
-#pragma unroll
-        for (int d = 0; d < 16; ++d) cnt[d] = 0;
-        for (int e0 = lo; e0 < hi; e0 += 64) {
-            const int e = e0 + lane;
-            const int dig = e < hi ? 15 - (int)((kin[e] >> shift) & 15ull) : -1;       // descending: largest digit first
-#pragma unroll
-            for (int d = 0; d < 16; ++d) cnt[d] += __popcll(__ballot(dig == d));
-        }
-        if (lane == 0) {
-#pragma unroll
-            for (int d = 0; d < 16; ++d) hist[d][wave] = cnt[d];
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            int run = 0, uni = -1;
-            for (int d = 0; d < 16; ++d) {
-                int tot = 0;
-                for (int w = 0; w < kSortWaves; ++w) { const int c = hist[d][w]; hist[d][w] = run; run += c; tot += c; }
-                if (tot == n) uni = d;
-            }
-            uniform_digit = uni;
-        }
-        __syncthreads();
-        const bool skip = uniform_digit >= 0;                    // every key has this digit: the pass would be the identity
-        if (!skip) {
-            int cur[16];
-#pragma unroll
-            for (int d = 0; d < 16; ++d) cur[d] = hist[d][wave];
-            for (int e0 = lo; e0 < hi; e0 += 64) {
-                const int e = e0 + lane;
-                unsigned long long k = 0; unsigned v = 0;
-                if (e < hi) { k = kin[e]; v = vin[e]; }
-                const int dig = e < hi ? 15 - (int)((k >> shift) & 15ull) : -1;
-                int dst = 0;
-#pragma unroll
-                for (int d = 0; d < 16; ++d) {
-                    const unsigned long long b = __ballot(dig == d);
-                    if (dig == d) dst = cur[d] + __popcll(b & below);
-                    cur[d] += __popcll(b);
-                }
-                if (e < hi) { kout[dst] = k; vout[dst] = v; }
-            }
-        }
-        __syncthreads();                                         // the pass's writes are visible to the whole workgroup; hist is free
-        if (!skip) {
-            unsigned long long *tk = kin; kin = kout; kout = tk;
-            unsigned *tv = vin; vin = vout; vout = tv;
-        }
-    }
-    if (kin != k1)                                               // (uniform) the sorted pairs sit in (k0, v0): copy
-        for (int e = threadIdx.x; e < n; e += kSortWaves * 64) { k1[e] = kin[e]; v1[e] = vin[e]; }
+    rep_sort_pairs(k0, v0, k1, v1, n, hist, &uniform_digit);
 }
 
 struct RepWs {
@@ -331,15 +214,9 @@ extern "C" int balf_apply_homography(const double *points_dev, int n, const doub
 }
 
 
-// ------------------------------------------------------------------------------------------------
-// create_common_region_masks (/root/reference/balf/benchmark_test/geometry_tools.py:7-26): the part of each image that
-// the other image covers.  The reference warps an all-ones image whose 15-pixel frame is zeroed with
-// cv2.warpPerspective (default flags: bilinear, constant-zero border), thresholds at 0.75 and zeroes the frame of the
-// result.  Restated here from OpenCV's algorithm: the output pixel (x, y) samples the input at M^-1 (x, y, 1), the
-// source coordinates are rounded to 1/32 pixel (INTER_TAB_SIZE = 32, round half to even), the four bilinear weights
-// are the exact products of those 5-bit fractions.  cv2 is not installed in the build container: parity with it is
-// UNPINNED (checked against the oracle's restatement of the same algorithm only).
-// ------------------------------------------------------------------------------------------------
+// create_common_region_masks (reference balf/benchmark_test/geometry_tools.py:7-26): the per-pixel body and the
+// inverse maps are in common_mask.h (shared with the batched point filter of repeat_batch.hip).  cv2 is not installed in
+// the build container: parity with it is UNPINNED (checked against the oracle's restatement of the same algorithm only).
 namespace {
 
 struct MaskArgs {
@@ -350,50 +227,11 @@ struct MaskArgs {
     double *out;
 };
 
-__device__ __forceinline__ double ones_inner(int y, int x, int h, int w, int b) {
-    return (y >= b && y < h - b && x >= b && x < w - b) ? 1.0 : 0.0;      // zero outside the image too
-}
-
-// fp contraction is OFF in this kernel and in invert3: every product and sum below is an individually rounded fp64
-// operation in source order, so that the CPU oracle (NumPy, no FMA) reproduces the 1/32-pixel rounding bit for bit and the
-// two {0,1} masks can be compared for equality.
 __global__ __launch_bounds__(256) void common_mask_kernel(MaskArgs a) {
-#pragma clang fp contract(off)
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= (long)a.h_out * a.w_out) return;
     const int y = (int)(i / a.w_out), x = (int)(i - (long)y * a.w_out);
-    double v = 0.0;
-    if (y >= a.border && y < a.h_out - a.border && x >= a.border && x < a.w_out - a.border) {
-        const double X0 = a.m[0] * x + a.m[1] * y + a.m[2];
-        const double Y0 = a.m[3] * x + a.m[4] * y + a.m[5];
-        double W = a.m[6] * x + a.m[7] * y + a.m[8];
-        W = W != 0.0 ? 32.0 / W : 0.0;
-        const double fx = fmax(-2147483648.0, fmin(2147483647.0, X0 * W));
-        const double fy = fmax(-2147483648.0, fmin(2147483647.0, Y0 * W));
-        const long long X = llrint(fx), Y = llrint(fy);                     // round half to even, like cvRound
-        const int sx = (int)(X >> 5), sy = (int)(Y >> 5);
-        const double ax = (double)(X & 31) * (1.0 / 32.0), ay = (double)(Y & 31) * (1.0 / 32.0);
-        const double s = ones_inner(sy, sx, a.h_in, a.w_in, a.border) * ((1.0 - ax) * (1.0 - ay)) +
-                         ones_inner(sy, sx + 1, a.h_in, a.w_in, a.border) * (ax * (1.0 - ay)) +
-                         ones_inner(sy + 1, sx, a.h_in, a.w_in, a.border) * ((1.0 - ax) * ay) +
-                         ones_inner(sy + 1, sx + 1, a.h_in, a.w_in, a.border) * (ax * ay);
-        v = s >= 0.75 ? 1.0 : 0.0;
-    }
-    a.out[i] = v;
-}
-
-// closed-form 3x3 inverse (adjugate / determinant), the form OpenCV's cv::invert takes for n <= 3
-bool invert3(const double *m, double *o) {
-#pragma clang fp contract(off)
-    const double a = m[0], b = m[1], c = m[2], d = m[3], e = m[4], f = m[5], g = m[6], h = m[7], i = m[8];
-    const double A = e * i - f * h, B = -(d * i - f * g), C = d * h - e * g;
-    const double det = a * A + b * B + c * C;
-    if (det == 0.0) return false;
-    const double r = 1.0 / det;
-    o[0] = A * r; o[1] = -(b * i - c * h) * r; o[2] = (b * f - c * e) * r;
-    o[3] = B * r; o[4] = (a * i - c * g) * r;  o[5] = -(a * f - c * d) * r;
-    o[6] = C * r; o[7] = -(a * h - b * g) * r; o[8] = (a * e - b * d) * r;
-    return true;
+    a.out[i] = common_mask_pixel(a.m, y, x, a.h_out, a.w_out, a.h_in, a.w_in, a.border);
 }
 
 }  // namespace
@@ -406,10 +244,7 @@ extern "C" int balf_common_region_masks(const double *h_dst_2_src_host, int h_sr
     // mask_src = warp(ones_dst, M = h_dst_2_src): samples ones_dst at M^-1 (x, y, 1)
     // mask_dst = warp(ones_src, M = inv(h_dst_2_src) / its [2,2]): samples ones_src at M^-1 = a multiple of h_dst_2_src
     MaskArgs ms{}, md{};
-    double inv_h[9];
-    if (!invert3(h_dst_2_src_host, ms.m)) return BALF_ERR_ARG;
-    for (int k = 0; k < 9; ++k) inv_h[k] = ms.m[k] / ms.m[8];               // the matrix the reference hands to cv2 ...
-    if (!invert3(inv_h, md.m)) return BALF_ERR_ARG;                          // ... and cv2 inverts again
+    if (!common_mask_maps(h_dst_2_src_host, ms.m, md.m)) return BALF_ERR_ARG;
     ms.h_out = h_src; ms.w_out = w_src; ms.h_in = h_dst; ms.w_in = w_dst; ms.border = border; ms.out = mask_src_dev;
     md.h_out = h_dst; md.w_out = w_dst; md.h_in = h_src; md.w_in = w_src; md.border = border; md.out = mask_dst_dev;
     common_mask_kernel<<<balf_ceil_div((long)h_src * w_src, 256), 256, 0, st>>>(ms);

@@ -327,6 +327,39 @@ int balf_apply_homography(const double *points_dev, int n, const double *h_dev, 
 int balf_common_region_masks(const double *h_dst_2_src_host, int h_src, int w_src, int h_dst, int w_dst, int border,
                              double *mask_src_dev, double *mask_dst_dev, void *stream);
 
+/* ---- batched HSequences evaluation (check_val_hsequences_repeatability, balf/utils/train_utils.py:308-413) ---------------
+ * P independent image pairs, stream-ordered, nothing read back: every per-pair count is read on the device.
+ *
+ * balf_common_points_batch: what train_utils.py:350-369 does after detection, per pair p.  src_dev [P,ns_max,4] /
+ * dst_dev [P,nd_max,4] float64 rows (x, y, radius, score), the first ns_dev[p] / nd_dev[p] of them used (clamped to
+ * [0, n_max]); h_dst_2_src_dev [P,9] row-major, shapes_dev [P,4] int32 = (h_src, w_src, h_dst, w_dst).  A source row is kept
+ * iff mask_src[round(y) - 1, round(x) - 1] != 0 (check_common_points: round half to even, a negative index wraps like
+ * NumPy's, an index NumPy would reject drops the row), a destination row likewise against mask_dst, where the masks are
+ * those balf_common_region_masks computes for the pair with border 15, evaluated at the point only (the two inverse maps are
+ * computed on the device in the same operations).  Kept rows keep their order: src_out_dev [P,ns_max,4] the kept source rows,
+ * dst_out_dev [P,nd_max,4] the kept destination rows warped as balf_apply_homography does (score carried); rows past the kept
+ * count are 0.  kept_dev [P,2] = kept counts (source, destination); valid_dev[P] = both > 0.  A singular h_dst_2_src keeps
+ * nothing.  No workspace.
+ *
+ * balf_repeatability_batch: balf_repeatability for each pair, bit-identical to it.  Rows of src_dev / dst_dev start with
+ * (x, y, radius), src_stride / dst_stride doubles apart (>= 3); pair p's rows start at row p * ns_max / p * nd_max, its counts
+ * are ns_dev[p * count_stride] / nd_dev[p * count_stride] (clamped to [0, n_max]).  max_edges bounds the candidate pairs of
+ * each scale summed over ALL pairs: pair p's candidates take the slice after those of pairs < p, and a pair whose slice does
+ * not end within max_edges reports found = -1 (and NaN rep / err) for that scale, its candidate count still written.
+ * Outputs: rep_dev [P,4] float64 = (rep_single_scale, rep_multi_scale, error_overlap_single_scale,
+ * error_overlap_multi_scale) with compute_repeatability's formulas (rep = found / total * 100, NaN for total 0; err = 0 for
+ * found 0, else the error sum / (found + DBL_EPSILON)); counts_dev [P,6] int32 = (num_points_single_scale,
+ * num_points_multi_scale, possible_matches, total_num_points = min(ns, nd), candidates single scale, candidates multi scale).
+ * ns_max, nd_max <= 65536 (BALF_ERR_ARG), ns_max * nd_max < 2^31 (BALF_ERR_SHAPE), 1 <= P <= 65535. */
+int balf_common_points_batch(const double *src_dev, const int32_t *ns_dev, int ns_max, const double *dst_dev,
+                             const int32_t *nd_dev, int nd_max, int P, const double *h_dst_2_src_dev, const int32_t *shapes_dev,
+                             double *src_out_dev, double *dst_out_dev, int32_t *kept_dev, int32_t *valid_dev, void *stream);
+size_t balf_repeatability_batch_workspace_bytes(int P, int ns_max, int nd_max, int max_edges);
+int balf_repeatability_batch(const double *src_dev, const int32_t *ns_dev, int ns_max, int src_stride, const double *dst_dev,
+                             const int32_t *nd_dev, int nd_max, int dst_stride, int count_stride, int P, double overlap_err,
+                             double eps, double dist_match_thresh, double radius_size, int max_edges, double *rep_dev,
+                             int32_t *counts_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+
 /* ---- measurement aid (not part of the data path) ---------------------------------------------
  * Between balf_profile_begin() and balf_profile_end() every kernel launch of the library is bracketed
  * by a hipEvent pair on its launch stream.  balf_profile_end() waits for those events and returns,
