@@ -3,6 +3,8 @@
 // layout.h.  Replaces MLP_MA_DECODER.load_state_dict as reached from
 // /root/reference/balf/model/get_model.py:60-67 (tensor names and shapes are that state_dict's).
 #include <math.h>
+#include <algorithm>
+#include <cmath>
 #include <string.h>
 
 #include <string>
@@ -150,6 +152,21 @@ void fold_ln(const float *W, const float *b, const float *gamma, const float *be
     }
 }
 
+// The gating unit's LayerNorm -> token mix is the one LayerNorm -> Linear pair that is NOT folded (the Linear acts on the token
+// axis, the affine part on the channels): the split-f16 kernels split n * gamma + beta and the mix weights separately, and a
+// checkpoint that carries this pair as (gamma, beta) * 2^-k with W * 2^k -- the same function -- pushed one of the two operands
+// into the f16 subnormals (measured before this: 1.3e-4 on the score map at k = 10 with the probes passing, 2e-3 at k = 14).
+// So the pair is brought back to O(1) here by an exact power of two: (gamma, beta) * s and W / s, s = 2^-e with e the exponent
+// of max(|gamma|, |beta|).  Checkpoints whose largest gain lies in [1/4, 4) keep s = 1, i.e. the bits they always had.
+float gate_pair_scale(const float *gamma, const float *beta, int C) {
+    float m = 0.0f;
+    for (int c = 0; c < C; ++c) m = fmaxf(m, fmaxf(fabsf(gamma[c]), fabsf(beta[c])));
+    if (!(m > 0.0f) || !std::isfinite(m)) return 1.0f;
+    const int e = std::ilogb(m);
+    if (e >= -2 && e < 2) return 1.0f;
+    return std::ldexp(1.0f, -std::min(std::max(e, -100), 100));
+}
+
 }  // namespace
 
 extern "C" int balf_num_state_tensors(void) { return (int)table().size(); }
@@ -212,9 +229,21 @@ extern "C" int balf_pack_weights(const float *const *tensors, int n_tensors, int
             copy(blob + B.d1_b, bf.data(), 2 * C);
             copy(blob + B.gln_g, u[4], C);
             copy(blob + B.gln_b, u[5], C);
-            if (f16 && fmt32) pack_frags32(blob + B.mix_w, u[6], kTokens, kTokens, kTokens, false, /*token_rows=*/s == 0);
-            else if (f16) pack_frags16(blob + B.mix_w, u[6], kTokens, kTokens, kTokens, false);
-            else pack_frags(blob + B.mix_w, u[6], kTokens, kTokens, kTokens);
+            const float *mixw = u[6];
+            std::vector<float> mixs;
+            const float gs = f16 ? gate_pair_scale(u[4], u[5], C) : 1.0f;    // (the fp32 kernels have no operand range to leave)
+            if (gs != 1.0f) {
+                for (int c = 0; c < C; ++c) {
+                    blob[B.gln_g + c] *= gs;
+                    blob[B.gln_b + c] *= gs;
+                }
+                mixs.assign(u[6], u[6] + (size_t)kTokens * kTokens);
+                for (float &w : mixs) w *= 1.0f / gs;
+                mixw = mixs.data();
+            }
+            if (f16 && fmt32) pack_frags32(blob + B.mix_w, mixw, kTokens, kTokens, kTokens, false, /*token_rows=*/s == 0);
+            else if (f16) pack_frags16(blob + B.mix_w, mixw, kTokens, kTokens, kTokens, false);
+            else pack_frags(blob + B.mix_w, mixw, kTokens, kTokens, kTokens);
             copy(blob + B.mix_b, u[7], kTokens);
             pack(blob + B.d2_w, u[8], C, C, C);
             copy(blob + B.d2_b, u[9], C);

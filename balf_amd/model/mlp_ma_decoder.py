@@ -465,7 +465,17 @@ class MLP_MA_DECODER(nn.Module):
         max-abs score-map difference and raises if it exceeds ``tol`` or if the f16 path produced a non-finite value.
         Worth one call per new checkpoint: every MFMA operand is carried as two f16 halves, so an activation or
         weight beyond +-6.5e4 saturates (split16.h) -- LayerNorm keeps most operands O(1), but the stage inputs, the
-        gated branch, the RCAB hidden layer and the head input scale with the checkpoint's weights."""
+        gated branch, the RCAB hidden layer and the head input scale with the checkpoint's weights.
+
+        What the comparison does and does not see (the load-time probes are this method on three 128x128 images).  LARGE
+        operands: covered -- they end non-finite or far beyond ``tol`` (tests/test_forward_gpu.py, x3e4 and up).  SMALL
+        ones lose the low half silently (below ~2^-3 it drops bits, near 1e-4 it is gone): an operand pair at 2^-10 of its
+        usual size measured 1.3e-4 on a caller's image while the probes passed, and the probes tripped only from 2^-12
+        (weights) / 2^-14 (activations) on.  ``tol`` is a bound on THIS input, not on the next one, and an error between
+        2e-5 and ``tol`` passes.  The packer therefore leaves no LayerNorm -> Linear pair to the checkpoint's
+        parameterisation (folded, or normalised by a power of two: weights.hip); operands that no LayerNorm precedes and
+        that are merely small (a residual branch at 2^-12, near-constant channels) measured 3e-6
+        (tests/test_checkpoint_family_gpu.py, profiles/checkpoint_family.json)."""
         keep = self.precision
         nested = getattr(self, "_validating", False)
         try:

@@ -259,3 +259,117 @@ def poster_u8():
 
 
 POSTER_FLAT = {"black": (20, 140, 20, 180), "white": (20, 140, 220, 380)}   # interiors (y0, y1, x0, x1) of two constant rectangles
+
+
+# ---- a family of checkpoints derived from the synthetic one (tests/test_checkpoint_family*.py, tools/checkpoint_family.py) ----
+# Every accuracy figure of the split-f16 forward was taken on ONE weight distribution (synth.synthetic_state_dict: unit-gain
+# Gaussians, LayerNorm gains near 1).  The members below move operands away from O(1), mostly DOWN, where the f16 halves lose
+# bits without any trap (csrc/split16.h).  A member is (id, kind, spec); family_state(sd0, member) builds its state dict.
+#
+# kind "exact": a LayerNorm -> Linear pair re-parameterised by a power of two -- the norm's weight and bias times 2^-k, the
+#   Linear's weight times 2^k (bias untouched; "up": the other way round, so that the weights become small).  Exact in fp32:
+#   the reference's output is bit-identical to the base member's (tests/test_checkpoint_family.py proves it per member).
+#   spec = (direction, k, [(norm prefix, linear prefix), ...]).
+# kind "dist": a change of the weight distribution, not function-preserving; spec = (name, parameter).
+_F_RSH = "residual_split_head_multi_axis_gmlp_layer"
+_F_RCAB = "residual_channel_attention_block"
+FAMILY_KS = (0, 4, 8, 10, 12, 14)
+FAMILY_STAGES = (1, 2, 3, 4)
+FAMILY_DIRECTIONS = ("down", "up")       # down: norm x 2^-k, Linear x 2^k (small activations); up: small weights
+# pair name -> (norm, Linear) below "down<stage>."; the gate pairs' Linear mixes the 64 TOKENS of a group (8x8), the others
+# act on the channels
+FAMILY_PAIRS = {
+    "rsh": (f"{_F_RSH}.norm", f"{_F_RSH}.dense1"),
+    "grid": (f"{_F_RSH}.grid_gmlp_layer.norm", f"{_F_RSH}.grid_gmlp_layer.dense1"),
+    "block": (f"{_F_RSH}.block_gmlp_layer.norm", f"{_F_RSH}.block_gmlp_layer.dense1"),
+    "rcab": (f"{_F_RCAB}.norm", f"{_F_RCAB}.conv1"),
+    "grid_gate": (f"{_F_RSH}.grid_gmlp_layer.grid_gating_unit.norm", f"{_F_RSH}.grid_gmlp_layer.grid_gating_unit.dense"),
+    "block_gate": (f"{_F_RSH}.block_gmlp_layer.block_gating_unit.norm", f"{_F_RSH}.block_gmlp_layer.block_gating_unit.dense"),
+}
+FAMILY_BASE = ("base", "exact", ("down", 0, []))
+
+
+def family_exact_members():
+    """The base member (k = 0), every pair of every stage at every k > 0 in both directions one at a time, and all six pairs of
+    one stage at once ("all")."""
+    out = [FAMILY_BASE]
+    for s in FAMILY_STAGES:
+        for name in list(FAMILY_PAIRS) + ["all"]:
+            pairs = [(f"down{s}.{n}", f"down{s}.{l}") for n, l in (FAMILY_PAIRS.values() if name == "all" else [FAMILY_PAIRS[name]])]
+            for d in FAMILY_DIRECTIONS:
+                for k in FAMILY_KS[1:]:
+                    out.append((f"{name}.s{s}.{d}{k}", "exact", (d, k, pairs)))
+    return out
+
+
+def family_dist_members():
+    return [("heavy_tails", "dist", ("heavy_tails", None)), ("row_gains", "dist", ("row_gains", None)),
+            ("row_gains_rms", "dist", ("row_gains", "rms")),
+            ("small_residual.k6", "dist", ("small_residual", 6)), ("small_residual.k12", "dist", ("small_residual", 12)),
+            ("flat_channels", "dist", ("flat_channels", None))]
+
+
+def family_touched_keys(member):
+    """The state-dict keys an exact member changes."""
+    _, kind, spec = member
+    assert kind == "exact"
+    return [k for n, l in spec[2] for k in (n + ".weight", n + ".bias", l + ".weight")]
+
+
+def _is_linear_weight(name, v):
+    return name.endswith(".weight") and v.dim() == 2
+
+
+def family_state(sd0, member):
+    """The member's state dict (new tensors where it differs from ``sd0``, which is left alone)."""
+    mid, kind, spec = member
+    sd = dict(sd0)
+    if kind == "exact":
+        d, k, pairs = spec
+        f = 2.0 ** (-k if d == "down" else k)
+        for n, l in pairs:
+            sd[n + ".weight"] = sd0[n + ".weight"] * f
+            sd[n + ".bias"] = sd0[n + ".bias"] * f
+            sd[l + ".weight"] = sd0[l + ".weight"] * (1.0 / f)
+        return sd
+    what, par = spec
+    for i, (name, v) in enumerate(sd0.items()):
+        rng = np.random.default_rng([WEIGHT_SEED, 77, i])
+        if what == "heavy_tails" and _is_linear_weight(name, v):
+            # 1 % of the entries eight times as large, then back to the tensor's former RMS
+            w = v.double().numpy().copy()
+            w[rng.random(w.shape) < 0.01] *= 8.0
+            w *= np.sqrt((v.double().numpy() ** 2).mean() / (w ** 2).mean())
+            sd[name] = torch.from_numpy(w.astype(np.float32))
+        elif what == "row_gains" and _is_linear_weight(name, v):
+            # every output channel of every Linear with a gain 2^u of its own, u uniform in -4 .. 4.  As it stands the gains
+            # compound (RMS gain ~6 per Linear): stage outputs pass 65504 from stage 2 on, the logits reach 1e8 and the score map
+            # is one-hot -- a member for the guard's LARGE end.  "rms": the tensor is brought back to its former RMS, which keeps
+            # the activations O(1) and the score map soft while rows of one matrix still differ by up to 2^8.
+            u = rng.integers(-4, 5, size=(v.shape[0], 1))
+            w = v.double() * torch.from_numpy(2.0 ** u.astype(np.float64))
+            if par == "rms":
+                w = w * torch.sqrt((v.double() ** 2).mean() / (w ** 2).mean())
+            sd[name] = w.float()
+        elif what == "small_residual" and f".{_F_RCAB}.conv2." in name:
+            # the RCAB branch t = conv2(...) 2^-k of its size: the mirror of test_forward_gpu.py's x40 checkpoint
+            sd[name] = v * 2.0 ** -par
+        elif what == "flat_channels" and ".norm.weight" in name and not name.startswith("detector_head"):
+            # a quarter of every LayerNorm's channels nearly constant: gain 2^-12
+            g = v.clone()
+            g[torch.from_numpy(rng.permutation(v.numel())[:v.numel() // 4].copy())] = 2.0 ** -12
+            sd[name] = g
+    return sd
+
+
+FAMILY_INPUT = (128, 192, 31, "im1", 176, 288)       # H, W, noise seed, natural.npz image, top-left corner of its crop
+
+
+def family_input(golden_dir):
+    """[2,3,128,192]: cases.forward_input noise and a crop of the photograph im1 (natural.npz), so that the check is on a caller's
+    image and not on the three load-time probe images of the module."""
+    import os
+    h, w, seed, name, y0, x0 = FAMILY_INPUT
+    im = np.load(os.path.join(golden_dir, "natural.npz"))[name + ".u8"][y0:y0 + h, x0:x0 + w]
+    photo = torch.from_numpy((im / 255.0).astype(np.float32)).permute(2, 0, 1)
+    return torch.cat([forward_input(1, h, w, seed), photo[None]]).contiguous()
