@@ -17,6 +17,7 @@ PREC_FP32, PREC_FP16 = 0, 1
 MAX_NMS_SIZE, MAX_TOPK = 32, 16384
 PYR_SRC_U8, PYR_SRC_F32, PYR_SRC_LEVEL = 0, 1, 2                   # include/balf_hip.h: balf_pyramid_level
 PYR_MAX_RADIUS, MAX_PYRAMID_LEVELS = 8, 32
+VAL_LEG_GREEDY, VAL_LEG_WINDOW = 0, 1                              # include/balf_hip.h: balf_val_points
 STATUS_SCORE, STATUS_RANGE, STATUS_SE, STATUS_WORDS = 0, 1, 2, 4      # include/balf_hip.h: balf_forward_status
 
 # name -> (restype, argtypes); kept in step with include/balf_hip.h (tests/test_abi.py checks)
@@ -76,6 +77,8 @@ PROTOTYPES = {
     "balf_repeatability_batch_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "balf_repeatability_batch": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, C.c_double, C.c_double, C.c_double,
                                      C.c_double, _i, _vp, _vp, _vp, _sz, _vp]),
+    "balf_val_points_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i, _i]),
+    "balf_val_points": (_i, [_fp, _i, _i, _fp, _i, _i, _i, _vp, _i, C.c_float, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "balf_profile_num_slots": (_i, []),
     "balf_profile_slot_name": (C.c_char_p, [_i]),
     "balf_profile_begin": (_i, []),

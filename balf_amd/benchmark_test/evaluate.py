@@ -89,3 +89,25 @@ def evaluate_pairs(src_pts, src_count, dst_pts, dst_count, h_dst_2_src, shapes, 
     cp = common_points_batch(src_pts, src_count, dst_pts, dst_count, h_dst_2_src, shapes)
     r: RepeatabilityBatch = compute_repeatability_batch(cp.src, cp.kept[:, 0], cp.dst_to_src, cp.kept[:, 1], **repeat_kw)
     return PairEvaluation(*r, cp.valid, cp.kept)
+
+
+def evaluate_val_pairs(prob_src, prob_dst, h_dst_2_src, nms_size=15, num_points=25, leg="greedy", conf_thresh=0.015,
+                       **repeat_kw) -> PairEvaluation:
+    """The per-pair body of ``check_val_repeatability`` (reference balf/utils/train_utils.py:232-283) after the forward, for P
+    pairs at once: score maps ``prob_src`` [P,Hs,Ws] / ``prob_dst`` [P,Hd,Wd] fp32, ``h_dst_2_src`` [P,3,3] float64, on the
+    GPU.  ``leg='greedy'`` is the loop's main evaluation (``get_nms_score_map_from_score_map`` with ``conf_thresh``, times
+    the common-region mask, ``get_point_coordinates``), ``leg='window'`` its ``compute_repeatability_with_maximum_filter``
+    (``apply_nms`` instead).  Unlike :func:`evaluate_pairs` the ``num_points`` best are chosen AFTER the mask and come out in
+    raster order (``ops.val_points``); then :func:`~balf_amd.benchmark_test.repeatability_tools.compute_repeatability_batch`
+    (``repeat_kw``).  Returns the same tuple as :func:`evaluate_pairs`, device tensors: ``kept`` [P,2] are the selected
+    counts, ``valid`` is 1 everywhere (the reference's loop skips no pair: the selection never returns an empty list).
+    Nothing synchronises or is read back; the call can be captured with ``torch.cuda.graph``."""
+    from .. import ops
+    dev = prob_src.device if isinstance(prob_src, torch.Tensor) else None
+    if isinstance(h_dst_2_src, torch.Tensor) and h_dst_2_src.dtype != torch.float64:
+        h_dst_2_src = h_dst_2_src.to(torch.float64)
+    elif not isinstance(h_dst_2_src, torch.Tensor):
+        h_dst_2_src = torch.as_tensor(np.asarray(h_dst_2_src, dtype=np.float64)).to(dev)   # (host -> device: not capturable)
+    src, dst, count = ops.val_points(prob_src, prob_dst, h_dst_2_src.contiguous(), nms_size, num_points, leg, conf_thresh)
+    r: RepeatabilityBatch = compute_repeatability_batch(src, count[:, 0], dst, count[:, 1], **repeat_kw)
+    return PairEvaluation(*r, torch.ones_like(count[:, 0]), count)

@@ -737,6 +737,15 @@ int nms_select(const float *prob_dev, int B, int Hp, int Wp, int crop_y, int cro
 }
 }  // namespace
 
+// The survivor list alone, no crop and no border frame: apply_nms of whole maps, as balf_val_points (val_points.hip) needs it.
+// counts [B] (cleared here) and surv [B, H*W] are the caller's.
+int balf_window_survivors_launch(const float *prob_dev, int B, int H, int W, int nms_size, int2 *surv, int *counts,
+                                 hipStream_t st) {
+    if (balf_fill_u32(counts, 0u, (size_t)B, st) != BALF_OK) return BALF_ERR_LAUNCH;
+    NmsArgs a{prob_dev, H, W, 0, 0, H, W, 0, nms_size, surv, counts, (long)H * W, nullptr};
+    return launch_nms_tiles(a, B, st);
+}
+
 extern "C" int balf_nms_topk(const float *prob_dev, int B, int Hp, int Wp, int crop_y, int crop_x, int H, int W,
                              int border, int nms_size, int K, int32_t *idx_dev, float *score_dev,
                              int32_t *count_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {

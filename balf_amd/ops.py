@@ -346,3 +346,49 @@ def multiscale_merge(idx: torch.Tensor, score: torch.Tensor, count: torch.Tensor
                                           int(n), int(bool(order_yx)), pts.data_ptr(), cnt.data_ptr(),
                                           current_stream_ptr(dev)), "balf_multiscale_merge")
     return pts, cnt
+
+
+# ---- synthetic-pair validation (balf_amd/benchmark_test/evaluate.py drives this) -------------------------------------------
+VAL_LEGS = {"greedy": _lib.VAL_LEG_GREEDY, "window": _lib.VAL_LEG_WINDOW}
+
+
+def val_points(prob_src: torch.Tensor, prob_dst: torch.Tensor, h_dst_2_src: torch.Tensor, nms_size: int, num_points: int,
+               leg: str, conf_thresh: float = 0.015):
+    """The point selection of ``check_val_repeatability`` for P pairs (balf_val_points in include/balf_hip.h): score maps
+    ``prob_src`` [P,Hs,Ws] / ``prob_dst`` [P,Hd,Wd] fp32 and ``h_dst_2_src`` [P,3,3] (or [P,9]) float64 on the GPU ->
+    (src_pts [P,K,4] float64, dst_to_src_pts [P,K,4] float64, count [P,2] int32).  ``leg``: ``'greedy'`` (nms_fast on the
+    candidates >= ``conf_thresh``) or ``'window'`` (apply_nms).  ``num_points`` beyond a map's pixels raises IndexError like
+    the reference.  Nothing is read back."""
+    if leg not in VAL_LEGS:
+        raise ValueError(f"leg must be one of {sorted(VAL_LEGS)}, got {leg!r}")
+    for t, name in ((prob_src, "prob_src"), (prob_dst, "prob_dst"), (h_dst_2_src, "h_dst_2_src")):
+        require_gpu_tensor(t, name)
+    for t, name in ((prob_src, "prob_src"), (prob_dst, "prob_dst")):
+        if t.dtype != torch.float32 or t.dim() != 3:
+            raise BalfHipError(f"{name} must be a [P,H,W] float32 tensor")
+    p, hs, ws_ = prob_src.shape
+    dev = prob_src.device
+    if prob_dst.shape[0] != p or p == 0 or prob_dst.device != dev:
+        raise BalfHipError(f"prob_src and prob_dst must hold the same number (> 0) of pairs on one device")
+    hd, wd = prob_dst.shape[1:]
+    if h_dst_2_src.dtype != torch.float64 or tuple(h_dst_2_src.shape) not in ((p, 3, 3), (p, 9)) or h_dst_2_src.device != dev:
+        raise BalfHipError(f"h_dst_2_src must be a [{p},3,3] float64 tensor on {dev}")
+    k = int(num_points)
+    if k <= 0:
+        raise ValueError(f"num_points must be positive, got {num_points}")
+    if k > min(hs * ws_, hd * wd):
+        raise IndexError(f"index {k - 1} is out of bounds for axis 0 with size {min(hs * ws_, hd * wd)}")
+    l = lib()
+    nbytes = l.balf_val_points_workspace_bytes(p, hs, ws_, hd, wd, VAL_LEGS[leg], int(nms_size), k)
+    if nbytes == 0:
+        raise BalfHipError(f"balf_val_points: unsupported sizes P={p}, {hs}x{ws_} / {hd}x{wd}, leg={leg}, nms_size={nms_size}, "
+                           f"num_points={k}")
+    src = torch.empty((p, k, 4), dtype=torch.float64, device=dev)
+    dst = torch.empty((p, k, 4), dtype=torch.float64, device=dev)
+    count = torch.empty((p, 2), dtype=torch.int32, device=dev)
+    ws = _workspace("val_points", dev, nbytes)
+    with torch.cuda.device(dev):
+        check(l.balf_val_points(prob_src.data_ptr(), hs, ws_, prob_dst.data_ptr(), hd, wd, p, h_dst_2_src.data_ptr(),
+                                VAL_LEGS[leg], float(conf_thresh), int(nms_size), k, src.data_ptr(), dst.data_ptr(),
+                                count.data_ptr(), ws.data_ptr(), ws.numel(), current_stream_ptr(dev)), "balf_val_points")
+    return src, dst, count

@@ -360,6 +360,33 @@ int balf_repeatability_batch(const double *src_dev, const int32_t *ns_dev, int n
                              double eps, double dist_match_thresh, double radius_size, int max_edges, double *rep_dev,
                              int32_t *counts_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
 
+/* ---- batched synthetic-pair validation (check_val_repeatability, balf/utils/train_utils.py:205-306) -----------------------
+ * balf_val_points: the point selection of that loop for P pairs x 2 sides, stream-ordered, nothing read back.  Per side
+ *   nms    = the NMS map of the side's score map, no border frame:
+ *              BALF_VAL_LEG_GREEDY  get_nms_score_map_from_score_map (repeatability_tools.py:82-100): candidates >= conf_thresh
+ *                                   (> 0), nms_fast with dist_thresh = nms_size (<= 16), survivors scattered into a zero map
+ *                                   (balf_greedy_nms' kept list; conf_thresh is ignored by the window leg);
+ *              BALF_VAL_LEG_WINDOW  apply_nms(prob, nms_size) (:19-23), 1 <= nms_size <= BALF_MAX_NMS_SIZE;
+ *   masked = nms * the side's common-region mask (balf_common_region_masks for the pair with border 15, evaluated at the NMS
+ *            survivors only, the inverse maps computed on the device in the same operations; a singular h_dst_2_src gives
+ *            empty masks);
+ *   rows   = get_point_coordinates(masked, num_points = K, 'xysr') (geometry_tools.py:86-125): the first K pixels in RASTER
+ *            order with masked >= the K-th largest value of masked.  When that value is <= 0 the threshold is the smallest
+ *            positive value (fewer than K positive values: exactly those, count < K), and with no positive value at all it
+ *            is 0: the first K raster pixels of the whole map with score 0.
+ * prob_src_dev [P,h_src,w_src] / prob_dst_dev [P,h_dst,w_dst] fp32 (scores are probabilities, >= +0), h_dst_2_src_dev [P,9]
+ * float64 row-major.  src_pts_dev / dst_pts_dev [P,K,4] float64 rows (x, y, 1.0, score); the destination rows are warped
+ * into the source image as balf_apply_homography does (x', y', radius, score).  count_dev [P,2] int32 = rows of (source,
+ * destination); rows past the count are 0.  The layout is what balf_repeatability_batch takes (strides 4, count_stride 2).
+ * K <= BALF_MAX_TOPK, K <= h * w of both sides (the reference raises IndexError; BALF_ERR_SHAPE), 1 <= P <= 65535; greedy leg:
+ * ceil(h / (nms_size + 1)) * ceil(w / (nms_size + 1)) <= BALF_MAX_TOPK (a bound on the points it can keep; BALF_ERR_SHAPE). */
+#define BALF_VAL_LEG_GREEDY 0
+#define BALF_VAL_LEG_WINDOW 1
+size_t balf_val_points_workspace_bytes(int P, int h_src, int w_src, int h_dst, int w_dst, int leg, int nms_size, int K);
+int balf_val_points(const float *prob_src_dev, int h_src, int w_src, const float *prob_dst_dev, int h_dst, int w_dst, int P,
+                    const double *h_dst_2_src_dev, int leg, float conf_thresh, int nms_size, int K, double *src_pts_dev,
+                    double *dst_pts_dev, int32_t *count_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+
 /* ---- measurement aid (not part of the data path) ---------------------------------------------
  * Between balf_profile_begin() and balf_profile_end() every kernel launch of the library is bracketed
  * by a hipEvent pair on its launch stream.  balf_profile_end() waits for those events and returns,
