@@ -111,3 +111,125 @@ def evaluate_val_pairs(prob_src, prob_dst, h_dst_2_src, nms_size=15, num_points=
     src, dst, count = ops.val_points(prob_src, prob_dst, h_dst_2_src.contiguous(), nms_size, num_points, leg, conf_thresh)
     r: RepeatabilityBatch = compute_repeatability_batch(src, count[:, 0], dst, count[:, 1], **repeat_kw)
     return PairEvaluation(*r, torch.ones_like(count[:, 0]), count)
+
+
+# ---- the resize protocol (reference configs/config_hpatches.py: parse_resize_eval_config) -----------------------------------
+def evaluate_resize_pairs(src_pts, src_count, dst_pts, dst_count, h, shapes, keep_k_points=1000, distance_thresh=5,
+                          h_inv=None, order="xyrs"):
+    """The resize-protocol metric of P pairs after detection, device in, device out:
+    :func:`~balf_amd.benchmark_test.repeatability_tools.compute_resize_repeatability_batch` on ``[P,N,4]`` float64 rows
+    (x, y, radius, score) plus counts, the layout of this package's detectors (``order='rcp'`` for the reference's
+    (row, col, prob) rows).  ``h`` [P,3,3] maps source to destination pixels; pass ``h_inv`` too (both device tensors) to keep
+    the call free of host work and capturable with ``torch.cuda.graph``.  Returns a ``ResizeRepeatabilityBatch`` of device
+    tensors; nothing is read back."""
+    from .repeatability_tools import compute_resize_repeatability_batch
+    return compute_resize_repeatability_batch(src_pts, src_count, dst_pts, dst_count, h, shapes, keep_k_points,
+                                              distance_thresh, h_inv=h_inv, order=order)
+
+
+def detection_rows(idx, score, count, w):
+    """``detect_batch_u8``'s (idx [B,K] flat ``y * w + x``, score [B,K], count [B]) -> rows [B,K,4] float64 (x, y, 1.0, score);
+    slots past an image's count are never read by the evaluation."""
+    i = idx.to(torch.int64).clamp_(min=0)
+    rows = torch.empty(idx.shape + (4,), dtype=torch.float64, device=idx.device)
+    rows[..., 0] = i % w
+    rows[..., 1] = torch.div(i, w, rounding_mode="floor")
+    rows[..., 2] = 1.0
+    rows[..., 3] = score
+    return rows
+
+
+def _as_rgb_u8(img):
+    """A loader image (``*_BGR``: gray [H,W] / [H,W,1] or BGR [H,W,3] uint8) as the detector's input: gray as it is, colour
+    with the channels reversed to RGB (the reference converts BGR to RGB before detection)."""
+    a = np.asarray(img)
+    if a.ndim == 3 and a.shape[2] == 1:
+        a = a[:, :, 0]
+    return np.ascontiguousarray(a[:, :, ::-1]) if a.ndim == 3 else np.ascontiguousarray(a)
+
+
+def _resize_chunk(seqs, model, device, resize_shape, top_k, pixel_threshold, nms_size, border_size, batch_size):
+    """One chunk of sequences -> [P, 6] float64 on the host (one read), pairs in (sequence, destination) order."""
+    from types import SimpleNamespace
+    from ..datasets import dataset_utils
+    from ..pipeline import detect_batch_u8
+    th, tw = int(resize_shape[0]), int(resize_shape[1])
+    args = SimpleNamespace(resize_shape=[th, tw])
+    images, pair_src, pair_dst, hs = [], [], [], []
+    for s in seqs:
+        src = _as_rgb_u8(s['im_src_BGR'])
+        i_src = len(images)
+        images.append(src)
+        for dst, h in zip(s['images_dst_BGR'], s['homographies']):
+            dst = _as_rgb_u8(dst)
+            pair_src.append(i_src)
+            pair_dst.append(len(images))
+            images.append(dst)
+            hs.append(dataset_utils.adapt_homography_to_preprocessing(
+                {'homography': np.asarray(h), 'shape': np.array(src.shape[:2]), 'warped_shape': np.array(dst.shape[:2])}, args))
+    if not hs:
+        return np.zeros((0, 6))
+    if len({im.ndim for im in images}) != 1:                     # gray and colour in one chunk: gray replicated to 3 channels
+        images = [im if im.ndim == 3 else np.repeat(im[:, :, None], 3, axis=2) for im in images]
+    batch = dataset_utils.ratio_preserving_resize_batch(images, (th, tw), device)
+    rows, counts = [], []
+    for b0 in range(0, batch.shape[0], batch_size):
+        idx, score, count, _ = detect_batch_u8(model, batch[b0:b0 + batch_size], border_size, nms_size, top_k)
+        rows.append(detection_rows(idx, score, count, tw))
+        counts.append(count)
+    rows, counts = torch.cat(rows), torch.cat(counts)
+    i_s = torch.tensor(pair_src, dtype=torch.long, device=rows.device)
+    i_d = torch.tensor(pair_dst, dtype=torch.long, device=rows.device)
+    shapes = np.tile(np.asarray([th, tw, th, tw], dtype=np.int32), (len(hs), 1))
+    r = evaluate_resize_pairs(rows[i_s], counts[i_s], rows[i_d], counts[i_d], np.stack(hs), shapes, top_k, pixel_threshold)
+    return torch.stack([r.repeatability, r.localization_err, r.common_src_num.double(), r.common_dst_num.double(),
+                        r.rep_src_num.double(), r.rep_dst_num.double()], dim=1).cpu().numpy()      # the one read of the chunk
+
+
+@torch.no_grad()
+def evaluate_resize_hsequences(dataloader, model, device, resize_shape=(240, 320), top_k_points=1000, pixel_threshold=5,
+                               nms_size=15, border_size=15, chunk_sequences=16, batch_size=64):
+    """The resize protocol of the HSequences evaluation.  The reference ships its configuration
+    (``parse_resize_eval_config``: 240 x 320, ``top_k_points`` 1000, ``pixel_threshold`` 5), its pre-processing
+    (``ratio_preserving_resize``, ``adapt_homography_to_preprocessing``), its metric (``compute_resize_repeatability``) and its
+    result record (``create_resize_metrics_results``) but no driver loop; the protocol here is:
+
+    * ``dataloader`` has ``.sequences`` and ``get_sequence_data(i)`` returning what ``Resize_HSequences.get_sequence_data``
+      returns with ``resize_image=False``: ``im_src_BGR``, ``images_dst_BGR``, ``homographies`` (H_1_k: source -> k-th
+      destination, original pixels), ``sequence_name``; images gray or 3-channel uint8 of any size;
+    * every image is brought to ``resize_shape`` (``datasets.dataset_utils.ratio_preserving_resize_batch``, one launch per
+      chunk) and every homography re-based on the host (``adapt_homography_to_preprocessing``);
+    * CHANNEL ORDER: a 3-channel image is taken as BGR (what cv2 reads) and handed to the detector as RGB, as the reference
+      converts before detection; a gray image goes as it is (the detector replicates it);
+    * each image is detected ONCE (the source is not detected again per destination), ``batch_size`` images per
+      ``pipeline.detect_batch_u8`` call -- after the resize all images have one shape --, with ``top_k_points``,
+      ``nms_size``, ``border_size``; its rows are (row, col, prob) = (y, x, score);
+    * per pair ``compute_resize_repeatability(rows_src, rows_dst, H_resized, resize_shape, resize_shape,
+      keep_k_points=top_k_points, distance_thresh=pixel_threshold)``, all pairs of ``chunk_sequences`` sequences in one
+      stream-ordered call and ONE device-to-host read per chunk.  On that read the split-f16 guard is applied as
+      ``check_val_hsequences_repeatability`` does: a chunk whose forward was flagged (or during which the checkpoint was
+      switched to the fp32 kernels) is repeated.
+
+    Returns the ``create_resize_metrics_results`` record: the six lists with one entry per pair in (sequence, destination)
+    order (float for the first two, int for the counts), ``sequences`` = the sequence names, ``top_k``, ``pixel_threshold``."""
+    from .test_utils import RESIZE_RESULT_KEYS, create_resize_metrics_results
+    device = torch.device(device)
+    guard = getattr(model, "fp16_guard_check", None)
+    chunk, batch_size = max(1, int(chunk_sequences)), max(1, int(batch_size))
+    names, out_rows = [], []
+    n_seq = len(dataloader.sequences)
+    for c0 in range(0, n_seq, chunk):
+        seqs = [dataloader.get_sequence_data(i) for i in range(c0, min(n_seq, c0 + chunk))]
+        names.extend(s['sequence_name'] for s in seqs)
+        chunk_args = (seqs, model, device, resize_shape, int(top_k_points), pixel_threshold, nms_size, border_size, batch_size)
+        on_fp32 = getattr(model, "effective_precision", None) == "fp32"
+        out = _resize_chunk(*chunk_args)
+        flagged = guard is not None and guard(synchronize=False)     # (the read above has passed every forward of the chunk)
+        if flagged or (not on_fp32 and getattr(model, "effective_precision", None) == "fp32"):
+            out = _resize_chunk(*chunk_args)
+        out_rows.append(out)
+    results = create_resize_metrics_results(names, top_k_points, pixel_threshold)
+    for r in (np.concatenate(out_rows) if out_rows else np.zeros((0, 6))):
+        for j, k in enumerate(RESIZE_RESULT_KEYS):
+            results[k].append(float(r[j]) if j < 2 else int(r[j]))
+    return results

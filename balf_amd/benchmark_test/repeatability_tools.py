@@ -144,3 +144,75 @@ def check_common_points(kpts, mask):
 def select_top_k(kpts, k=1000):
     """Indices of the ``k`` highest-scoring rows (score in column 3; repeatability_tools.py:15-17)."""
     return np.argsort(-1 * np.asarray(kpts)[:, 3])[:k]
+
+
+# ---- the resize protocol (reference repeatability_tools.py:516-614) -----------------------------------------------------------
+class ResizeRepeatabilityBatch(NamedTuple):
+    """Per-pair results of :func:`compute_resize_repeatability_batch`, device tensors ``[P]``: the fields of
+    :func:`compute_resize_repeatability`'s dict (float64 / int32)."""
+    repeatability: torch.Tensor
+    localization_err: torch.Tensor
+    common_src_num: torch.Tensor
+    common_dst_num: torch.Tensor
+    rep_src_num: torch.Tensor
+    rep_dst_num: torch.Tensor
+
+
+def _host_or_device(t, dev, dtype, shapes_ok, name):
+    if not isinstance(t, torch.Tensor):
+        t = torch.from_numpy(np.ascontiguousarray(np.asarray(t), dtype={torch.float64: np.float64, torch.int32: np.int32}[dtype]))
+    if tuple(t.shape) not in shapes_ok:
+        raise BalfHipError(f"{name} must have shape {' or '.join(map(str, shapes_ok))}, got {tuple(t.shape)}")
+    return t.to(device=dev, dtype=dtype).contiguous()
+
+
+def compute_resize_repeatability_batch(src, ns, dst, nd, h, shapes, keep_k_points=1000, distance_thresh=5, h_inv=None,
+                                       order="rcp") -> ResizeRepeatabilityBatch:
+    """:func:`compute_resize_repeatability` for P independent pairs in one stream-ordered call
+    (``balf_resize_repeatability_batch``, include/balf_hip.h), equal to it per pair bit for bit.  ``src`` [P,Ns,C] / ``dst``
+    [P,Nd,C] float64 rows on the GPU -- ``order='rcp'``: (row, col, prob), the reference's; ``order='xyrs'``: (x, y, radius,
+    score), this library's detector rows --, ``ns`` / ``nd`` [P] int32 on the GPU (rows past a count are never read), ``h``
+    [P,3,3] source -> destination in (x, y), ``shapes`` [P,4] = (h_src, w_src, h_dst, w_dst).  ``h_inv`` None: ``h`` is a host
+    array and ``np.linalg.inv`` runs on the host, as in the reference (two small uploads: not capturable); with ``h`` and
+    ``h_inv`` both device tensors nothing leaves the device and the call can be captured with ``torch.cuda.graph``.
+    Tie rule of ``select_k_best``: higher prob first, then the lower row index.  No input is written."""
+    require_gpu_tensor(src, "src")
+    dev, p = src.device, src.shape[0]
+    if h_inv is None:
+        if isinstance(h, torch.Tensor):
+            h = h.detach().cpu().numpy()
+        h = np.asarray(h).reshape(-1, 3, 3)
+        h_inv = np.linalg.inv(h)
+    h = _host_or_device(h, dev, torch.float64, ((p, 3, 3), (p, 9)), "h")
+    h_inv = _host_or_device(h_inv, dev, torch.float64, ((p, 3, 3), (p, 9)), "h_inv")
+    shapes = _host_or_device(shapes, dev, torch.int32, ((p, 4),), "shapes")
+    ns, nd = _counts(ns, p, dev, "ns").contiguous(), _counts(nd, p, dev, "nd").contiguous()
+    rep, cnt = ops.resize_repeatability_batch(src, ns, dst, nd, h, h_inv, shapes, keep_k_points, distance_thresh, order)
+    return ResizeRepeatabilityBatch(rep[:, 0], rep[:, 1], cnt[:, 0], cnt[:, 1], cnt[:, 2], cnt[:, 3])
+
+
+def compute_resize_repeatability(keypoints, warped_keypoints, h, shape_src, shape_dst, keep_k_points=1000, distance_thresh=5):
+    """The reference's resize-protocol metric (repeatability_tools.py:516-614) on the GPU: same arguments, same dict, same
+    value types.  ``keypoints`` [N,3] / ``warped_keypoints`` [M,3] rows (row, col, prob) of the source / destination image,
+    ``h`` the 3x3 homography source -> destination in (x, y) (``np.linalg.inv(h)`` is taken on the host, as there).
+
+    Two deliberate differences: among rows of EQUAL prob at the ``keep_k_points`` cut the lower row index is kept (the
+    reference's ``argsort`` is unstable there); and ``keypoints`` is NOT overwritten -- the reference writes the warped
+    coordinates into the caller's array, so that a source array used for a second destination is already warped."""
+    kp = np.asarray(keypoints, dtype=np.float64).reshape(-1, 3)
+    wkp = np.asarray(warped_keypoints, dtype=np.float64).reshape(-1, 3)
+    h = np.asarray(h).reshape(3, 3)
+    dev = _device()
+    s = torch.from_numpy(np.ascontiguousarray(kp)).to(dev)[None]
+    d = torch.from_numpy(np.ascontiguousarray(wkp)).to(dev)[None]
+    ns = torch.tensor([len(kp)], dtype=torch.int32, device=dev)
+    nd = torch.tensor([len(wkp)], dtype=torch.int32, device=dev)
+    shapes = np.asarray([[shape_src[0], shape_src[1], shape_dst[0], shape_dst[1]]], dtype=np.int32)
+    r = compute_resize_repeatability_batch(s, ns, d, nd, h[None], shapes, keep_k_points, distance_thresh)
+    rep, err = float(r.repeatability[0]), float(r.localization_err[0])
+    n1, n2, c1, c2 = (int(t[0]) for t in (r.common_src_num, r.common_dst_num, r.rep_src_num, r.rep_dst_num))
+    # the reference's value types: NumPy scalars where it computed with NumPy, Python numbers where it did not
+    found = c1 + c2 > 0
+    return {'repeatability': np.float64(rep) if found else 0., 'localization_err': np.float64(err) if found else -1,
+            'common_src_num': n1, 'common_dst_num': n2,
+            'rep_src_num': np.int64(c1) if n2 != 0 else 0, 'rep_dst_num': np.int64(c2) if n1 != 0 else 0}

@@ -392,3 +392,77 @@ def val_points(prob_src: torch.Tensor, prob_dst: torch.Tensor, h_dst_2_src: torc
                                 VAL_LEGS[leg], float(conf_thresh), int(nms_size), k, src.data_ptr(), dst.data_ptr(),
                                 count.data_ptr(), ws.data_ptr(), ws.numel(), current_stream_ptr(dev)), "balf_val_points")
     return src, dst, count
+
+
+# ---- the resize protocol of the HSequences evaluation (benchmark_test/evaluate.py, datasets/dataset_utils.py drive these) ---
+ROW_ORDERS = {"rcp": 0, "xyrs": 1}
+
+
+def resize_repeatability_batch(src: torch.Tensor, ns: torch.Tensor, dst: torch.Tensor, nd: torch.Tensor, h: torch.Tensor,
+                               h_inv: torch.Tensor, shapes: torch.Tensor, keep_k_points: int = 1000,
+                               distance_thresh: float = 5, order: str = "rcp"):
+    """``compute_resize_repeatability`` for P pairs (balf_resize_repeatability_batch in include/balf_hip.h): ``src``
+    [P,Ns,C] / ``dst`` [P,Nd,C] float64 rows, ``order='rcp'``: (row, col, prob, ...) as the reference, ``'xyrs'``:
+    (x, y, radius, score) as this library's detectors; ``ns`` / ``nd`` [P] int32; ``h`` / ``h_inv`` [P,3,3] (or [P,9])
+    float64, ``shapes`` [P,4] int32 = (h_src, w_src, h_dst, w_dst); everything on the GPU.  Returns (rep [P,2] float64 =
+    (repeatability, localization_err), counts [P,4] int32 = (N1, N2, count1, count2)); nothing is read back and no input is
+    written."""
+    if order not in ROW_ORDERS:
+        raise ValueError(f"order must be one of {sorted(ROW_ORDERS)}, got {order!r}")
+    k = int(keep_k_points)
+    if k <= 0 or k > _lib.MAX_TOPK:
+        raise ValueError(f"keep_k_points must be in 1..{_lib.MAX_TOPK}, got {keep_k_points}")
+    if not float(distance_thresh) >= 0.0:
+        raise ValueError(f"distance_thresh must be >= 0, got {distance_thresh}")
+    min_c = 4 if order == "xyrs" else 3
+    for t, name in ((src, "src"), (dst, "dst")):
+        require_gpu_tensor(t, name)
+        if t.dtype != torch.float64 or t.dim() != 3 or t.shape[2] < min_c:
+            raise BalfHipError(f"{name} must be a [P,N,C>={min_c}] float64 tensor for order {order!r}")
+    p, ns_max, nd_max = src.shape[0], src.shape[1], dst.shape[1]
+    dev = src.device
+    if dst.shape[0] != p or p == 0 or dst.device != dev:
+        raise BalfHipError(f"src and dst must hold the same number (> 0) of pairs on one device, got {p} and {dst.shape[0]}")
+    for t, name, shapes_ok, dt in ((ns, "ns", ((p,),), torch.int32), (nd, "nd", ((p,),), torch.int32),
+                                   (h, "h", ((p, 3, 3), (p, 9)), torch.float64),
+                                   (h_inv, "h_inv", ((p, 3, 3), (p, 9)), torch.float64), (shapes, "shapes", ((p, 4),), torch.int32)):
+        require_gpu_tensor(t, name)
+        if tuple(t.shape) not in shapes_ok or t.dtype != dt or t.device != dev:
+            raise BalfHipError(f"{name} must be a {' or '.join(map(str, shapes_ok))} {dt} tensor on {dev}")
+    l = lib()
+    nbytes = l.balf_resize_repeatability_batch_workspace_bytes(p, ns_max, nd_max, k)
+    if nbytes == 0:
+        raise BalfHipError(f"balf_resize_repeatability_batch: unsupported sizes P={p}, Ns={ns_max}, Nd={nd_max}, k={k}")
+    rep = torch.empty((p, 2), dtype=torch.float64, device=dev)
+    cnt = torch.empty((p, 4), dtype=torch.int32, device=dev)
+    ws = _workspace("resize_repeat", dev, nbytes)
+    with torch.cuda.device(dev):
+        check(l.balf_resize_repeatability_batch(src.data_ptr(), ns.data_ptr(), ns_max, src.shape[2], dst.data_ptr(),
+                                                nd.data_ptr(), nd_max, dst.shape[2], 1, ROW_ORDERS[order], p, h.data_ptr(),
+                                                h_inv.data_ptr(), shapes.data_ptr(), k, float(distance_thresh),
+                                                rep.data_ptr(), cnt.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                current_stream_ptr(dev)), "balf_resize_repeatability_batch")
+    return rep, cnt
+
+
+def resize_crop_u8(packed: torch.Tensor, offsets: torch.Tensor, sizes: torch.Tensor, channels: int, target_h: int,
+                   target_w: int) -> torch.Tensor:
+    """``ratio_preserving_resize`` of B uint8 images of different sizes in one launch (balf_resize_crop_u8 in
+    include/balf_hip.h): ``packed`` the images back to back (uint8, 1-D), ``offsets`` [B] int64 byte offsets, ``sizes`` [B,2]
+    int32 (h, w), all on the GPU -> [B,target_h,target_w] (``channels`` 1) or [B,target_h,target_w,3] uint8: what
+    ``pipeline.detect_batch_u8`` takes."""
+    for t, name in ((packed, "packed"), (offsets, "offsets"), (sizes, "sizes")):
+        require_gpu_tensor(t, name)
+    b = offsets.shape[0]
+    if packed.dtype != torch.uint8 or packed.dim() != 1 or offsets.dtype != torch.int64 or offsets.dim() != 1 or \
+            sizes.dtype != torch.int32 or tuple(sizes.shape) != (b, 2) or b == 0:
+        raise BalfHipError("packed must be a 1-D uint8 tensor, offsets [B] int64 and sizes [B,2] int32 with B > 0")
+    if channels not in (1, 3):
+        raise ValueError(f"channels must be 1 or 3, got {channels}")
+    dev = packed.device
+    out = torch.empty((b, int(target_h), int(target_w)) + ((3,) if channels == 3 else ()), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().balf_resize_crop_u8(packed.data_ptr(), packed.numel(), offsets.data_ptr(), sizes.data_ptr(), b,
+                                        int(channels), int(target_h), int(target_w), out.data_ptr(),
+                                        current_stream_ptr(dev)), "balf_resize_crop_u8")
+    return out

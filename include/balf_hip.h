@@ -387,6 +387,54 @@ int balf_val_points(const float *prob_src_dev, int h_src, int w_src, const float
                     const double *h_dst_2_src_dev, int leg, float conf_thresh, int nms_size, int K, double *src_pts_dev,
                     double *dst_pts_dev, int32_t *count_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
 
+/* ---- the resize protocol of the HSequences evaluation (balf/configs/config_hpatches.py: parse_resize_eval_config) -----------
+ * balf_resize_repeatability_batch: compute_resize_repeatability (balf/benchmark_test/repeatability_tools.py:516-614) for P
+ * independent pairs, stream-ordered, nothing read back.  Rows of src_dev [P,ns_max,src_stride] / dst_dev [P,nd_max,dst_stride]
+ * float64; order_xy = 0: a row starts with (row, col, prob), the reference's order (stride >= 3); order_xy = 1: a row is
+ * (x, y, radius, score) as the detectors of this library write it (stride >= 4; x = col, y = row, the radius is not read).
+ * Pair p's rows start at row p * n_max, its counts are ns_dev[p * count_stride] / nd_dev[p * count_stride] (clamped to
+ * [0, n_max]); rows past a count are never read (src_dev / dst_dev may be null when its n_max is 0).  h_dev [P,9] row-major maps source (x, y) to destination (x, y),
+ * h_inv_dev [P,9] is its inverse (computed by the caller on the host, np.linalg.inv, as the reference does; nothing is inverted
+ * here); shapes_dev [P,4] int32 = (h_src, w_src, h_dst, w_dst).  Per pair:
+ *   destination rows: warped with h_inv on (col, row); a row whose warped 0 <= row < h_src and 0 <= col < w_src is kept and
+ *                     goes on UNWARPED;
+ *   source rows:      warped with h; the WARPED (row, col, prob) goes on when inside (h_dst, w_dst);
+ *   select_k_best:    the keep_k_points rows of highest prob of each side (all when fewer).  Ties at the cut: higher prob
+ *                     first, then the lower original index (the reference cuts with NumPy's unstable argsort);
+ *   N1 x N2 Euclidean distances sqrt(dy*dy + dx*dx) (float64, no fused operation), row minima (when N2 != 0) and column minima
+ *   (when N1 != 0), count1 / count2 = minima <= distance_thresh, summed in one fixed order (a pair's result does not depend on
+ *   P or on its place in the batch).
+ * Outputs: rep_dev [P,2] float64 = (repeatability = (count1 + count2) / (N1 + N2) * 100, localization_err = sum1 / (count1 +
+ * count2) + sum2 / (count1 + count2)); count1 + count2 == 0 gives (0.0, -1.0).  counts_dev [P,4] int32 = (common_src_num N1,
+ * common_dst_num N2, rep_src_num count1, rep_dst_num count2).  The inputs are never written (the reference overwrites the
+ * caller's source array with the warped coordinates; that is not reproduced).
+ * Limits: 1 <= P <= 65535, ns_max, nd_max <= 65536, 1 <= keep_k_points <= BALF_MAX_TOPK, distance_thresh >= 0 (BALF_ERR_ARG).
+ * rr_min_kernel stages 1024 kept rows of the other side at a time in 16 KB of LDS, whatever the counts.
+ *
+ * balf_resize_crop_u8: ratio_preserving_resize (balf/datasets/dataset_utils.py:15-27) of B uint8 images of DIFFERENT sizes into
+ * out_dev [B, target_h, target_w, channels] (channels 1 or 3, interleaved), one launch.  packed_dev holds the images back to
+ * back, image b = sizes_dev[b] = (h, w) int32 starting at byte offsets_dev[b] (int64); an image that does not lie inside
+ * packed_bytes comes out all zero.  Per image scale = max(target_h / h, target_w / w), new = round_half_even((h, w) * scale)
+ * in float64; bilinear resize to `new`, then the centred crop / zero pad: the output pixel (y, x) is the resized pixel
+ * (y - top, x - left), top = floor((target_h - new_h) / 2), left = (target_w - new_w) - floor((target_w - new_w) / 2) (the
+ * reference hands its four amounts to imgaug's CropAndPad, whose order is top, right, bottom, left), zero where that falls
+ * outside the resized image.  The resize is DEFINED here as OpenCV's INTER_LINEAR for uint8 is documented to work (parity with a
+ * cv2 build is unpinned): per axis, output coordinate d samples f = float32((d + 0.5) * (n_src / n_new) - 0.5)
+ * (float64 product and difference), s = floor(f), f -= s; s < 0 -> (s, f) = (0, 0); s >= n_src - 1 -> (n_src - 1, 0); the
+ * second tap is min(s + 1, n_src - 1); weights w0 = rint((1 - f) * 2048), w1 = rint(f * 2048) in float32 (half to even).
+ * Horizontal pass S = p[s] * w0 + p[s + 1] * w1 (int32) on the two rows, vertical pass
+ * out = (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2.
+ * 1 <= B <= 65535 (BALF_ERR_ARG), target_h, target_w <= 16384 (BALF_ERR_SHAPE).  No workspace. */
+size_t balf_resize_repeatability_batch_workspace_bytes(int P, int ns_max, int nd_max, int keep_k_points);
+int balf_resize_repeatability_batch(const double *src_dev, const int32_t *ns_dev, int ns_max, int src_stride,
+                                    const double *dst_dev, const int32_t *nd_dev, int nd_max, int dst_stride, int count_stride,
+                                    int order_xy, int P, const double *h_dev, const double *h_inv_dev,
+                                    const int32_t *shapes_dev, int keep_k_points, double distance_thresh, double *rep_dev,
+                                    int32_t *counts_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+int balf_resize_crop_u8(const unsigned char *packed_dev, size_t packed_bytes, const long long *offsets_dev,
+                        const int32_t *sizes_dev, int B, int channels, int target_h, int target_w, unsigned char *out_dev,
+                        void *stream);
+
 /* ---- measurement aid (not part of the data path) ---------------------------------------------
  * Between balf_profile_begin() and balf_profile_end() every kernel launch of the library is bracketed
  * by a hipEvent pair on its launch stream.  balf_profile_end() waits for those events and returns,
