@@ -15,6 +15,8 @@
 namespace balf {
 namespace {
 
+constexpr int kCommonBorder = 15;           // create_common_region_masks' fixed frame (geometry_tools.py:16,22)
+
 __host__ __device__ __forceinline__ double ones_inner(int y, int x, int h, int w, int b) {
     return (y >= b && y < h - b && x >= b && x < w - b) ? 1.0 : 0.0;      // zero outside the image too
 }

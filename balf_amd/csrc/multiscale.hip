@@ -10,11 +10,12 @@
 //                         batch balf_forward takes (padding included: every padded pixel is written, 0 outside the image)
 //   (budgeted top-K)      balf_nms_topk_budget: the kernels of balf_nms_topk (nms_topk.hip) with K decided per image
 //   merge_kernel          one workgroup per image: the L level lists -> LDS keys (score desc, level asc, index asc),
-//                         bitonic sort, each row mapped to the original image with the homography arithmetic of
-//                         balf_apply_homography (homography.h), [N,4] float64 rows + count
+//                         bitonic sort (block_ops.h), each row mapped to the original image with the homography arithmetic
+//                         of balf_apply_homography (homography.h), [N,4] float64 rows + count
 #include <cmath>
 #include <cstdint>
 
+#include "block_ops.h"
 #include "common.h"
 #include "homography.h"
 #include "prof.h"
@@ -186,9 +187,7 @@ __global__ __launch_bounds__(MERGE_THREADS) void merge_kernel(MergeArgs a) {
         int o = 0;
         for (int l = 0; l < a.L; ++l) {
             s_off[l] = o;
-            int c = a.cnt[(long)l * a.B + b];
-            c = c < 0 ? 0 : (c > a.K_max ? a.K_max : c);
-            o += c;
+            o += balf::clamp_count(a.cnt, (long)l * a.B + b, a.K_max);
         }
         s_off[a.L] = o;
     }
@@ -200,8 +199,7 @@ __global__ __launch_bounds__(MERGE_THREADS) void merge_kernel(MergeArgs a) {
         if (tid == 0) a.count_out[b] = -1;
         return;
     }
-    int npow2 = 1;
-    while (npow2 < total) npow2 <<= 1;
+    const int npow2 = balf::next_pow2(total);
     for (int p = tid; p < npow2; p += MERGE_THREADS) {
         unsigned long long k = ~0ull;
         if (p < total) {
@@ -215,19 +213,7 @@ __global__ __launch_bounds__(MERGE_THREADS) void merge_kernel(MergeArgs a) {
         keys[p] = k;                           // ascending = score desc, level asc, index asc
     }
     __syncthreads();
-    for (int k = 2; k <= npow2; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < npow2; i += MERGE_THREADS) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const unsigned long long x = keys[i], y = keys[l];
-                    const bool up = ((i & k) == 0);
-                    if ((x > y) == up) { keys[i] = y; keys[l] = x; }
-                }
-            }
-            __syncthreads();
-        }
-    }
+    balf::bitonic_sort<MERGE_THREADS>(keys, npow2);
     const int n = total < a.N ? total : a.N;
     for (int r = tid; r < a.N; r += MERGE_THREADS) {
         double *row = out + (long)r * 4;
@@ -248,12 +234,6 @@ __global__ __launch_bounds__(MERGE_THREADS) void merge_kernel(MergeArgs a) {
         row[3] = (double)score;
     }
     if (tid == 0) a.count_out[b] = n;
-}
-
-int next_pow2(int v) {
-    int p = 1;
-    while (p < v) p <<= 1;
-    return p;
 }
 
 }  // namespace
@@ -335,7 +315,7 @@ extern "C" int balf_multiscale_merge(const int32_t *idx_dev, const float *score_
     }
     const long all = (long)L * K_max;
     a.cap = (int)(all < BALF_MAX_TOPK ? all : BALF_MAX_TOPK);
-    a.npow2_cap = next_pow2(a.cap);
+    a.npow2_cap = balf::next_pow2(a.cap);
     const size_t smem = (size_t)a.npow2_cap * 8;
     if (smem > 48 * 1024 &&
         hipFuncSetAttribute(reinterpret_cast<const void *>(merge_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,

@@ -37,6 +37,7 @@
 
 #include <atomic>
 
+#include "block_ops.h"
 #include "common.h"
 #include "prof.h"
 
@@ -325,21 +326,8 @@ __device__ void keep_tile(const GreedyArgs &a, KeepLds &s, int b, int tile, int 
     }
 }
 
-// wave-wide helpers (64 lanes, all active)
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ int wave_incl_scan(int v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(v, o);
-        if (lane >= o) v += t;
-    }
-    return v;
-}
+using balf::wave_incl_scan;                           // wave-wide helpers (64 lanes, all active): block_ops.h
+using balf::wave_sum;
 
 // Kill pass of one tile.  Wave 0 of the workgroup does the work; every thread must call it (two barriers).
 __device__ void kill_tile(const GreedyArgs &a, KillLds &s, int b, int tile, int round, bool check_activity) {

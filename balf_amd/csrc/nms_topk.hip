@@ -18,8 +18,10 @@
 //                          survivors reach it, a second radix select on the flat index keeps the
 //                          raster-first K of them (as the reference does); LDS bitonic sort of the
 //                          <= K selected (score desc, index asc) and the padded output rows.
+// The select, the sort and the wave scan are the shared ones of block_ops.h.
 #include <cstdint>
 #include <cstdlib>
+#include "block_ops.h"
 #include "common.h"
 #include "prof.h"
 
@@ -78,12 +80,7 @@ __device__ __forceinline__ float load_score(const NmsArgs &a, const float *img, 
 // prefix and leaves the block total in *total.
 __device__ __forceinline__ int block_exclusive_scan(int v, int *s_wave /*[4]*/, int *total) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        int t = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += t;
-    }
+    const int inc = balf::wave_incl_scan(v);
     if (lane == 63) s_wave[wave] = inc;
     __syncthreads();
     int base = 0;
@@ -406,73 +403,6 @@ __global__ __launch_bounds__(NTHREADS) void nms_tile_kernel_generic(NmsArgs a) {
 // ---------------------------------------------------------------------------------------------
 constexpr int SEL_THREADS = 1024;
 
-// Radix select over 32-bit keys of the elements that pass `pred`.  Finds the key of rank `rank`
-// (1-based) counting from the top (FROM_TOP) or from the bottom; *n_same = how many elements carry
-// exactly that key and *rank_in_same = how many of them are needed to reach `rank`.
-template <bool FROM_TOP, typename KeyFn>
-__device__ unsigned radix_select(int n, int rank, bool cached, const int2 (&ent)[16], const int2 *surv, KeyFn key_of,
-                                 unsigned *s_hist /*[256]*/, int *s_tmp /*[4]*/, int *n_same, int *rank_in_same) {
-    unsigned prefix = 0, mask = 0;
-    for (int shift = 24; shift >= 0; shift -= 8) {
-        for (int i = threadIdx.x; i < 256; i += SEL_THREADS) s_hist[i] = 0;
-        __syncthreads();
-        if (cached) {
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                unsigned k;
-                if (threadIdx.x + j * SEL_THREADS < n && key_of(ent[j], &k) && (k & mask) == prefix)
-                    atomicAdd(&s_hist[(k >> shift) & 255u], 1u);
-            }
-        } else {
-            for (int i = threadIdx.x; i < n; i += SEL_THREADS) {
-                unsigned k;
-                if (key_of(surv[i], &k) && (k & mask) == prefix) atomicAdd(&s_hist[(k >> shift) & 255u], 1u);
-            }
-        }
-        __syncthreads();
-        if (threadIdx.x < 64) {
-            // first bin (in scan order) at which the running count reaches `rank`: wave 0, four bins per lane, a
-            // shuffle prefix over the lanes (the scan used to be 256 serial LDS reads on thread 0, four times per select)
-            const int l = threadIdx.x;
-            int h[4], sum = 0;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int t = 4 * l + i;
-                h[i] = (int)s_hist[FROM_TOP ? 255 - t : t];
-                sum += h[i];
-            }
-            int inc = sum;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const int v = __shfl_up(inc, d, 64);
-                if (l >= d) inc += v;
-            }
-            int cum = inc - sum;
-            if (cum < rank && rank <= inc) {                 // exactly one lane
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    if (cum + h[i] >= rank) {
-                        const int t = 4 * l + i;
-                        s_tmp[0] = FROM_TOP ? 255 - t : t;
-                        s_tmp[1] = rank - cum;
-                        s_tmp[2] = h[i];
-                        break;
-                    }
-                    cum += h[i];
-                }
-            }
-        }
-        __syncthreads();
-        prefix |= (unsigned)s_tmp[0] << shift;
-        mask |= 255u << shift;
-        rank = s_tmp[1];
-        __syncthreads();
-    }
-    *n_same = s_tmp[2];
-    *rank_in_same = rank;
-    return prefix;
-}
-
 // thr_explicit = 0: the threshold is the K-th largest survivor score (find_index_higher_scores with threshold = -1,
 // test_utils.py:76-89).  thr_explicit != 0: the bits of a caller-given positive threshold (`threshold != -1`,
 // test_utils.py:91-95): every survivor with score >= it, the raster-first K of them if there are more.
@@ -505,9 +435,7 @@ __global__ __launch_bounds__(SEL_THREADS) void topk_select_kernel(const int2 *su
         __syncthreads();
         K = *s_cnt;
         __syncthreads();
-        int p = 1;
-        while (p < K) p <<= 1;
-        npow2 = p;                 // <= the host's next_pow2(K_row): the LDS holds it
+        npow2 = balf::next_pow2(K); // <= the host's next_pow2(K_row): the LDS holds it
     }
 
     if (K == 0 || (n == 0 && (!zero_fallback || thr_explicit))) {   // greedy-NMS caller / explicit threshold / no budget left
@@ -541,79 +469,60 @@ __global__ __launch_bounds__(SEL_THREADS) void topk_select_kernel(const int2 *su
             ent[j] = (i < n) ? surv[i] : make_int2(0x7fffffff, 0);      // score bits 0 never reach a threshold > 0
         }
     }
+    // f(entry) for every survivor of this thread; all of it inlines (ent[] must stay in registers).  ent[j] is a survivor for
+    // j < n_mine, i.e. threadIdx.x + j * SEL_THREADS < n (in that form 16 more registers stay alive through the select).
+    const int n_mine = (n - (int)threadIdx.x + SEL_THREADS - 1) / SEL_THREADS;
+    auto each = [&](auto f) {
+        if (cached) {
+#pragma unroll
+            for (int j = 0; j < CACHE; ++j)
+                if (j < n_mine) f(ent[j]);
+        } else {
+            for (int i = threadIdx.x; i < n; i += SEL_THREADS) f(surv[i]);
+        }
+    };
 
     unsigned thr = 0;            // score bits; select score >= thr with idx <= idx_cut
     int idx_cut = 0x7fffffff;
+    // the K-th smallest flat index among the survivors that reach thr: `argwhere(...)[:K]` keeps the raster-first K
+    auto raster_cut = [&]() {
+        int d0, d1;
+        const unsigned t = thr;
+        return (int)balf::radix_select<32, false, SEL_THREADS>(
+            K, [&](auto count) { each([&](int2 e) { if ((unsigned)e.y >= t) count((unsigned)e.x); }); }, s_hist, s_tmp, &d0, &d1);
+    };
     if (thr_explicit) {
         thr = thr_explicit;
         if (threadIdx.x == 0) *s_cnt = 0;
         __syncthreads();
         int mine = 0;
-        if (cached) {
-#pragma unroll
-            for (int j = 0; j < CACHE; ++j)
-                if (threadIdx.x + j * SEL_THREADS < n && (unsigned)ent[j].y >= thr) ++mine;
-        } else {
-            for (int i = threadIdx.x; i < n; i += SEL_THREADS)
-                if ((unsigned)surv[i].y >= thr) ++mine;
-        }
+        each([&](int2 e) { if ((unsigned)e.y >= thr) ++mine; });
         if (mine) atomicAdd(s_cnt, mine);
         __syncthreads();
         const int reach = *s_cnt;
         __syncthreads();
-        if (reach > K) {         // more than K pixels reach the threshold: `argwhere(...)[:K]` keeps the raster-first K
-            int d0, d1;
-            const unsigned t = thr;
-            idx_cut = (int)radix_select<false>(
-                n, K, cached, ent, surv, [t](int2 e, unsigned *k) { *k = (unsigned)e.x; return (unsigned)e.y >= t; },
-                s_hist, s_tmp, &d0, &d1);
-        }
+        if (reach > K) idx_cut = raster_cut();                     // more than K pixels reach the threshold
     } else if (n > K) {
         int n_eq, need_eq;
-        thr = radix_select<true>(n, K, cached, ent, surv, [](int2 e, unsigned *k) { *k = (unsigned)e.y; return true; },
-                                 s_hist, s_tmp, &n_eq, &need_eq);
-        if (n_eq > need_eq) {    // more than K candidates reach the threshold: keep the raster-first K
-            int d0, d1;
-            const unsigned t = thr;
-            idx_cut = (int)radix_select<false>(
-                n, K, cached, ent, surv, [t](int2 e, unsigned *k) { *k = (unsigned)e.x; return (unsigned)e.y >= t; },
-                s_hist, s_tmp, &d0, &d1);
-        }
+        thr = (unsigned)balf::radix_select<32, true, SEL_THREADS>(
+            K, [&](auto count) { each([&](int2 e) { count((unsigned)e.y); }); }, s_hist, s_tmp, &n_eq, &need_eq);
+        if (n_eq > need_eq) idx_cut = raster_cut();                // more than K candidates reach the threshold
     }
 
     if (threadIdx.x == 0) *s_cnt = 0;
     for (int i = threadIdx.x; i < npow2; i += SEL_THREADS) keys[i] = ~0ull;
     __syncthreads();
-    auto take = [&](int2 e) {
+    each([&](int2 e) {
         const unsigned sb = (unsigned)e.y;
         if (sb >= thr && e.x <= idx_cut) {
             const int p = atomicAdd(s_cnt, 1);
             keys[p] = ((unsigned long long)(~sb) << 32) | (unsigned)e.x;   // ascending = score desc, idx asc
         }
-    };
-    if (cached) {
-#pragma unroll
-        for (int j = 0; j < CACHE; ++j)
-            if (threadIdx.x + j * SEL_THREADS < n) take(ent[j]);
-    } else {
-        for (int i = threadIdx.x; i < n; i += SEL_THREADS) take(surv[i]);
-    }
+    });
     __syncthreads();
     const int cnt = *s_cnt;
 
-    for (int k = 2; k <= npow2; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = threadIdx.x; i < npow2; i += SEL_THREADS) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const unsigned long long x = keys[i], y = keys[l];
-                    const bool up = ((i & k) == 0);
-                    if ((x > y) == up) { keys[i] = y; keys[l] = x; }
-                }
-            }
-            __syncthreads();
-        }
-    }
+    balf::bitonic_sort<SEL_THREADS>(keys, npow2);
     for (int i = threadIdx.x; i < K_row; i += SEL_THREADS) {
         if (i < cnt) {
             const unsigned long long kv = keys[i];
@@ -653,12 +562,6 @@ int launch_nms_tiles(const NmsArgs &a, int B, hipStream_t stream) {
     return BALF_OK;
 }
 
-int next_pow2(int v) {
-    int p = 1;
-    while (p < v) p <<= 1;
-    return p;
-}
-
 }  // namespace
 
 namespace {
@@ -681,7 +584,7 @@ int balf_fill_u32(void *dst_dev, unsigned value, size_t n_words, hipStream_t str
 int balf_topk_select_launch(const int2 *surv, const int *counts, long cap, int B, int K, int zero_fallback,
                             int32_t *idx_dev, float *score_dev, int32_t *count_dev, hipStream_t st,
                             unsigned thr_explicit, int32_t *taken_dev, int cum_budget) {
-    const int npow2 = next_pow2(K);
+    const int npow2 = balf::next_pow2(K);
     const size_t smem = (size_t)npow2 * 8 + 256 * 4 + 8 * 4;
     if (smem > 48 * 1024 &&
         hipFuncSetAttribute(reinterpret_cast<const void *>(topk_select_kernel),

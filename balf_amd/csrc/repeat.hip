@@ -16,7 +16,8 @@
 //   rep_greedy_kernel  one wave walks the sorted candidates 64 at a time; visited bitmaps in LDS; the error sum is
 //                      accumulated in the reference's order
 // The candidate count is data dependent and stays on the device.  The overlaps, the sort and the greedy walk are in
-// repeat_core.h, shared with the batched entry of repeat_batch.hip.
+// repeat_core.h, shared with the batched entry of repeat_batch.hip; the scan is block_scan_chunk of block_ops.h.
+#include "block_ops.h"
 #include "common.h"
 #include "common_mask.h"
 #include "homography.h"
@@ -50,35 +51,15 @@ __global__ __launch_bounds__(1024) void rep_scan_kernel(const int *cnt_s, const 
                                                         int *off_s, int *off_m, int *totals, int *poss_out) {
     __shared__ int wsum[3][16];
     __shared__ int base[3];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     if (tid < 3) base[tid] = 0;
     __syncthreads();
     for (int i0 = 0; i0 < ns; i0 += 1024) {
         const int i = i0 + tid;
-        int v[3] = {i < ns ? cnt_s[i] : 0, i < ns ? cnt_m[i] : 0, i < ns ? poss[i] : 0};
-        int incl[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            int x = v[c];
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const int y = __shfl_up(x, o);
-                if (lane >= o) x += y;
-            }
-            incl[c] = x;
-            if (lane == 63) wsum[c][wave] = x;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            int before = base[c];
-            for (int w = 0; w < wave; ++w) before += wsum[c][w];
-            incl[c] += before;
-        }
-        if (i < ns) { off_s[i] = incl[0] - v[0]; off_m[i] = incl[1] - v[1]; }
-        __syncthreads();
-        if (tid == 1023) { base[0] = incl[0]; base[1] = incl[1]; base[2] = incl[2]; }
-        __syncthreads();
+        const int v[3] = {i < ns ? cnt_s[i] : 0, i < ns ? cnt_m[i] : 0, i < ns ? poss[i] : 0};
+        int excl[3];
+        block_scan_chunk<int, 3, 1024>(v, excl, wsum, base);
+        if (i < ns) { off_s[i] = excl[0]; off_m[i] = excl[1]; }
     }
     if (tid == 0) { totals[0] = base[0]; totals[1] = base[1]; totals[2] = base[2]; *poss_out = base[2]; }
 }
@@ -152,15 +133,15 @@ struct RepWs {
 
 RepWs rep_layout(char *base, int ns, int max_edges) {
     RepWs w{};
-    size_t o = 0;
-    auto take = [&](size_t bytes) { char *p = base ? base + o : nullptr; o += balf_align_up(bytes, 256); return p; };
-    w.cnt_s = (int *)take((size_t)ns * 4); w.cnt_m = (int *)take((size_t)ns * 4); w.poss = (int *)take((size_t)ns * 4);
-    w.off_s = (int *)take((size_t)ns * 4); w.off_m = (int *)take((size_t)ns * 4); w.totals = (int *)take(16);
-    w.key_s = (unsigned long long *)take((size_t)max_edges * 8); w.key_m = (unsigned long long *)take((size_t)max_edges * 8);
-    w.key_out = (unsigned long long *)take((size_t)max_edges * 8);
-    w.val_s = (unsigned *)take((size_t)max_edges * 4); w.val_m = (unsigned *)take((size_t)max_edges * 4);
-    w.val_out = (unsigned *)take((size_t)max_edges * 4);
-    w.total = o;
+    WorkspaceCursor c{base, 0};
+    const size_t rows = (size_t)ns * 4, e = (size_t)max_edges;
+    w.cnt_s = c.take<int>(rows); w.cnt_m = c.take<int>(rows); w.poss = c.take<int>(rows);
+    w.off_s = c.take<int>(rows); w.off_m = c.take<int>(rows); w.totals = c.take<int>(16);
+    w.key_s = c.take<unsigned long long>(e * 8); w.key_m = c.take<unsigned long long>(e * 8);
+    w.key_out = c.take<unsigned long long>(e * 8);
+    w.val_s = c.take<unsigned>(e * 4); w.val_m = c.take<unsigned>(e * 4);
+    w.val_out = c.take<unsigned>(e * 4);
+    w.total = c.used;
     return w;
 }
 

@@ -13,6 +13,8 @@
 //     rpb_sort_kernel          one workgroup per (pair, scale): the stable radix sort of the slice
 //     rpb_greedy_kernel        one wave per (pair, scale): the greedy assignment walk
 //     rpb_finalize_kernel      one thread per pair: the result fields with the reference's formulas
+// The ordered compaction, the scans and the count clamp are the shared ones of block_ops.h.
+#include "block_ops.h"
 #include "common.h"
 #include "common_mask.h"
 #include "homography.h"
@@ -21,13 +23,7 @@
 namespace balf {
 namespace {
 
-constexpr int kCommonBorder = 15;           // create_common_region_masks' fixed frame (geometry_tools.py:16,22)
 constexpr int kRowsPerBlock = 4;            // count / fill: one wave per source row
-
-__device__ __forceinline__ int pair_count(const int *c, int p, int stride, int n_max) {
-    const int v = c[(long)p * stride];
-    return v < 0 ? 0 : (v > n_max ? n_max : v);
-}
 
 // check_common_points (repeatability_tools.py:8-13) of one point against the mask of h_out x w_out: mask[round(y) - 1,
 // round(x) - 1] with NumPy's indexing (round half to even; -k wraps to row h_out - k).  An index NumPy would reject is
@@ -47,8 +43,7 @@ __global__ __launch_bounds__(256) void common_points_kernel(const double *src, c
                                                             const int *nd, int nd_max, const double *h_all, const int *shapes,
                                                             double *src_out, double *dst_out, int *kept, int *valid) {
     __shared__ int wcnt[4];
-    const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const unsigned long long below = (1ull << lane) - 1ull;
+    const int p = blockIdx.x, tid = threadIdx.x;
     const double *h = h_all + 9 * (long)p;
     double m_src[9], m_dst[9];
     const bool inv_ok = common_mask_maps(h, m_src, m_dst);       // (every thread: two closed-form inverses)
@@ -57,7 +52,7 @@ __global__ __launch_bounds__(256) void common_points_kernel(const double *src, c
     int kept_side[2];
     for (int side = 0; side < 2; ++side) {
         const int n_max = side ? nd_max : ns_max;
-        const int n = inv_ok && shape_ok ? pair_count(side ? nd : ns, p, 1, n_max) : 0;
+        const int n = inv_ok && shape_ok ? clamp_count(side ? nd : ns, p, n_max) : 0;
         const double *in = (side ? dst : src) + (long)p * n_max * 4;
         double *out = (side ? dst_out : src_out) + (long)p * n_max * 4;
         const double *m = side ? m_dst : m_src;
@@ -71,20 +66,13 @@ __global__ __launch_bounds__(256) void common_points_kernel(const double *src, c
                 x = in[4 * r]; y = in[4 * r + 1]; rad = in[4 * r + 2]; sc = in[4 * r + 3];
                 keep = point_in_mask(m, x, y, h_out, w_out, h_in, w_in);
             }
-            const unsigned long long b = __ballot(keep);
-            if (lane == 0) wcnt[wave] = __popcll(b);
-            __syncthreads();
-            int before = base, chunk = 0;
-#pragma unroll
-            for (int w = 0; w < 4; ++w) { before += w < wave ? wcnt[w] : 0; chunk += wcnt[w]; }
+            const int q = compact_slot<256>(keep, wcnt, base);
             if (keep) {
-                double *o = out + 4 * (long)(before + __popcll(b & below));
+                double *o = out + 4 * (long)q;
                 if (side) homography_point(h, x, y, rad, &o[0], &o[1], &o[2]);
                 else { o[0] = x; o[1] = y; o[2] = rad; }
                 o[3] = sc;
             }
-            base += chunk;
-            __syncthreads();                                     // wcnt is free again
         }
         for (long k = 4 * (long)base + tid; k < 4 * (long)n_max; k += 256) out[k] = 0.0;
         kept_side[side] = base;
@@ -100,18 +88,14 @@ struct BatchIn {
     const double *src, *dst;
     const int *ns, *nd;
     int ns_max, nd_max, src_stride, dst_stride, count_stride;
+    __device__ int n_src(int p) const { return clamp_count(ns, (long)p * count_stride, ns_max); }
+    __device__ int n_dst(int p) const { return clamp_count(nd, (long)p * count_stride, nd_max); }
 };
-
-__device__ __forceinline__ int wave_sum(int x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-    return x;
-}
 
 __global__ __launch_bounds__(64 * kRowsPerBlock) void rpb_count_kernel(BatchIn in, RepParams rp, int *cnt_s, int *cnt_m, int *poss) {
     const int p = blockIdx.y, lane = threadIdx.x & 63;
     const int i = blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
-    const int ns = pair_count(in.ns, p, in.count_stride, in.ns_max), nd = pair_count(in.nd, p, in.count_stride, in.nd_max);
+    const int ns = in.n_src(p), nd = in.n_dst(p);
     if (i >= ns) return;                                          // (a whole wave)
     const double *s = in.src + ((long)p * in.ns_max + i) * in.src_stride;
     const double *d = in.dst + (long)p * in.nd_max * in.dst_stride;
@@ -135,39 +119,19 @@ __global__ __launch_bounds__(1024) void rpb_row_scan_kernel(BatchIn in, const in
                                                             int *off_s, int *off_m, int *tot) {
     __shared__ int wsum[3][16];
     __shared__ int base[3];
-    const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int ns = pair_count(in.ns, p, in.count_stride, in.ns_max);
-    const int nd = pair_count(in.nd, p, in.count_stride, in.nd_max);
+    const int p = blockIdx.x, tid = threadIdx.x;
+    const int ns = in.n_src(p);
+    const int nd = in.n_dst(p);
     const int n = nd > 0 ? ns : 0;                                // no destination rows: every count is 0 (not computed)
     const long row0 = (long)p * in.ns_max;
     if (tid < 3) base[tid] = 0;
     __syncthreads();
     for (int i0 = 0; i0 < n; i0 += 1024) {
         const int i = i0 + tid;
-        int v[3] = {i < n ? cnt_s[row0 + i] : 0, i < n ? cnt_m[row0 + i] : 0, i < n ? poss[row0 + i] : 0};
-        int incl[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            int x = v[c];
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const int y = __shfl_up(x, o);
-                if (lane >= o) x += y;
-            }
-            incl[c] = x;
-            if (lane == 63) wsum[c][wave] = x;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            int before = base[c];
-            for (int w = 0; w < wave; ++w) before += wsum[c][w];
-            incl[c] += before;
-        }
-        if (i < n) { off_s[row0 + i] = incl[0] - v[0]; off_m[row0 + i] = incl[1] - v[1]; }
-        __syncthreads();
-        if (tid == 1023) { base[0] = incl[0]; base[1] = incl[1]; base[2] = incl[2]; }
-        __syncthreads();
+        const int v[3] = {i < n ? cnt_s[row0 + i] : 0, i < n ? cnt_m[row0 + i] : 0, i < n ? poss[row0 + i] : 0};
+        int excl[3];
+        block_scan_chunk<int, 3, 1024>(v, excl, wsum, base);
+        if (i < n) { off_s[row0 + i] = excl[0]; off_m[row0 + i] = excl[1]; }
     }
     if (tid == 0) { tot[3 * p] = base[0]; tot[3 * p + 1] = base[1]; tot[3 * p + 2] = base[2]; }
 }
@@ -176,35 +140,15 @@ __global__ __launch_bounds__(1024) void rpb_row_scan_kernel(BatchIn in, const in
 __global__ __launch_bounds__(1024) void rpb_pair_scan_kernel(const int *tot, int P, long long *slice) {
     __shared__ long long wsum[2][16];
     __shared__ long long base[2];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     if (tid < 2) base[tid] = 0;
     __syncthreads();
     for (int p0 = 0; p0 < P; p0 += 1024) {
         const int p = p0 + tid;
-        long long v[2] = {p < P ? (long long)tot[3 * p] : 0, p < P ? (long long)tot[3 * p + 1] : 0};
-        long long incl[2];
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            long long x = v[c];
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const long long y = __shfl_up(x, o);
-                if (lane >= o) x += y;
-            }
-            incl[c] = x;
-            if (lane == 63) wsum[c][wave] = x;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            long long before = base[c];
-            for (int w = 0; w < wave; ++w) before += wsum[c][w];
-            incl[c] += before;
-        }
-        if (p < P) { slice[2 * p] = incl[0] - v[0]; slice[2 * p + 1] = incl[1] - v[1]; }
-        __syncthreads();
-        if (tid == 1023) { base[0] = incl[0]; base[1] = incl[1]; }
-        __syncthreads();
+        const long long v[2] = {p < P ? (long long)tot[3 * p] : 0, p < P ? (long long)tot[3 * p + 1] : 0};
+        long long excl[2];
+        block_scan_chunk<long long, 2, 1024>(v, excl, wsum, base);
+        if (p < P) { slice[2 * p] = excl[0]; slice[2 * p + 1] = excl[1]; }
     }
 }
 
@@ -214,7 +158,7 @@ __global__ __launch_bounds__(64 * kRowsPerBlock) void rpb_fill_kernel(BatchIn in
                                                                       unsigned long long *key_m, unsigned *val_m) {
     const int p = blockIdx.y, lane = threadIdx.x & 63;
     const int i = blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
-    const int ns = pair_count(in.ns, p, in.count_stride, in.ns_max), nd = pair_count(in.nd, p, in.count_stride, in.nd_max);
+    const int ns = in.n_src(p), nd = in.n_dst(p);
     if (i >= ns) return;                                          // (a whole wave)
     const double *s = in.src + ((long)p * in.ns_max + i) * in.src_stride;
     const double *d = in.dst + (long)p * in.nd_max * in.dst_stride;
@@ -265,7 +209,7 @@ __global__ __launch_bounds__(64) void rpb_greedy_kernel(BatchIn in, const unsign
         if (lane == 0) { found_out[2 * p + which] = -1; err_out[2 * p + which] = 0.0; }
         return;
     }
-    const int ns = pair_count(in.ns, p, in.count_stride, in.ns_max), nd = pair_count(in.nd, p, in.count_stride, in.nd_max);
+    const int ns = in.n_src(p), nd = in.n_dst(p);
     const long long o = slice[2 * p + which];
     int found = 0;
     double err = 0.0;
@@ -282,7 +226,7 @@ __global__ __launch_bounds__(256) void rpb_finalize_kernel(BatchIn in, int P, co
 #pragma clang fp contract(off)
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= P) return;
-    const int ns = pair_count(in.ns, p, in.count_stride, in.ns_max), nd = pair_count(in.nd, p, in.count_stride, in.nd_max);
+    const int ns = in.n_src(p), nd = in.n_dst(p);
     const int total = ns < nd ? ns : nd;
     const double nan = __longlong_as_double(0x7ff8000000000000LL);
     for (int which = 0; which < 2; ++which) {
@@ -308,22 +252,19 @@ struct RpbWs {
 
 RpbWs rpb_layout(char *base, int P, int ns_max, int max_edges) {
     RpbWs w{};
-    size_t o = 0;
-    auto take = [&](size_t bytes) { char *p = base ? base + o : nullptr; o += balf_align_up(bytes, 256); return p; };
+    WorkspaceCursor c{base, 0};
     const size_t rows = (size_t)P * ns_max, e = (size_t)max_edges;
-    w.cnt_s = (int *)take(rows * 4); w.cnt_m = (int *)take(rows * 4); w.poss = (int *)take(rows * 4);
-    w.off_s = (int *)take(rows * 4); w.off_m = (int *)take(rows * 4);
-    w.tot = (int *)take((size_t)P * 12); w.found = (int *)take((size_t)P * 8);
-    w.slice = (long long *)take((size_t)P * 16); w.err = (double *)take((size_t)P * 16);
-    w.key_s = (unsigned long long *)take(e * 8); w.key_m = (unsigned long long *)take(e * 8);
-    w.out_key_s = (unsigned long long *)take(e * 8); w.out_key_m = (unsigned long long *)take(e * 8);
-    w.val_s = (unsigned *)take(e * 4); w.val_m = (unsigned *)take(e * 4);
-    w.out_val_s = (unsigned *)take(e * 4); w.out_val_m = (unsigned *)take(e * 4);
-    w.total = o;
+    w.cnt_s = c.take<int>(rows * 4); w.cnt_m = c.take<int>(rows * 4); w.poss = c.take<int>(rows * 4);
+    w.off_s = c.take<int>(rows * 4); w.off_m = c.take<int>(rows * 4);
+    w.tot = c.take<int>((size_t)P * 12); w.found = c.take<int>((size_t)P * 8);
+    w.slice = c.take<long long>((size_t)P * 16); w.err = c.take<double>((size_t)P * 16);
+    w.key_s = c.take<unsigned long long>(e * 8); w.key_m = c.take<unsigned long long>(e * 8);
+    w.out_key_s = c.take<unsigned long long>(e * 8); w.out_key_m = c.take<unsigned long long>(e * 8);
+    w.val_s = c.take<unsigned>(e * 4); w.val_m = c.take<unsigned>(e * 4);
+    w.out_val_s = c.take<unsigned>(e * 4); w.out_val_m = c.take<unsigned>(e * 4);
+    w.total = c.used;
     return w;
 }
-
-constexpr int kMaxPairs = 65535;            // grid y of the count / fill launches
 
 int check_sizes(int P, int ns_max, int nd_max) {
     if (P <= 0 || P > kMaxPairs || ns_max < 0 || nd_max < 0 || ns_max > kMaxPoints || nd_max > kMaxPoints) return BALF_ERR_ARG;

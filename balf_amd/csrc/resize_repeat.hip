@@ -7,6 +7,7 @@
 //                         expressions) and tested against the other image's shape; the keep_k_points rows of highest prob by an
 //                         MSB-first radix select on the monotone 64-bit key of the float64 prob (ties at the cut: the lower
 //                         original index, a second select); ordered compaction of the kept (row, col) into the workspace
+//                         (block_sum, radix_select and compact_slot of block_ops.h)
 //     rr_min_kernel       grid (64-row tiles, 2 directions, P), 4 waves per workgroup: every wave takes the same 64 kept rows
 //                         of one side (one per lane) against a quarter of the other side's kept rows, staged in LDS in tiles
 //                         (every lane reads the same address: a broadcast); min of dx*dx + dy*dy, one sqrt per row.  Run with
@@ -15,6 +16,7 @@
 //                         t sums rows t, t + 256, ...; then a fixed tree), so a pair's result does not depend on P or on its
 //                         place in the batch; the result fields with the reference's formulas
 // fp contraction is OFF wherever a float64 expression is compared against the reference (warps, distances, results).
+#include "block_ops.h"
 #include "common.h"
 #include "homography.h"
 
@@ -23,7 +25,6 @@ namespace {
 
 constexpr int kSelThreads = 1024;
 constexpr int kMaxRows = 65536;             // rows per side and pair
-constexpr int kMaxPairs = 65535;            // grid z of rr_min_kernel
 constexpr int kMinRows = 64;                // rows per workgroup of rr_min_kernel (one per lane)
 constexpr int kMinWaves = 4;                // ... each wave a quarter of the columns
 constexpr int kMinTile = 1024;              // columns staged in LDS at a time (16 KB)
@@ -44,11 +45,6 @@ struct RrArgs {
     double *kept;                           // [P, 2, kcap, 2] (row, col)
     int *kept_n;                            // [P, 2]
 };
-
-__device__ __forceinline__ int clamp_count(const int *c, long at, int n_max) {
-    const int v = c[at];
-    return v < 0 ? 0 : (v > n_max ? n_max : v);
-}
 
 // order-preserving map of a float64 onto unsigned: a < b  <=>  key(a) < key(b); never 0 (0 marks a dropped row)
 __device__ __forceinline__ unsigned long long prob_key(double v) {
@@ -73,79 +69,12 @@ __device__ __forceinline__ bool side_point(const double *r, int order_xy, int sd
     return wr >= 0.0 && wr < (double)h_lim && wc >= 0.0 && wc < (double)w_lim;
 }
 
-__device__ __forceinline__ int block_sum(int v, int *s_red /*[16]*/) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();                                              // s_red is free
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    int t = 0;
-#pragma unroll
-    for (int w = 0; w < kSelThreads / 64; ++w) t += s_red[w];
-    return t;
-}
-
-// MSB-first radix select (the scheme of val_select_kernel, val_points.hip) over the keys key_of(i) of i < n that pass: the key of
-// rank `rank` (1-based) from the top / bottom; *n_same = entries with that key, *rank_in_same = how many of them reach `rank`.
-template <int BITS, bool FROM_TOP, typename KeyFn>
-__device__ unsigned long long radix_select(int n, int rank, KeyFn key_of, unsigned *s_hist /*[256]*/, int *s_tmp /*[4]*/,
-                                           int *n_same, int *rank_in_same) {
-    unsigned long long prefix = 0, mask = 0;
-    for (int shift = BITS - 8; shift >= 0; shift -= 8) {
-        for (int i = threadIdx.x; i < 256; i += kSelThreads) s_hist[i] = 0;
-        __syncthreads();
-        for (int i = threadIdx.x; i < n; i += kSelThreads) {
-            unsigned long long k;
-            if (key_of(i, &k) && (k & mask) == prefix) atomicAdd(&s_hist[(unsigned)(k >> shift) & 255u], 1u);
-        }
-        __syncthreads();
-        if (threadIdx.x < 64) {
-            const int l = threadIdx.x;
-            int h[4], sum = 0;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int t = 4 * l + i;
-                h[i] = (int)s_hist[FROM_TOP ? 255 - t : t];
-                sum += h[i];
-            }
-            int inc = sum;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const int v = __shfl_up(inc, d, 64);
-                if (l >= d) inc += v;
-            }
-            int cum = inc - sum;
-            if (cum < rank && rank <= inc) {                     // exactly one lane
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    if (cum + h[i] >= rank) {
-                        const int t = 4 * l + i;
-                        s_tmp[0] = FROM_TOP ? 255 - t : t;
-                        s_tmp[1] = rank - cum;
-                        s_tmp[2] = h[i];
-                        break;
-                    }
-                    cum += h[i];
-                }
-            }
-        }
-        __syncthreads();
-        prefix |= (unsigned long long)(unsigned)s_tmp[0] << shift;
-        mask |= 255ull << shift;
-        rank = s_tmp[1];
-        __syncthreads();
-    }
-    *n_same = s_tmp[2];
-    *rank_in_same = rank;
-    return prefix;
-}
-
 // grid (P, 2): blockIdx.y = side (0 source, 1 destination)
 __global__ __launch_bounds__(kSelThreads) void rr_select_kernel(RrArgs a) {
     __shared__ unsigned s_hist[256];
     __shared__ int s_tmp[4];
-    __shared__ int s_red[16];
-    const int p = blockIdx.x, sd = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ int s_red[kSelThreads / 64];
+    const int p = blockIdx.x, sd = blockIdx.y, tid = threadIdx.x;
     const RrSide &s = a.side[sd];
     const int n = clamp_count(s.count, (long)p * a.count_stride, s.n_max);
     const double *rows = s.rows + (long)p * s.n_max * s.stride;
@@ -162,27 +91,37 @@ __global__ __launch_bounds__(kSelThreads) void rr_select_kernel(RrArgs a) {
         keys[i] = in ? prob_key(prob) : 0ull;
         mine += in;
     }
-    const int n_in = block_sum(mine, s_red);                     // (its barriers also order the stores above before step 2)
+    const int n_in = block_sum<kSelThreads>(mine, s_red);        // (its barriers also order the stores above before step 2)
 
     // 2. select_k_best: key > thr, or key == thr with index <= idx_cut (higher prob first, then the lower original index)
     unsigned long long thr = 1ull;
     int idx_cut = 0x7fffffff;
     if (n_in > a.K) {
         int n_eq, need_eq;
-        thr = radix_select<64, true>(n, a.K, [keys](int i, unsigned long long *k) { *k = keys[i]; return *k != 0ull; }, s_hist,
-                                     s_tmp, &n_eq, &need_eq);
+        thr = radix_select<64, true, kSelThreads>(
+            a.K,
+            [&](auto count) {
+                for (int i = tid; i < n; i += kSelThreads) {
+                    const unsigned long long k = keys[i];
+                    if (k != 0ull) count(k);
+                }
+            },
+            s_hist, s_tmp, &n_eq, &need_eq);
         if (n_eq > need_eq) {
             int d0, d1;
             const unsigned long long t = thr;
-            idx_cut = (int)radix_select<32, false>(
-                n, need_eq, [keys, t](int i, unsigned long long *k) { *k = (unsigned long long)i; return keys[i] == t; }, s_hist,
-                s_tmp, &d0, &d1);
+            idx_cut = (int)radix_select<32, false, kSelThreads>(
+                need_eq,
+                [&](auto count) {
+                    for (int i = tid; i < n; i += kSelThreads)
+                        if (keys[i] == t) count((unsigned)i);
+                },
+                s_hist, s_tmp, &d0, &d1);
         }
     }
 
     // 3. ordered compaction of the kept rows (original order: the finalize sums depend on nothing else)
     double *out = a.kept + ((long)p * 2 + sd) * a.kcap * 2;
-    const unsigned long long below = (1ull << lane) - 1ull;
     int base = 0;
     for (int i0 = 0; i0 < n; i0 += kSelThreads) {
         const int i = i0 + tid;
@@ -191,23 +130,13 @@ __global__ __launch_bounds__(kSelThreads) void rr_select_kernel(RrArgs a) {
             const unsigned long long k = keys[i];
             keep = k != 0ull && (k > thr || (k == thr && i <= idx_cut));
         }
-        const unsigned long long b = __ballot(keep);
-        __syncthreads();                                         // s_red is free
-        if (lane == 0) s_red[wave] = __popcll(b);
-        __syncthreads();
-        int before = base, chunk = 0;
-#pragma unroll
-        for (int w = 0; w < kSelThreads / 64; ++w) { before += w < wave ? s_red[w] : 0; chunk += s_red[w]; }
-        if (keep) {
-            const int q = before + __popcll(b & below);
-            if (q < a.kcap) {                                    // (always: at most min(K, n_max) rows are kept)
-                double orow, ocol, prob;
-                side_point(rows + (long)i * s.stride, a.order_xy, sd, m, h_lim, w_lim, &orow, &ocol, &prob);
-                out[2 * q] = orow;
-                out[2 * q + 1] = ocol;
-            }
+        const int q = compact_slot<kSelThreads>(keep, s_red, base);
+        if (keep && q < a.kcap) {                                // (always: at most min(K, n_max) rows are kept)
+            double orow, ocol, prob;
+            side_point(rows + (long)i * s.stride, a.order_xy, sd, m, h_lim, w_lim, &orow, &ocol, &prob);
+            out[2 * q] = orow;
+            out[2 * q + 1] = ocol;
         }
-        base += chunk;
     }
     if (tid == 0) a.kept_n[2 * p + sd] = base < a.kcap ? base : a.kcap;
 }
@@ -309,15 +238,14 @@ int kept_cap(int ns_max, int nd_max, int K) {
 
 RrWs rr_layout(char *base, int P, int ns_max, int nd_max, int K) {
     RrWs w{};
-    size_t o = 0;
-    auto take = [&](size_t bytes) { char *p = base ? base + o : nullptr; o += balf_align_up(bytes, 256); return p; };
+    WorkspaceCursor c{base, 0};
     const size_t kcap = (size_t)kept_cap(ns_max, nd_max, K);
-    w.keys_s = (unsigned long long *)take((size_t)P * ns_max * 8);
-    w.keys_d = (unsigned long long *)take((size_t)P * nd_max * 8);
-    w.kept = (double *)take((size_t)P * 2 * kcap * 16);
-    w.mins = (double *)take((size_t)P * 2 * kcap * 8);
-    w.kept_n = (int *)take((size_t)P * 8);
-    w.total = o;
+    w.keys_s = c.take<unsigned long long>((size_t)P * ns_max * 8);
+    w.keys_d = c.take<unsigned long long>((size_t)P * nd_max * 8);
+    w.kept = c.take<double>((size_t)P * 2 * kcap * 16);
+    w.mins = c.take<double>((size_t)P * 2 * kcap * 8);
+    w.kept_n = c.take<int>((size_t)P * 8);
+    w.total = c.used;
     return w;
 }
 
@@ -452,7 +380,8 @@ extern "C" int balf_resize_crop_u8(const unsigned char *packed_dev, size_t packe
                                    const int32_t *sizes_dev, int B, int channels, int target_h, int target_w,
                                    unsigned char *out_dev, void *stream) {
     if (!packed_dev || !offsets_dev || !sizes_dev || !out_dev) return BALF_ERR_ARG;
-    if (B <= 0 || B > 65535 || (channels != 1 && channels != 3) || target_h <= 0 || target_w <= 0) return BALF_ERR_ARG;
+    if (B <= 0 || B > kMaxPairs /* B is grid z */ || (channels != 1 && channels != 3) || target_h <= 0 || target_w <= 0)
+        return BALF_ERR_ARG;
     if (target_h > 16384 || target_w > 16384) return BALF_ERR_SHAPE;
     resize_crop_kernel<<<dim3(balf_ceil_div(target_w, 64), balf_ceil_div(target_h, 4), B), dim3(64, 4), 0,
                          static_cast<hipStream_t>(stream)>>>(packed_dev, packed_bytes, offsets_dev, sizes_dev, channels, target_h,

@@ -19,6 +19,8 @@
 //          index keeps the raster-first K (`argwhere(map >= thr)[:K]`);
 //       3. the selected (flat index, score) pairs are sorted by flat index in LDS (bitonic) and written as float64 rows
 //          (x, y, 1.0, score); destination rows go through homography_point first.  Rows past the count are 0.
+//   The reduction, the select and the sort are the shared ones of block_ops.h.
+#include "block_ops.h"
 #include "common.h"
 #include "common_mask.h"
 #include "homography.h"
@@ -29,7 +31,6 @@ int balf_window_survivors_launch(const float *prob_dev, int B, int H, int W, int
 namespace balf {
 namespace {
 
-constexpr int kCommonBorder = 15;           // create_common_region_masks' fixed frame (geometry_tools.py:16,22)
 constexpr int kSelThreads = 1024;
 constexpr int kGreedyMaxDist = 16;          // balf_greedy_nms' limit
 
@@ -56,74 +57,6 @@ __device__ __forceinline__ int2 entry(const ValSide &s, long base, int i) {
     return s.surv ? s.surv[base + i] : make_int2(s.idx[base + i], __float_as_int(s.score[base + i]));
 }
 
-__device__ __forceinline__ int block_sum(int v, int *s_red /*[17]*/) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();                                              // s_red is free
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    int t = 0;
-#pragma unroll
-    for (int w = 0; w < kSelThreads / 64; ++w) t += s_red[w];
-    return t;
-}
-
-// Radix select over the 32-bit keys of the entries that pass `pred`: the key of rank `rank` (1-based) from the top (FROM_TOP) or
-// from the bottom; *n_same = entries carrying exactly that key, *rank_in_same = how many of them are needed to reach `rank`.
-// (The scheme of topk_select_kernel, nms_topk.hip, reading the list from memory: it is short or L2-resident.)
-template <bool FROM_TOP, typename KeyFn>
-__device__ unsigned radix_select(const ValSide &s, long base, int n, int rank, KeyFn key_of, unsigned *s_hist /*[256]*/,
-                                 int *s_tmp /*[4]*/, int *n_same, int *rank_in_same) {
-    unsigned prefix = 0, mask = 0;
-    for (int shift = 24; shift >= 0; shift -= 8) {
-        for (int i = threadIdx.x; i < 256; i += kSelThreads) s_hist[i] = 0;
-        __syncthreads();
-        for (int i = threadIdx.x; i < n; i += kSelThreads) {
-            unsigned k;
-            if (key_of(entry(s, base, i), &k) && (k & mask) == prefix) atomicAdd(&s_hist[(k >> shift) & 255u], 1u);
-        }
-        __syncthreads();
-        if (threadIdx.x < 64) {
-            const int l = threadIdx.x;
-            int h[4], sum = 0;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int t = 4 * l + i;
-                h[i] = (int)s_hist[FROM_TOP ? 255 - t : t];
-                sum += h[i];
-            }
-            int inc = sum;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const int v = __shfl_up(inc, d, 64);
-                if (l >= d) inc += v;
-            }
-            int cum = inc - sum;
-            if (cum < rank && rank <= inc) {                     // exactly one lane
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    if (cum + h[i] >= rank) {
-                        const int t = 4 * l + i;
-                        s_tmp[0] = FROM_TOP ? 255 - t : t;
-                        s_tmp[1] = rank - cum;
-                        s_tmp[2] = h[i];
-                        break;
-                    }
-                    cum += h[i];
-                }
-            }
-        }
-        __syncthreads();
-        prefix |= (unsigned)s_tmp[0] << shift;
-        mask |= 255u << shift;
-        rank = s_tmp[1];
-        __syncthreads();
-    }
-    *n_same = s_tmp[2];
-    *rank_in_same = rank;
-    return prefix;
-}
-
 // grid (P, 2): blockIdx.y = side (0 source, 1 destination)
 __global__ __launch_bounds__(kSelThreads) void val_select_kernel(ValArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -140,8 +73,7 @@ __global__ __launch_bounds__(kSelThreads) void val_select_kernel(ValArgs a) {
     const long base = (long)p * s.cap;
     const double *h = a.h + 9 * (long)p;
     double *out = s.out + (long)p * K * 4;
-    int n = s.count[p];
-    n = n < 0 ? 0 : (n > s.cap ? (int)s.cap : n);
+    const int n = clamp_count(s.count, p, (int)s.cap);          // (cap <= H * W < 2^31)
 
     // 1. the mask at every survivor
     double m_src[9], m_dst[9];
@@ -159,7 +91,7 @@ __global__ __launch_bounds__(kSelThreads) void val_select_kernel(ValArgs a) {
         else if (s.surv) s.surv[base + i].y = 0;
         else s.score[base + i] = 0.0f;
     }
-    const int n_pos = block_sum(mine, s_red);                    // (its barriers also order the stores above before step 2)
+    const int n_pos = block_sum<kSelThreads>(mine, s_red);        // (its barriers also order the stores above before step 2)
 
     if (n_pos == 0) {
         // 2a. no positive value in the masked map: the threshold falls back to 0.0 and `map >= 0` holds everywhere
@@ -178,15 +110,19 @@ __global__ __launch_bounds__(kSelThreads) void val_select_kernel(ValArgs a) {
     // survivor inside the mask (bits >= 1: positive floats order like their bits)
     unsigned thr = 1u;
     int idx_cut = 0x7fffffff;
+    auto each = [&](auto f) {                                    // f(entry) for every list entry of this thread
+        for (int i = tid; i < n; i += kSelThreads) f(entry(s, base, i));
+    };
     if (n_pos > K) {
         int n_eq, need_eq;
-        thr = radix_select<true>(s, base, n, K, [](int2 e, unsigned *k) { *k = (unsigned)e.y; return e.y > 0; }, s_hist, s_tmp,
-                                 &n_eq, &need_eq);
+        // (the list is read from memory in every pass: it is short or L2-resident)
+        thr = (unsigned)radix_select<32, true, kSelThreads>(
+            K, [&](auto count) { each([&](int2 e) { if (e.y > 0) count((unsigned)e.y); }); }, s_hist, s_tmp, &n_eq, &need_eq);
         if (n_eq > need_eq) {                                    // more than K reach the threshold: the raster-first K
             int d0, d1;
             const unsigned t = thr;
-            idx_cut = (int)radix_select<false>(
-                s, base, n, K, [t](int2 e, unsigned *k) { *k = (unsigned)e.x; return e.y > 0 && (unsigned)e.y >= t; }, s_hist,
+            idx_cut = (int)radix_select<32, false, kSelThreads>(
+                K, [&](auto count) { each([&](int2 e) { if (e.y > 0 && (unsigned)e.y >= t) count((unsigned)e.x); }); }, s_hist,
                 s_tmp, &d0, &d1);
         }
     }
@@ -195,28 +131,15 @@ __global__ __launch_bounds__(kSelThreads) void val_select_kernel(ValArgs a) {
     if (tid == 0) *s_cnt = 0;
     for (int i = tid; i < a.npow2; i += kSelThreads) keys[i] = ~0ull;
     __syncthreads();
-    for (int i = tid; i < n; i += kSelThreads) {
-        const int2 e = entry(s, base, i);
+    each([&](int2 e) {
         if (e.y > 0 && (unsigned)e.y >= thr && e.x <= idx_cut) {
             const int q = atomicAdd(s_cnt, 1);
             if (q < a.npow2) keys[q] = ((unsigned long long)(unsigned)e.x << 32) | (unsigned)e.y;
         }
-    }
+    });
     __syncthreads();
     const int cnt = *s_cnt < K ? *s_cnt : K;                     // (== *s_cnt: the selection holds at most K)
-    for (int k = 2; k <= a.npow2; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < a.npow2; i += kSelThreads) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const unsigned long long x = keys[i], y = keys[l];
-                    const bool up = ((i & k) == 0);
-                    if ((x > y) == up) { keys[i] = y; keys[l] = x; }
-                }
-            }
-            __syncthreads();
-        }
-    }
+    bitonic_sort<kSelThreads>(keys, a.npow2);
     for (int i = tid; i < K; i += kSelThreads) {
         double ox = 0.0, oy = 0.0, orad = 0.0, osc = 0.0;
         if (i < cnt) {
@@ -232,12 +155,6 @@ __global__ __launch_bounds__(kSelThreads) void val_select_kernel(ValArgs a) {
     if (tid == 0) a.count_out[2 * p + sd] = cnt;
 }
 
-int next_pow2(int v) {
-    int p = 1;
-    while (p < v) p <<= 1;
-    return p;
-}
-
 // a bound on what the greedy NMS can keep: one point per (d+1) x (d+1) cell
 long greedy_keep_bound(int H, int W, int d) { return (long)balf_ceil_div(H, d + 1) * balf_ceil_div(W, d + 1); }
 
@@ -249,23 +166,23 @@ struct SideWs {
 // the workspace slice of one side starting at byte `o`
 SideWs side_layout(size_t o, int P, int H, int W, int leg, int nms_size) {
     SideWs w{};
-    auto take = [&](size_t bytes) { const size_t at = o; o += balf_align_up(bytes, 256); return at; };
-    w.counts = take((size_t)P * 4);
+    WorkspaceCursor c{nullptr, o};
+    w.counts = c.offset((size_t)P * 4);
     if (leg == BALF_VAL_LEG_WINDOW) {
-        w.list = take((size_t)P * H * W * sizeof(int2));
+        w.list = c.offset((size_t)P * H * W * sizeof(int2));
     } else {
         w.kg = (int)greedy_keep_bound(H, W, nms_size);
-        w.idx = take((size_t)P * w.kg * 4);
-        w.score = take((size_t)P * w.kg * 4);
+        w.idx = c.offset((size_t)P * w.kg * 4);
+        w.score = c.offset((size_t)P * w.kg * 4);
         w.nms_ws_bytes = balf_greedy_nms_workspace_bytes(P, H, W, w.kg);
-        w.nms_ws = take(w.nms_ws_bytes);
+        w.nms_ws = c.offset(w.nms_ws_bytes);
     }
-    w.end = o;
+    w.end = c.used;
     return w;
 }
 
 int check_args(int P, int h_src, int w_src, int h_dst, int w_dst, int leg, int nms_size, int K) {
-    if (P <= 0 || P > 65535 || h_src <= 0 || w_src <= 0 || h_dst <= 0 || w_dst <= 0 || K <= 0 || K > BALF_MAX_TOPK)
+    if (P <= 0 || P > kMaxPairs || h_src <= 0 || w_src <= 0 || h_dst <= 0 || w_dst <= 0 || K <= 0 || K > BALF_MAX_TOPK)
         return BALF_ERR_ARG;
     if (leg == BALF_VAL_LEG_WINDOW) {
         if (nms_size < 1 || nms_size > BALF_MAX_NMS_SIZE) return BALF_ERR_ARG;
