@@ -83,6 +83,9 @@ PROTOTYPES = {
     "balf_resize_repeatability_batch": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, C.c_double,
                                             _vp, _vp, _vp, _sz, _vp]),
     "balf_resize_crop_u8": (_i, [_vp, _sz, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "balf_synth_pairs_workspace_bytes": (_sz, [_i, _i]),
+    "balf_synth_pairs": (_i, [_vp, _sz, _vp, _vp, _i, _vp, _vp, _vp, _fp, _i, _vp, _i, _i, _fp, _fp, _fp, _fp, _vp, _vp, _sz,
+                             _vp]),
     "balf_profile_num_slots": (_i, []),
     "balf_profile_slot_name": (C.c_char_p, [_i]),
     "balf_profile_begin": (_i, []),

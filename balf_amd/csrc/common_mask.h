@@ -6,7 +6,7 @@
 // 1/32 pixel (INTER_TAB_SIZE = 32, round half to even), the four bilinear weights are the exact products of those 5-bit
 // fractions.  Parity with cv2 itself is UNPINNED (checked against the oracle's restatement of the same algorithm only).
 //
-// fp contraction is OFF in both functions: every product and sum below is an individually rounded fp64 operation in source
+// fp contraction is OFF in every function here: every product and sum below is an individually rounded fp64 operation in source
 // order, so that the CPU oracle (NumPy, no FMA) reproduces the 1/32-pixel rounding bit for bit, and so that invert3 gives the
 // same bits on the host and on the device.
 #pragma once
@@ -21,6 +21,24 @@ __host__ __device__ __forceinline__ double ones_inner(int y, int x, int h, int w
     return (y >= b && y < h - b && x >= b && x < w - b) ? 1.0 : 0.0;      // zero outside the image too
 }
 
+// The source coordinates of output pixel (x, y) under the inverse map m (row-major, homogeneous), rounded to 1/32 pixel as
+// cv2.warpPerspective does: *sx, *sy the integer tap (floor), *fx, *fy the 5-bit fractions (0..31).  ONE definition, shared
+// by the masks below and by the 8-bit image warp (pair_synth.hip), so that the two sample the same coordinates.
+__device__ __forceinline__ void warp_source_q5(const double *m, int y, int x, int *sx, int *sy, int *fx, int *fy) {
+#pragma clang fp contract(off)
+    const double X0 = m[0] * x + m[1] * y + m[2];
+    const double Y0 = m[3] * x + m[4] * y + m[5];
+    double W = m[6] * x + m[7] * y + m[8];
+    W = W != 0.0 ? 32.0 / W : 0.0;
+    const double qx = fmax(-2147483648.0, fmin(2147483647.0, X0 * W));
+    const double qy = fmax(-2147483648.0, fmin(2147483647.0, Y0 * W));
+    const long long X = llrint(qx), Y = llrint(qy);                         // round half to even, like cvRound
+    *sx = (int)(X >> 5);
+    *sy = (int)(Y >> 5);
+    *fx = (int)(X & 31);
+    *fy = (int)(Y & 31);
+}
+
 // m: the inverse map, row-major (output pixel -> input coordinates, homogeneous); the mask is h_out x w_out, the all-ones
 // image being warped h_in x w_in, both with a zeroed `border` frame
 __device__ __forceinline__ double common_mask_pixel(const double *m, int y, int x, int h_out, int w_out, int h_in, int w_in,
@@ -28,15 +46,9 @@ __device__ __forceinline__ double common_mask_pixel(const double *m, int y, int 
 #pragma clang fp contract(off)
     double v = 0.0;
     if (y >= border && y < h_out - border && x >= border && x < w_out - border) {
-        const double X0 = m[0] * x + m[1] * y + m[2];
-        const double Y0 = m[3] * x + m[4] * y + m[5];
-        double W = m[6] * x + m[7] * y + m[8];
-        W = W != 0.0 ? 32.0 / W : 0.0;
-        const double fx = fmax(-2147483648.0, fmin(2147483647.0, X0 * W));
-        const double fy = fmax(-2147483648.0, fmin(2147483647.0, Y0 * W));
-        const long long X = llrint(fx), Y = llrint(fy);                     // round half to even, like cvRound
-        const int sx = (int)(X >> 5), sy = (int)(Y >> 5);
-        const double ax = (double)(X & 31) * (1.0 / 32.0), ay = (double)(Y & 31) * (1.0 / 32.0);
+        int sx, sy, fx, fy;
+        warp_source_q5(m, y, x, &sx, &sy, &fx, &fy);
+        const double ax = (double)fx * (1.0 / 32.0), ay = (double)fy * (1.0 / 32.0);
         const double s = ones_inner(sy, sx, h_in, w_in, border) * ((1.0 - ax) * (1.0 - ay)) +
                          ones_inner(sy, sx + 1, h_in, w_in, border) * (ax * (1.0 - ay)) +
                          ones_inner(sy + 1, sx, h_in, w_in, border) * ((1.0 - ax) * ay) +

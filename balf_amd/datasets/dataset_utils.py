@@ -2,10 +2,20 @@
 ``ratio_preserving_resize`` on the GPU (``balf_resize_crop_u8``, include/balf_hip.h) and ``adapt_homography_to_preprocessing``
 on the host.  The dataset walker ``Resize_HSequences`` (it reads files with cv2) is not ported.
 
+The geometry of the synthetic-homography pairs of the validation task (reference :137-192, :277-304 and COCO.py:97-142), on
+the host -- 3 x 3 arithmetic per pair: ``generate_homography``, ``get_dst_point``, ``get_window_point``,
+``sample_pair_geometry``, and ``select_k_best`` / ``labels_to_heatmap`` as NumPy restatements.  The per-pixel part (warp,
+crops, heat maps) is ``balf_synth_pairs`` (datasets/synthetic_pairs.py).  The two cv2 calls of ``generate_homography`` are
+written out (``getRotationMatrix2D`` in closed form, ``getPerspectiveTransform`` as the 8 x 8 float64 solve); their last
+bits against a cv2 build are UNPINNED.
+
 PARITY of the resize is UNPINNED: the reference resizes with ``cv2.resize`` and crops with imgaug, neither of which is
 available where this library is built.  The 8-bit arithmetic is defined in include/balf_hip.h after OpenCV's documented
 INTER_LINEAR scheme and has not been checked against a cv2 build."""
 from __future__ import annotations
+
+import math
+import random
 
 import numpy as np
 import torch
@@ -68,3 +78,134 @@ def ratio_preserving_resize(img, target_size):
     img = np.asarray(img)
     out = ratio_preserving_resize_batch([img], target_size)[0].cpu().numpy()
     return out[..., None] if img.ndim == 3 and img.shape[2] == 1 else out
+
+
+# ---- synthetic-homography pairs: the host side ------------------------------------------------------------------------------
+def get_dst_point(perspective, IMAGE_SHAPE, rng=None):
+    """The four perturbed corners (float32 [4,3], homogeneous), reference :161-192: seven ``random()`` draws in its order."""
+    rng = random if rng is None else rng
+    a, b, c, d, e, f = (rng.random() for _ in range(6))
+    if rng.random() > 0.5:
+        lt, rt = (perspective * a, perspective * b), (0.9 + perspective * c, perspective * d)
+        lb, rb = (perspective * a, 0.9 + perspective * e), (0.9 + perspective * c, 0.9 + perspective * f)
+    else:
+        lt, rt = (perspective * a, perspective * b), (0.9 + perspective * c, perspective * d)
+        lb, rb = (perspective * e, 0.9 + perspective * b), (0.9 + perspective * f, 0.9 + perspective * d)
+    return np.array([(IMAGE_SHAPE[1] * x, IMAGE_SHAPE[0] * y, 1) for x, y in (lt, rt, lb, rb)], dtype='float32')
+
+
+def rotation_matrix_2d(center, angle, scale):
+    """``cv2.getRotationMatrix2D`` in closed form (float64 [2,3]; the centre is taken as float32, as cv2's Point2f)."""
+    cx, cy = float(np.float32(center[0])), float(np.float32(center[1]))
+    alpha, beta = math.cos(angle * math.pi / 180.0) * scale, math.sin(angle * math.pi / 180.0) * scale
+    return np.array([[alpha, beta, (1 - alpha) * cx - beta * cy], [-beta, alpha, beta * cx + (1 - alpha) * cy]])
+
+
+def perspective_transform(src, dst):
+    """``cv2.getPerspectiveTransform`` of four point pairs (float32 [4,2]): OpenCV's 8 x 8 system solved in float64, the last
+    element 1.  Last bits against cv2 (its own LU) are unpinned."""
+    src, dst = np.asarray(src, np.float64), np.asarray(dst, np.float64)
+    a, b = np.zeros((8, 8)), np.zeros(8)
+    for i in range(4):
+        x, y = src[i]
+        a[i] = (x, y, 1, 0, 0, 0, -x * dst[i, 0], -y * dst[i, 0])
+        a[i + 4] = (0, 0, 0, x, y, 1, -x * dst[i, 1], -y * dst[i, 1])
+        b[i], b[i + 4] = dst[i]
+    return np.append(np.linalg.solve(a, b), 1.0).reshape(3, 3)
+
+
+def generate_homography(IMAGE_SHAPE, hom_config, rng=None):
+    """Reference :137-159: a random perspective + rotation + scale about a jittered centre, float64 [3,3].  Consumes the
+    ``random`` module (or the ``random.Random`` passed as ``rng``) in the reference's call order: ``get_dst_point``'s seven
+    draws, then four ``randint`` (rotation, scale, centre x, centre y)."""
+    rng = random if rng is None else rng
+    src_point = np.array([[0, 0], [IMAGE_SHAPE[1] - 1, 0], [0, IMAGE_SHAPE[0] - 1], [IMAGE_SHAPE[1] - 1, IMAGE_SHAPE[0] - 1]],
+                         dtype=np.float32)
+    dst_point = get_dst_point(hom_config['perspective'], IMAGE_SHAPE, rng)
+    rotation = hom_config['rotation']
+    rot = rng.randint(-rotation, rotation)
+    scale = 1.0 + hom_config['scale'] * rng.randint(-25, 50) * 0.1
+    center_offset = 40
+    center = (IMAGE_SHAPE[1] / 2 + rng.randint(-center_offset, center_offset),
+              IMAGE_SHAPE[0] / 2 + rng.randint(-center_offset, center_offset))
+    rs_mat = rotation_matrix_2d(center, rot, scale)
+    f_point = np.matmul(dst_point, rs_mat.T).astype('float32')
+    return perspective_transform(src_point, f_point)
+
+
+def get_window_point(shape, patch_size, crop_type='random', rng=None):
+    """Reference :295-304: the centre (row, col) of the source window.  The reference hands ``patch_size / 2`` (a float) to
+    ``randint``; here the bounds are converted to int first (the same draws for an even ``patch_size``)."""
+    rng = random if rng is None else rng
+    h, w = shape[0], shape[1]
+    if crop_type == 'random':
+        window_h = rng.randint(int(patch_size / 2), int(h - patch_size / 2))
+        window_w = rng.randint(int(patch_size / 2), int(w - patch_size / 2))
+    else:
+        window_h, window_w = h / 2, w / 2
+    return np.array([window_h, window_w])
+
+
+def select_k_best(points, k):
+    """Reference :277-286 restated: the ``k`` rows of largest prob (all for ``k == 0`` or fewer rows), in ascending prob.  Ties
+    at the cut keep the LOWER row index, the rule of ``balf_synth_pairs`` (the reference's argsort is unstable there)."""
+    points = np.asarray(points)
+    if points.shape[1] > 2 and k != 0:
+        order = np.argsort(-points[:, 2], kind="stable")[:min(k, points.shape[0])]
+        return points[order[::-1]]
+    return points
+
+
+def labels_to_heatmap(points, IMAGE_SHAPE):
+    """Reference :288-292: float32 [H,W], 1 at the truncated (y, x) of every point."""
+    heatmap = np.zeros((IMAGE_SHAPE[0], IMAGE_SHAPE[1]))
+    points = np.asarray(points).astype(int)
+    heatmap[points[:, 1], points[:, 0]] = 1
+    return heatmap.astype('float32')
+
+
+def compose_pair_homographies(h, point_src, point_dst, patch_size):
+    """COCO.py:111-116 and :135-142: the homographies between the two PATCHES -> (h_src_2_dst, h_dst_2_src) float32 [3,3]:
+    float64 ``np.dot`` / ``np.linalg.inv``, then the float32 cast, then the division by [2,2]."""
+    h_src_translation = np.asanyarray([[1., 0., -(int(point_src[1]) - patch_size / 2)],
+                                       [0., 1., -(int(point_src[0]) - patch_size / 2)],
+                                       [0., 0., 1.]])
+    h_dst_translation = np.asanyarray([[1., 0., int(point_dst[1] - patch_size / 2)],
+                                       [0., 1., int(point_dst[0] - patch_size / 2)],
+                                       [0., 0., 1.]])
+    homography = np.dot(h_src_translation, np.dot(h, h_dst_translation))
+    h_dst_2_src = homography.astype('float32')
+    h_dst_2_src = h_dst_2_src / h_dst_2_src[2, 2]
+    h_src_2_dst = np.linalg.inv(homography).astype('float32')
+    h_src_2_dst = h_src_2_dst / h_src_2_dst[2, 2]
+    return h_src_2_dst, h_dst_2_src
+
+
+def sample_pair_geometry(shape, hom_config, patch_size, rng=None, max_draws=10000):
+    """The random part of one pair of the reference's loader (COCO.py:53-142) for an image of ``shape`` (h, w[, c]): draw a
+    homography, the source window, map its centre with ``inv_h``; a destination window that leaves the image redraws the pair
+    FROM THE HOMOGRAPHY ON, as the reference's loop does.  -> dict: ``inv_h`` float64 [3,3] (what ``cv2.warpPerspective`` is
+    handed), ``win_src`` / ``win_dst`` (top row, left column) ints, ``h_src_2_dst`` / ``h_dst_2_src`` float32 [3,3].
+    Not reproduced: the reference also redraws a homography whose whole warped image is black (see SyntheticPairs)."""
+    rng = random if rng is None else rng
+    half = patch_size / 2
+    if shape[0] < patch_size or shape[1] < patch_size:
+        raise ValueError(f"an image of {tuple(shape[:2])} holds no {patch_size} x {patch_size} window")
+    for _ in range(max_draws):
+        h = generate_homography(shape, hom_config, rng)
+        inv_h = np.linalg.inv(h)
+        inv_h = inv_h / inv_h[2, 2]
+        point_src = get_window_point(shape, patch_size, rng=rng)
+        point_dst = inv_h.dot([point_src[1], point_src[0], 1.0])
+        point_dst = [point_dst[1] / point_dst[2], point_dst[0] / point_dst[2]]
+        if (point_dst[0] - half) < 0 or (point_dst[1] - half) < 0:
+            continue
+        if (point_dst[0] + half) > shape[0] or (point_dst[1] + half) > shape[1]:
+            continue
+        win_src = (int(point_src[0] - half), int(point_src[1] - half))
+        win_dst = (int(point_dst[0] - half), int(point_dst[1] - half))
+        if any(int(c + half) - int(c - half) != patch_size for c in point_dst):     # the reference's final shape check
+            continue
+        h_src_2_dst, h_dst_2_src = compose_pair_homographies(h, point_src, point_dst, patch_size)
+        return {"inv_h": inv_h, "win_src": win_src, "win_dst": win_dst, "h_src_2_dst": h_src_2_dst, "h_dst_2_src": h_dst_2_src}
+    raise RuntimeError(f"no destination window inside the image in {max_draws} draws: {hom_config} on {tuple(shape[:2])}")

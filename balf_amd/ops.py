@@ -466,3 +466,57 @@ def resize_crop_u8(packed: torch.Tensor, offsets: torch.Tensor, sizes: torch.Ten
                                         int(channels), int(target_h), int(target_w), out.data_ptr(),
                                         current_stream_ptr(dev)), "balf_resize_crop_u8")
     return out
+
+
+# ---- synthetic-homography image pairs of the validation task (datasets/synthetic_pairs.py drives this) ----------------------
+def synth_pairs(packed: torch.Tensor, offsets: torch.Tensor, sizes: torch.Tensor, inv_h: torch.Tensor, win_src: torch.Tensor,
+                win_dst: torch.Tensor, pts: torch.Tensor, pts_offsets: torch.Tensor, top_k: int, patch: int, out=None):
+    """The image patches and heat maps of P synthetic-homography pairs in one call (balf_synth_pairs in include/balf_hip.h):
+    ``packed`` the uint8 RGB-interleaved source images back to back (1-D), ``offsets`` [P] int64 byte offsets, ``sizes`` [P,2]
+    int32 (h, w), ``inv_h`` [P,3,3] (or [P,9]) float64 -- the matrix the reference hands to ``cv2.warpPerspective`` --,
+    ``win_src`` / ``win_dst`` [P,2] int32 (top row, left column), ``pts`` [N,3] float32 label rows (x, y, prob),
+    ``pts_offsets`` [P+1] int32; everything on the GPU.  Returns (img_src [P,3,patch,patch], img_dst [P,3,patch,patch],
+    heat_src [P,1,patch,patch], heat_dst [P,1,patch,patch] float32, dst_max [P] int32); ``out`` = such a 5-tuple to write into
+    instead of allocating.  Nothing is read back: a window that leaves its image shows as ``dst_max == -1``."""
+    for t, name in ((packed, "packed"), (offsets, "offsets"), (sizes, "sizes"), (inv_h, "inv_h"), (win_src, "win_src"),
+                    (win_dst, "win_dst"), (pts, "pts"), (pts_offsets, "pts_offsets")):
+        require_gpu_tensor(t, name)
+    p = offsets.shape[0] if offsets.dim() == 1 else 0
+    if packed.dtype != torch.uint8 or packed.dim() != 1 or offsets.dtype != torch.int64 or p == 0 or \
+            sizes.dtype != torch.int32 or tuple(sizes.shape) != (p, 2):
+        raise BalfHipError("packed must be a 1-D uint8 tensor, offsets [P] int64 and sizes [P,2] int32 with P > 0")
+    dev = packed.device
+    for t, name, shapes_ok, dt in ((inv_h, "inv_h", ((p, 3, 3), (p, 9)), torch.float64), (win_src, "win_src", ((p, 2),), torch.int32),
+                                   (win_dst, "win_dst", ((p, 2),), torch.int32),
+                                   (pts_offsets, "pts_offsets", ((p + 1,),), torch.int32)):
+        if tuple(t.shape) not in shapes_ok or t.dtype != dt or t.device != dev:
+            raise BalfHipError(f"{name} must be a {' or '.join(map(str, shapes_ok))} {dt} tensor on {dev}")
+    if pts.dtype != torch.float32 or pts.dim() != 2 or pts.shape[1] != 3 or pts.device != dev:
+        raise BalfHipError(f"pts must be an [N,3] float32 tensor on {dev}")
+    top_k, patch = int(top_k), int(patch)
+    if top_k < 0:
+        raise ValueError(f"top_k must be >= 0 (0 keeps every row), got {top_k}")
+    if patch <= 0:
+        raise ValueError(f"patch must be positive, got {patch}")
+    l = lib()
+    nbytes = l.balf_synth_pairs_workspace_bytes(p, patch)
+    if nbytes == 0:
+        raise BalfHipError(f"balf_synth_pairs: unsupported sizes P={p}, patch={patch}")
+    shapes = ((p, 3, patch, patch), (p, 3, patch, patch), (p, 1, patch, patch), (p, 1, patch, patch), (p,))
+    if out is None:
+        out = tuple(torch.empty(s, dtype=torch.int32 if len(s) == 1 else torch.float32, device=dev) for s in shapes)
+    else:
+        if len(out) != 5:
+            raise BalfHipError("out must be (img_src, img_dst, heat_src, heat_dst, dst_max)")
+        for t, s in zip(out, shapes):
+            require_gpu_tensor(t, "out")
+            if tuple(t.shape) != s or t.dtype != (torch.int32 if len(s) == 1 else torch.float32) or t.device != dev:
+                raise BalfHipError(f"out tensors must be {shapes} (float32, dst_max int32) on {dev}")
+    ws = _workspace("synth_pairs", dev, nbytes)
+    with torch.cuda.device(dev):
+        check(l.balf_synth_pairs(packed.data_ptr(), packed.numel(), offsets.data_ptr(), sizes.data_ptr(), p, inv_h.data_ptr(),
+                                 win_src.data_ptr(), win_dst.data_ptr(), pts.data_ptr() if pts.shape[0] else None,
+                                 pts.shape[0], pts_offsets.data_ptr(), top_k, patch, out[0].data_ptr(), out[1].data_ptr(),
+                                 out[2].data_ptr(), out[3].data_ptr(), out[4].data_ptr(), ws.data_ptr(), ws.numel(),
+                                 current_stream_ptr(dev)), "balf_synth_pairs")
+    return tuple(out)

@@ -435,6 +435,52 @@ int balf_resize_crop_u8(const unsigned char *packed_dev, size_t packed_bytes, co
                         const int32_t *sizes_dev, int B, int channels, int target_h, int target_w, unsigned char *out_dev,
                         void *stream);
 
+/* ---- synthetic-homography image pairs of the validation task (balf/datasets/COCO.py:42-205; GOPRO inherits it) -----------
+ * balf_synth_pairs: what the reference's loader computes per pair AFTER the homography and the two windows are drawn (host:
+ * balf_amd/datasets/dataset_utils.py: sample_pair_geometry), for P pairs, stream-ordered, nothing read back, capturable.  Only
+ * the patch x patch windows are computed; the full warped image and the full-size heat maps are never formed.
+ * Inputs: packed_dev the uint8 RGB-interleaved source images back to back, image p = sizes_dev[p] = (h, w) int32 at byte
+ * offsets_dev[p] (int64), as balf_resize_crop_u8 takes them (pairs may share an image); inv_h_dev [P,9] float64 row-major, the
+ * matrix the reference hands to cv2.warpPerspective (COCO.py:67-68,75); win_src_dev / win_dst_dev [P,2] int32 = (top row, left
+ * column) of the two windows in full-image coordinates; pts_dev [pts_total,3] float32 label rows (x, y, prob), pair p's rows
+ * are pts_offsets_dev[p] .. pts_offsets_dev[p + 1] (int32, P + 1 entries; a range outside [0, pts_total] counts as empty).
+ * Outputs (float32): img_src_dev / img_dst_dev [P,3,patch,patch] planar, heat_src_dev / heat_dst_dev [P,1,patch,patch],
+ * dst_max_dev [P] int32.  Per pair:
+ *   source patch       (float)((double)byte / 255.0) of the source window (the reference divides in float64, then narrows).
+ *   destination patch  cv2.warpPerspective(src, inv_h, (w, h)) with default flags (bilinear, constant-zero border) for 8-bit
+ *                      3-channel data at the destination window's pixels, DEFINED here as OpenCV's 8-bit INTER_LINEAR remap is
+ *                      documented to work (parity with a cv2 build is unpinned): output pixel (x, y) samples
+ *                      M (x, y, 1), M = the closed-form inverse of inv_h, exactly as balf_common_region_masks does (one shared
+ *                      device function): X = M0 x + M1 y + M2 etc. in float64 without fused operations, 32 / W (0 for W = 0),
+ *                      clamped to the int range, rounded half to even; tap = value >> 5, fractions fx, fy = value & 31.
+ *                      Integer weights (32-fx)(32-fy)32, fx(32-fy)32, (32-fx)fy 32, fx fy 32 (sum 32768); a tap outside the
+ *                      source image contributes 0; byte = (sum + 16384) >> 15; then / 255 as above.  A singular inv_h gives an
+ *                      all-zero patch.
+ *   dst_max            the largest byte of the destination patch (0: an all-black patch).  The reference redraws a homography
+ *                      whose WHOLE warped image is black (COCO.py:77); that image is never formed here, nothing is redrawn, and
+ *                      the caller gets this value instead.
+ *   labels             select_k_best (dataset_utils.py:277-286): the top_k rows of largest prob; top_k == 0 or fewer rows than
+ *                      top_k keep all.  Ties at the cut keep the LOWER row index (the reference cuts with NumPy's unstable
+ *                      argsort: arbitrary there).  Kept points are truncated to integers (xi, yi).
+ *   source heat map    1.0 at (yi, xi) of each kept point inside the source window, 0 elsewhere (labels_to_heatmap, :288-292;
+ *                      a point outside the image is dropped, where NumPy would wrap a negative index or raise).
+ *   dest. heat map     apply_homography_to_source_labels_torch as it returns (:200-219; its bilinear labels are discarded by
+ *                      the reference and not computed): (xi, yi) warped with inv_h NARROWED TO float32 in float32 arithmetic
+ *                      without fused operations, x' = ((h0 xi + h1 yi) + h2) / ((h6 xi + h7 yi) + h8); kept where 0 <= x' <=
+ *                      w - 1 and 0 <= y' <= h - 1 of the FULL image; rounded half to even; 1.0 where the rounded point lies
+ *                      inside the destination window, 0 elsewhere.
+ * The heat maps are zeroed by the call itself.  An image that does not lie inside packed_bytes gives all-zero outputs; a window
+ * that leaves its image is read clamped (source) / evaluated where it lies (destination); both report dst_max = -1 (the
+ * windows live on the device, so the host cannot refuse them).
+ * Limits: 1 <= P <= 65535, patch >= 1, top_k >= 0, pts_total >= 0 (BALF_ERR_ARG); patch <= 16384 (BALF_ERR_SHAPE).  pts_dev
+ * may be null when pts_total is 0.  The workspace holds one int per 1024 output pixels and pair. */
+size_t balf_synth_pairs_workspace_bytes(int P, int patch);
+int balf_synth_pairs(const unsigned char *packed_dev, size_t packed_bytes, const long long *offsets_dev,
+                     const int32_t *sizes_dev, int P, const double *inv_h_dev, const int32_t *win_src_dev,
+                     const int32_t *win_dst_dev, const float *pts_dev, int pts_total, const int32_t *pts_offsets_dev,
+                     int top_k, int patch, float *img_src_dev, float *img_dst_dev, float *heat_src_dev, float *heat_dst_dev,
+                     int32_t *dst_max_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+
 /* ---- measurement aid (not part of the data path) ---------------------------------------------
  * Between balf_profile_begin() and balf_profile_end() every kernel launch of the library is bracketed
  * by a hipEvent pair on its launch stream.  balf_profile_end() waits for those events and returns,
