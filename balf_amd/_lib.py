@@ -77,6 +77,8 @@ PROTOTYPES = {
     "balf_repeatability_batch_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "balf_repeatability_batch": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, C.c_double, C.c_double, C.c_double,
                                      C.c_double, _i, _vp, _vp, _vp, _sz, _vp]),
+    "balf_common_points_index_batch": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "balf_match_accuracy_batch": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, C.POINTER(C.c_double), _i, _vp, _vp, _vp]),
     "balf_val_points_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i, _i]),
     "balf_val_points": (_i, [_fp, _i, _i, _fp, _i, _i, _i, _vp, _i, C.c_float, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "balf_resize_repeatability_batch_workspace_bytes": (_sz, [_i, _i, _i, _i]),

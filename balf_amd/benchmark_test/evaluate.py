@@ -6,9 +6,16 @@ Per pair, :func:`evaluate_pairs` does what that loop does with the one-pair func
 destination rows -> ``compute_repeatability`` -- with the same bits, but stream-ordered and without a host round trip: the
 masks are evaluated at the points only (``balf_common_points_batch``) and the repeatability of all pairs runs in one sequence
 of launches (``balf_repeatability_batch``).  Everything stays on the device; nothing is read back.
+
+:func:`evaluate_matching_pairs` adds the matching score of the same pairs (the ``mma`` / ``mma_corr`` /
+``num_matches`` / ``num_mutual_corresp`` / ``avg_mma`` fields of the reference's result record, which its public tree never
+fills): the filter also reports which original row each kept row was (``balf_common_points_index_batch``), the per-image
+descriptors are gathered through that, matched (``ops.match_smnn_batch``) and the matches verified against the homography
+(``balf_match_accuracy_batch``).  :func:`evaluate_matching_hsequences` is the driver over a dataset.
 """
 from __future__ import annotations
 
+import ctypes as C
 from typing import NamedTuple
 
 import numpy as np
@@ -49,11 +56,18 @@ def _pair_tensor(t, dev, name, shapes_ok, dtype):
     return t if t.dtype == dtype else t.to(dtype)
 
 
-def common_points_batch(src_pts, src_count, dst_pts, dst_count, h_dst_2_src, shapes) -> CommonPoints:
-    """``check_common_points`` of both lists against the pair's common-region masks, then ``apply_homography_to_points`` of
-    the kept destination rows (``balf_common_points_batch``, include/balf_hip.h).  ``src_pts`` [P,Ns,4] / ``dst_pts``
-    [P,Nd,4] float64 rows (x, y, radius, score) with counts ``src_count`` / ``dst_count`` [P] int32, ``h_dst_2_src``
-    [P,3,3] float64, ``shapes`` [P,4] int32 = (h_src, w_src, h_dst, w_dst), all on the GPU."""
+class CommonPointsIndex(NamedTuple):
+    src: torch.Tensor           # the four fields of CommonPoints, bit-identical to common_points_batch's
+    dst_to_src: torch.Tensor
+    kept: torch.Tensor
+    valid: torch.Tensor
+    src_index: torch.Tensor     # [P,Ns] int32: the row of src_pts each kept source row came from, -1 past the kept count
+    dst_index: torch.Tensor     # [P,Nd] int32: likewise for the destination rows
+
+
+def _common_points_args(src_pts, src_count, dst_pts, dst_count, h_dst_2_src, shapes):
+    """The checked inputs and the four outputs both filter calls share -> (the outputs as a CommonPoints, the leading C
+    arguments up to valid_dev)."""
     for t, name in ((src_pts, "src_pts"), (dst_pts, "dst_pts")):
         require_gpu_tensor(t, name)
         if t.dtype != torch.float64 or t.dim() != 3 or t.shape[2] != 4:
@@ -66,16 +80,40 @@ def common_points_batch(src_pts, src_count, dst_pts, dst_count, h_dst_2_src, sha
     nd = _counts(dst_count, p, dev, "dst_count").contiguous()
     h = _pair_tensor(h_dst_2_src, dev, "h_dst_2_src", ((p, 3, 3), (p, 9)), torch.float64)
     sh = _pair_tensor(shapes, dev, "shapes", ((p, 4),), torch.int32)
-    src_out = torch.empty_like(src_pts)
-    dst_out = torch.empty_like(dst_pts)
-    kept = torch.empty((p, 2), dtype=torch.int32, device=dev)
-    valid = torch.empty((p,), dtype=torch.int32, device=dev)
+    out = CommonPoints(torch.empty_like(src_pts), torch.empty_like(dst_pts),
+                       torch.empty((p, 2), dtype=torch.int32, device=dev), torch.empty((p,), dtype=torch.int32, device=dev))
+    # (ns, nd, h, sh may be fresh conversions: the tuple keeps them alive until the launch is enqueued)
+    keep = (ns, nd, h, sh)
+    args = (src_pts.data_ptr(), ns.data_ptr(), ns_max, dst_pts.data_ptr(), nd.data_ptr(), nd_max, p, h.data_ptr(), sh.data_ptr(),
+            out.src.data_ptr(), out.dst_to_src.data_ptr(), out.kept.data_ptr(), out.valid.data_ptr())
+    return out, args, keep
+
+
+def common_points_batch(src_pts, src_count, dst_pts, dst_count, h_dst_2_src, shapes) -> CommonPoints:
+    """``check_common_points`` of both lists against the pair's common-region masks, then ``apply_homography_to_points`` of
+    the kept destination rows (``balf_common_points_batch``, include/balf_hip.h).  ``src_pts`` [P,Ns,4] / ``dst_pts``
+    [P,Nd,4] float64 rows (x, y, radius, score) with counts ``src_count`` / ``dst_count`` [P] int32, ``h_dst_2_src``
+    [P,3,3] float64, ``shapes`` [P,4] int32 = (h_src, w_src, h_dst, w_dst), all on the GPU."""
+    out, args, _keep = _common_points_args(src_pts, src_count, dst_pts, dst_count, h_dst_2_src, shapes)
+    dev = src_pts.device
     with torch.cuda.device(dev):
-        check(lib().balf_common_points_batch(src_pts.data_ptr(), ns.data_ptr(), ns_max, dst_pts.data_ptr(), nd.data_ptr(),
-                                             nd_max, p, h.data_ptr(), sh.data_ptr(), src_out.data_ptr(), dst_out.data_ptr(),
-                                             kept.data_ptr(), valid.data_ptr(), current_stream_ptr(dev)),
-              "balf_common_points_batch")
-    return CommonPoints(src_out, dst_out, kept, valid)
+        check(lib().balf_common_points_batch(*args, current_stream_ptr(dev)), "balf_common_points_batch")
+    return out
+
+
+def common_points_index_batch(src_pts, src_count, dst_pts, dst_count, h_dst_2_src, shapes) -> CommonPointsIndex:
+    """:func:`common_points_batch` -- same inputs, the same four outputs bit for bit -- plus ``src_index`` [P,Ns] /
+    ``dst_index`` [P,Nd] int32: the original row of each kept row in kept order, -1 past the kept count
+    (``balf_common_points_index_batch``).  Whatever was computed per detected row -- a descriptor -- follows its row into
+    the kept list through them."""
+    out, args, _keep = _common_points_args(src_pts, src_count, dst_pts, dst_count, h_dst_2_src, shapes)
+    dev = src_pts.device
+    src_index = torch.empty(src_pts.shape[:2], dtype=torch.int32, device=dev)
+    dst_index = torch.empty(dst_pts.shape[:2], dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().balf_common_points_index_batch(*args, src_index.data_ptr(), dst_index.data_ptr(), current_stream_ptr(dev)),
+              "balf_common_points_index_batch")
+    return CommonPointsIndex(*out, src_index, dst_index)
 
 
 def evaluate_pairs(src_pts, src_count, dst_pts, dst_count, h_dst_2_src, shapes, **repeat_kw) -> PairEvaluation:
@@ -89,6 +127,135 @@ def evaluate_pairs(src_pts, src_count, dst_pts, dst_count, h_dst_2_src, shapes, 
     cp = common_points_batch(src_pts, src_count, dst_pts, dst_count, h_dst_2_src, shapes)
     r: RepeatabilityBatch = compute_repeatability_batch(cp.src, cp.kept[:, 0], cp.dst_to_src, cp.kept[:, 1], **repeat_kw)
     return PairEvaluation(*r, cp.valid, cp.kept)
+
+
+# ---- the matching score ------------------------------------------------------------------------------------------
+MAX_THRESHOLDS = 16
+
+
+class MatchingEvaluation(NamedTuple):
+    """Per-pair results of :func:`evaluate_matching_pairs`, device tensors: every field of :class:`PairEvaluation`, then the
+    matching score."""
+    rep_single_scale: torch.Tensor
+    rep_multi_scale: torch.Tensor
+    error_overlap_single_scale: torch.Tensor
+    error_overlap_multi_scale: torch.Tensor
+    num_points_single_scale: torch.Tensor
+    num_points_multi_scale: torch.Tensor
+    possible_matches: torch.Tensor
+    total_num_points: torch.Tensor
+    candidates_single_scale: torch.Tensor
+    candidates_multi_scale: torch.Tensor
+    valid: torch.Tensor
+    kept: torch.Tensor
+    num_mutual_corresp: torch.Tensor    # [P] int32: M, the mutual ratio-test matches between the kept lists
+    num_matches: torch.Tensor           # [P] int32: those within pixel_threshold
+    correct: torch.Tensor               # [P,T] int32: those within each threshold
+    mma: torch.Tensor                   # [P] float64: num_matches / M (0 for M == 0)
+    mma_corr: torch.Tensor              # [P] float64: num_matches / possible_matches (0 for possible_matches == 0)
+    avg_mma: torch.Tensor               # [P] float64: mean over the thresholds of correct / M (0 for M == 0)
+    match_idx: torch.Tensor             # [P,cap,2] int32: (row of the kept source list, row of the kept destination list), -1 padded
+    match_err: torch.Tensor             # [P,cap] float64: reprojection error in source pixels, NaN past M
+
+
+def _thresholds(thresholds):
+    """-> (the thresholds as Python floats, as a ctypes array): 1..16 of them, >= 0 and strictly ascending."""
+    ths = [float(t) for t in thresholds]
+    if not 1 <= len(ths) <= MAX_THRESHOLDS:
+        raise BalfHipError(f"between 1 and {MAX_THRESHOLDS} thresholds, got {len(ths)}")
+    if not ths[0] >= 0.0 or any(not b > a for a, b in zip(ths, ths[1:])):
+        raise BalfHipError(f"thresholds must be >= 0 and strictly ascending, got {ths}")
+    return ths, (C.c_double * len(ths))(*ths)
+
+
+def match_accuracy_batch(src, dst, kept, match_idx, match_count, thresholds):
+    """The matches of P pairs verified against the homography (``balf_match_accuracy_batch``, include/balf_hip.h).  ``src``
+    [P,Ns,4] / ``dst`` [P,Nd,4] float64: the kept source rows and the kept destination rows warped into the source image
+    (:func:`common_points_index_batch`), ``kept`` [P,2] int32 their lengths; ``match_idx`` [P,cap,2] int32 / ``match_count``
+    [P] int32 as ``ops.match_smnn_batch`` returns them; ``thresholds``: 1..16 ascending pixel thresholds on the host.
+    Returns (``err`` [P,cap] float64: ``sqrt(dx*dx + dy*dy)`` per match, NaN past the count and for an index outside the kept
+    lists; ``correct`` [P,T] int32: the matches with ``err <= thresholds[k]``).  Nothing is read back."""
+    ths, th_arr = _thresholds(thresholds)
+    for t, name in ((src, "src"), (dst, "dst")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.dim() != 3 or t.shape[2] != 4:
+            raise BalfHipError(f"{name} must be a [P,N,4] float64 tensor: rows (x, y, radius, score)")
+    p = src.shape[0]
+    if dst.shape[0] != p or p == 0:
+        raise BalfHipError(f"src and dst must hold the same number (> 0) of pairs, got {p} and {dst.shape[0]}")
+    if not isinstance(match_idx, torch.Tensor) or match_idx.dtype != torch.int32 or match_idx.dim() != 3 or \
+            match_idx.shape[0] != p or match_idx.shape[2] != 2:
+        raise BalfHipError(f"match_idx must be a [{p},cap,2] int32 tensor")
+    if not isinstance(kept, torch.Tensor) or kept.dtype != torch.int32 or tuple(kept.shape) != (p, 2):
+        raise BalfHipError(f"kept must be a [{p},2] int32 tensor")
+    dev = src.device
+    for t, name in ((src, "src"), (dst, "dst"), (kept, "kept"), (match_idx, "match_idx")):
+        require_gpu_tensor(t, name)
+        if t.device != dev:
+            raise BalfHipError(f"{name} must be on {dev} like src, got {t.device}")
+    count = _counts(match_count, p, dev, "match_count").contiguous()
+    cap = match_idx.shape[1]
+    err = torch.empty((p, cap), dtype=torch.float64, device=dev)
+    correct = torch.empty((p, len(ths)), dtype=torch.int32, device=dev)
+    if cap == 0:
+        return err, correct.zero_()
+    with torch.cuda.device(dev):
+        check(lib().balf_match_accuracy_batch(src.data_ptr(), src.shape[1], dst.data_ptr(), dst.shape[1], kept.data_ptr(),
+                                              match_idx.data_ptr(), count.data_ptr(), cap, p, th_arr, len(ths), err.data_ptr(),
+                                              correct.data_ptr(), current_stream_ptr(dev)), "balf_match_accuracy_batch")
+    return err, correct
+
+
+def _ratio(num, den):
+    """num / den in float64 per pair, 0 where den == 0 (int32 in: the quotient of the exact integers, rounded once)."""
+    den = den.to(torch.float64)
+    zero = den == 0
+    return torch.where(zero, torch.zeros_like(den), num.to(torch.float64) / torch.where(zero, torch.ones_like(den), den))
+
+
+def evaluate_matching_pairs(src_pts, src_count, src_desc, dst_pts, dst_count, dst_desc, h_dst_2_src, shapes, th=0.99,
+                            thresholds=range(1, 11), pixel_threshold=5, **repeat_kw) -> MatchingEvaluation:
+    """:func:`evaluate_pairs` plus the matching score of the same P pairs.  Inputs as :func:`evaluate_pairs`,
+    and ``src_desc`` [P,Ns,128] / ``dst_desc`` [P,Nd,128] float32: the descriptor of every DETECTED row, computed once per
+    image (``desc[pair_src_image]`` is what the driver passes).  Per pair:
+
+    * the common-region filter reports the original row of each kept row (:func:`common_points_index_batch`) and each kept
+      row takes that row's descriptor (a gather on the device);
+    * ``ops.match_smnn_batch`` of the kept source descriptors against the kept destination descriptors with ratio ``th``
+      (0.99 is the demo's value; ``th >= 1`` keeps every mutual nearest-neighbour pair) gives M matches (i, j);
+    * ``match_err`` = the distance in source pixels between kept source row i and warped kept destination row j, ``correct[k]``
+      = the matches within ``thresholds[k]`` (:func:`match_accuracy_batch`; ascending, at most 16, ``pixel_threshold`` one of
+      them);
+    * ``num_mutual_corresp`` = M, ``num_matches`` = correct at ``pixel_threshold``, ``mma`` = num_matches / M, ``mma_corr`` =
+      num_matches / possible_matches, ``avg_mma`` = the ratios correct[k] / M summed in ascending k, divided by T; a ratio with
+      a zero denominator is 0.
+
+    A pair with ``valid == 0`` has M = 0; it is left out of every mean, as in the repeatability loop.  Returns device tensors,
+    reads nothing back, and can be captured with ``torch.cuda.graph`` when every input is a device tensor."""
+    from .. import ops
+    ths, _ = _thresholds(thresholds)
+    if float(pixel_threshold) not in ths:
+        raise BalfHipError(f"pixel_threshold {pixel_threshold} is not one of the thresholds {ths}")
+    k_star = ths.index(float(pixel_threshold))
+    for d, pts, name in ((src_desc, src_pts, "src_desc"), (dst_desc, dst_pts, "dst_desc")):
+        if not isinstance(d, torch.Tensor) or not isinstance(pts, torch.Tensor) or d.dim() != 3 or d.shape[2] != 128 or \
+                tuple(d.shape[:2]) != tuple(pts.shape[:2]):
+            raise BalfHipError(f"{name} must be a [P,N,128] tensor: one descriptor per row of the point list")
+        require_gpu_tensor(d, name)
+    cp = common_points_index_batch(src_pts, src_count, dst_pts, dst_count, h_dst_2_src, shapes)
+    r: RepeatabilityBatch = compute_repeatability_batch(cp.src, cp.kept[:, 0], cp.dst_to_src, cp.kept[:, 1], **repeat_kw)
+
+    def kept_rows(desc, index):                                  # (rows past the kept count: row 0's descriptor, never matched)
+        return torch.gather(desc.float(), 1, index.clamp(min=0).to(torch.int64).unsqueeze(2).expand(-1, -1, 128))
+
+    _, match_idx, m = ops.match_smnn_batch(kept_rows(src_desc, cp.src_index), cp.kept[:, 0],
+                                           kept_rows(dst_desc, cp.dst_index), cp.kept[:, 1], float(th))
+    err, correct = match_accuracy_batch(cp.src, cp.dst_to_src, cp.kept, match_idx, m, ths)
+    num_matches = correct[:, k_star]
+    avg = _ratio(correct[:, 0], m)
+    for k in range(1, len(ths)):                                 # (in this order: the summation is part of the definition)
+        avg = avg + _ratio(correct[:, k], m)
+    return MatchingEvaluation(*r, cp.valid, cp.kept, m, num_matches, correct, _ratio(num_matches, m),
+                              _ratio(num_matches, r.possible_matches), avg / float(len(ths)), match_idx, err)
 
 
 def evaluate_val_pairs(prob_src, prob_dst, h_dst_2_src, nms_size=15, num_points=25, leg="greedy", conf_thresh=0.015,
@@ -232,4 +399,142 @@ def evaluate_resize_hsequences(dataloader, model, device, resize_shape=(240, 320
     for r in (np.concatenate(out_rows) if out_rows else np.zeros((0, 6))):
         for j, k in enumerate(RESIZE_RESULT_KEYS):
             results[k].append(float(r[j]) if j < 2 else int(r[j]))
+    return results
+
+
+# ---- the matching evaluation over a dataset ------------------------------------------------------------------------
+_MATCH_COLUMNS = ('rep_single_scale', 'rep_multi_scale', 'error_overlap_single_scale', 'error_overlap_multi_scale',
+                  'num_points_single_scale', 'num_points_multi_scale', 'candidates_single_scale', 'candidates_multi_scale',
+                  'valid', 'mma', 'mma_corr', 'avg_mma', 'num_matches', 'num_mutual_corresp')
+
+
+def _gray_u8(sd_image_u8, image_rgb_norm, device):
+    """The uint8 gray image the patches are cut from, on the device: the loader's uint8 image (gray, or BGR as cv2 reads it)
+    when it has one, else the normalised RGB image times 255, rounded; colour goes through PIL's ``convert('L')`` arithmetic
+    (``ops.rgb_to_gray_u8``), what the demo's ``load_im`` feeds the patch extractor."""
+    from .. import ops
+    if sd_image_u8 is not None:
+        a = _as_rgb_u8(sd_image_u8)
+        if a.dtype != np.uint8 or a.shape[:2] != image_rgb_norm.shape[:2]:
+            raise ValueError(f"the uint8 image must have the shape of the normalised one: {a.shape} / {image_rgb_norm.shape}")
+    else:
+        a = np.clip(np.rint(np.asarray(image_rgb_norm, dtype=np.float64) * 255.0), 0, 255).astype(np.uint8)
+        if a.ndim == 3 and a.shape[2] == 1:
+            a = a[:, :, 0]
+    t = torch.from_numpy(np.ascontiguousarray(a)).to(device)
+    return t if t.dim() == 2 else ops.rgb_to_gray_u8(t)
+
+
+def _describe_images(grays, rows, count, descriptor, s_mult, batch_size):
+    """One descriptor per detected row: gray images (device, [H,W] uint8 each), rows [I,K,4] / count [I] of
+    ``_detect_images`` -> [I,K,128] float32 (zero rows past an image's count).  Images of one shape go through
+    ``ops.extract_patches_batch`` and ``HardNet.forward_slots`` together, ``batch_size`` at a time."""
+    from collections import OrderedDict
+    from .. import ops
+    desc = torch.zeros(rows.shape[:2] + (128,), dtype=torch.float32, device=rows.device)
+    groups = OrderedDict()
+    for i, g in enumerate(grays):
+        groups.setdefault(tuple(g.shape), []).append(i)
+    for ids in groups.values():
+        for b0 in range(0, len(ids), batch_size):
+            sel = ids[b0:b0 + batch_size]
+            at = torch.tensor(sel, dtype=torch.long, device=rows.device)
+            cnt = count[at]
+            patches = ops.extract_patches_batch(torch.stack([grays[i] for i in sel]), rows[at][:, :, :2].float().contiguous(),
+                                                cnt, float(s_mult))
+            desc[at] = descriptor.forward_slots(patches, cnt)
+    return desc
+
+
+def _matching_chunk(seqs, detector, descriptor, device, nms_size, num_points, border_size, s_mult, th, ths, pixel_threshold,
+                    multi_scale, batch_size):
+    """Detect and describe the images of some sequences, each once, and evaluate their pairs -> [P, 16] float64 on the host
+    (one read): the _MATCH_COLUMNS, then the two kept counts; pairs in (sequence, destination) order."""
+    from ..utils import train_utils
+    images, src_ids, dst_ids, hs, shapes = train_utils._chunk_pairs(seqs)
+    if not src_ids:
+        return np.zeros((0, len(_MATCH_COLUMNS) + 2))
+    u8 = []
+    for sd in seqs:
+        u8.append(sd.get('im_src_BGR'))
+        dst_u8 = sd.get('images_dst_BGR')
+        u8.extend(dst_u8 if dst_u8 is not None else [None] * len(sd['images_dst_RGB_norm']))
+    rows, count = train_utils._detect_images(images, detector, device, nms_size, num_points, border_size, multi_scale,
+                                             batch_size)
+    desc = _describe_images([_gray_u8(a, im, device) for a, im in zip(u8, images)], rows, count, descriptor, s_mult, batch_size)
+    s_at = torch.tensor(src_ids, dtype=torch.long, device=device)
+    d_at = torch.tensor(dst_ids, dtype=torch.long, device=device)
+    args = (rows[s_at], count[s_at], desc[s_at], rows[d_at], count[d_at], desc[d_at], torch.from_numpy(np.stack(hs)).to(device),
+            torch.tensor(shapes, dtype=torch.int32, device=device))
+
+    def run(**kw):
+        r = evaluate_matching_pairs(*args, th=th, thresholds=ths, pixel_threshold=pixel_threshold, **kw)
+        cols = [getattr(r, k).double() for k in _MATCH_COLUMNS] + [r.kept[:, 0].double(), r.kept[:, 1].double()]
+        return torch.stack(cols, dim=1).cpu().numpy()
+
+    out = run()                         # the one device-to-host read of the chunk
+    if (out[:, 4:6] < 0).any():         # some pair's candidates did not fit the default buffer: size it from the totals
+        out = run(max_edges=int(max(out[:, 6].sum(), out[:, 7].sum(), 1)))
+    return out
+
+
+@torch.no_grad()
+def evaluate_matching_hsequences(dataloader, detector, descriptor, device, num_points=1000, nms_size=15, border_size=15,
+                                 s_mult=60, th=0.99, pixel_threshold=5, multi_scale=False, chunk_sequences=16, batch_size=16):
+    """The matching evaluation of HSequences (or GoPro): repeatability and matching score of every (source, destination) pair.
+    The reference ships the configuration (``--top_k_points``, ``--overlap``, ``--pixel_threshold``) and the result record
+    (``create_metrics_results``) but not the loop that fills it; the definitions are DESIGN.md 7h's and
+    :func:`evaluate_matching_pairs`'s.
+
+    * ``dataloader`` has ``.sequences`` and ``get_sequence_data(i)`` as ``check_val_hsequences_repeatability`` needs them:
+      ``im_src_RGB_norm``, ``images_dst_RGB_norm`` (what the detector sees) and ``h_dst_2_src``; ``sequence_name`` is used
+      when present (else ``sequences[i]``).
+    * PATCHES are cut from a uint8 gray image: the keys ``im_src_BGR`` / ``images_dst_BGR`` are read when present (gray
+      ``[H,W]`` / ``[H,W,1]``, or 3-channel BGR as cv2 reads it; the same size as the normalised image), as the reference's
+      ``HSequences.get_sequence_data`` returns them; otherwise ``im_src_RGB_norm * 255`` rounded.  Colour becomes gray with
+      PIL's ``convert('L')`` arithmetic on the device, as in the demo.  Every point's patch has scale ``s_mult`` (the demo's
+      60), multi-scale points too.
+    * ``detector`` is the model, ``descriptor`` a ``HardNet``.  Every image is detected AND described once -- the source is
+      not described again for every destination --, images of one shape ``batch_size`` at a time; ``multi_scale`` as in
+      ``check_val_hsequences_repeatability``.
+    * The pairs of ``chunk_sequences`` sequences are evaluated in one stream-ordered :func:`evaluate_matching_pairs` call with
+      thresholds 1..10 and ONE device-to-host read per chunk.  On that read the split-f16 guard is applied as
+      ``check_val_hsequences_repeatability`` does: a chunk whose forward was flagged (or during which the checkpoint was
+      switched to the fp32 kernels) is repeated.
+
+    Returns ``create_metrics_results(sequence names, num_points, 0.6, pixel_threshold)`` (0.6 = 1 - the ``overlap_err`` of
+    ``compute_repeatability``) with one entry per list and pair, in (sequence, destination) order; ``num_features`` holds
+    the kept counts (source, destination).  A pair with an empty kept list is skipped, as the repeatability loop skips it
+    (``continue``): it has no entry, so that a mean over a list is the mean the loop would have taken."""
+    from .test_utils import create_metrics_results
+    device = torch.device(device)
+    guard = getattr(detector, "fp16_guard_check", None)
+    chunk, batch_size = max(1, int(chunk_sequences)), max(1, int(batch_size))
+    ths = [float(t) for t in range(1, 11)]
+    if float(pixel_threshold) not in ths:
+        raise BalfHipError(f"pixel_threshold {pixel_threshold} is not one of the thresholds {ths}")
+    names, out_rows = [], []
+    n_seq = len(dataloader.sequences)
+    for c0 in range(0, n_seq, chunk):
+        seqs = [dataloader.get_sequence_data(i) for i in range(c0, min(n_seq, c0 + chunk))]
+        names.extend(s.get('sequence_name', dataloader.sequences[c0 + k]) for k, s in enumerate(seqs))
+        chunk_args = (seqs, detector, descriptor, device, nms_size, int(num_points), border_size, s_mult, th, ths,
+                      pixel_threshold, multi_scale, batch_size)
+        on_fp32 = getattr(detector, "effective_precision", None) == "fp32"
+        out = _matching_chunk(*chunk_args)
+        flagged = guard is not None and guard(synchronize=False)     # (the read above has passed every forward of the chunk)
+        if flagged or (not on_fp32 and getattr(detector, "effective_precision", None) == "fp32"):
+            out = _matching_chunk(*chunk_args)
+        out_rows.append(out)
+    results = create_metrics_results(names, num_points, 0.6, pixel_threshold)
+    floats = ('rep_single_scale', 'rep_multi_scale', 'error_overlap_single_scale', 'error_overlap_multi_scale', 'mma', 'mma_corr',
+              'avg_mma')
+    col = {k: j for j, k in enumerate(_MATCH_COLUMNS)}
+    for r in (np.concatenate(out_rows) if out_rows else np.zeros((0, len(_MATCH_COLUMNS) + 2))):
+        if r[col['valid']] == 0:
+            continue
+        for k in _MATCH_COLUMNS:
+            if k in results:
+                results[k].append(float(r[col[k]]) if k in floats else int(r[col[k]]))
+        results['num_features'].append((int(r[-2]), int(r[-1])))
     return results

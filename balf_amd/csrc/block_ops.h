@@ -1,5 +1,6 @@
 // Workgroup-level building blocks of the point kernels (nms_topk.hip, nms_fast.hip, multiscale.hip, repeat.hip,
-// repeat_batch.hip, val_points.hip, resize_repeat.hip): ONE definition each of the select, scan, compaction, sort and
+// repeat_batch.hip, val_points.hip, resize_repeat.hip, match_eval.hip, and the pair filter of common_points.h that
+// repeat_batch.hip and match_eval.hip share): ONE definition each of the select, scan, compaction, sort and
 // reduction these kernels are assembled from, so that a barrier or a tie rule is fixed in one place.
 // Every device function below that takes LDS is called by ALL threads of the workgroup (THREADS of them, a multiple of 64, x
 // only), with the same arguments where a comment says "uniform".  The LDS is the caller's: nothing here declares __shared__,

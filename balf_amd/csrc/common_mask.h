@@ -1,6 +1,6 @@
 // create_common_region_masks (balf/benchmark_test/geometry_tools.py:7-26), one pixel at a time: shared by the dense masks
-// (balf_common_region_masks, repeat.hip) and the batched point filter (balf_common_points_batch, repeat_batch.hip) so that
-// the two cannot drift.  The reference warps an all-ones image whose 15-pixel frame is zeroed with cv2.warpPerspective
+// (balf_common_region_masks, repeat.hip) and the batched point filters (balf_common_points_batch, repeat_batch.hip;
+// balf_common_points_index_batch, match_eval.hip) so that they cannot drift.  The reference warps an all-ones image whose 15-pixel frame is zeroed with cv2.warpPerspective
 // (default flags: bilinear, constant-zero border), thresholds at 0.75 and zeroes the frame of the result.  Restated here from
 // OpenCV's algorithm: the output pixel (x, y) samples the input at M^-1 (x, y, 1), the source coordinates are rounded to
 // 1/32 pixel (INTER_TAB_SIZE = 32, round half to even), the four bilinear weights are the exact products of those 5-bit
@@ -56,6 +56,18 @@ __device__ __forceinline__ double common_mask_pixel(const double *m, int y, int 
         v = s >= 0.75 ? 1.0 : 0.0;
     }
     return v;
+}
+
+// check_common_points (repeatability_tools.py:8-13) of one point against the mask of h_out x w_out: mask[round(y) - 1,
+// round(x) - 1] with NumPy's indexing (round half to even; -k wraps to row h_out - k).  An index NumPy would reject is
+// dropped here (the reference raises IndexError).  ONE definition for every batched point filter (common_points.h).
+__device__ __forceinline__ bool point_in_mask(const double *m, double x, double y, int h_out, int w_out, int h_in, int w_in) {
+    const double ry = rint(y) - 1.0, rx = rint(x) - 1.0;
+    if (!(ry >= -(double)h_out && ry < (double)h_out && rx >= -(double)w_out && rx < (double)w_out)) return false;
+    int iy = (int)ry, ix = (int)rx;
+    if (iy < 0) iy += h_out;
+    if (ix < 0) ix += w_out;
+    return common_mask_pixel(m, iy, ix, h_out, w_out, h_in, w_in, kCommonBorder) != 0.0;
 }
 
 // closed-form 3x3 inverse (adjugate / determinant), the form OpenCV's cv::invert takes for n <= 3

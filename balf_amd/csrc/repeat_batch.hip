@@ -5,6 +5,7 @@
 //   balf_common_points_batch   check_common_points against both common-region masks (evaluated at the point only, through
 //                              common_mask.h) + apply_homography_to_points of the kept destination rows (homography.h)
 //     common_points_kernel     one workgroup per pair: both inverse maps, then an ordered compaction of each side
+//                              (common_points.h, shared with balf_common_points_index_batch of match_eval.hip)
 //   balf_repeatability_batch   compute_repeatability per pair, bit-identical to balf_repeatability (repeat_core.h)
 //     rpb_count_kernel         one wave per (source row, pair): candidate counts and the "possible match" flag
 //     rpb_row_scan_kernel      one workgroup per pair: exclusive scan of its row counts, the pair's totals
@@ -16,8 +17,7 @@
 // The ordered compaction, the scans and the count clamp are the shared ones of block_ops.h.
 #include "block_ops.h"
 #include "common.h"
-#include "common_mask.h"
-#include "homography.h"
+#include "common_points.h"
 #include "repeat_core.h"
 
 namespace balf {
@@ -25,63 +25,13 @@ namespace {
 
 constexpr int kRowsPerBlock = 4;            // count / fill: one wave per source row
 
-// check_common_points (repeatability_tools.py:8-13) of one point against the mask of h_out x w_out: mask[round(y) - 1,
-// round(x) - 1] with NumPy's indexing (round half to even; -k wraps to row h_out - k).  An index NumPy would reject is
-// dropped here (the reference raises IndexError).
-__device__ __forceinline__ bool point_in_mask(const double *m, double x, double y, int h_out, int w_out, int h_in, int w_in) {
-    const double ry = rint(y) - 1.0, rx = rint(x) - 1.0;
-    if (!(ry >= -(double)h_out && ry < (double)h_out && rx >= -(double)w_out && rx < (double)w_out)) return false;
-    int iy = (int)ry, ix = (int)rx;
-    if (iy < 0) iy += h_out;
-    if (ix < 0) ix += w_out;
-    return common_mask_pixel(m, iy, ix, h_out, w_out, h_in, w_in, kCommonBorder) != 0.0;
-}
-
-// One workgroup of 256 per pair.  Side 0 keeps the source rows inside mask_src (copied), side 1 the destination rows inside
-// mask_dst (warped by h_dst_2_src, score carried).  Kept rows keep their order; rows past the kept count are zeroed.
+// One workgroup of 256 per pair: common_points_pair (common_points.h) without the row indices.
 __global__ __launch_bounds__(256) void common_points_kernel(const double *src, const int *ns, int ns_max, const double *dst,
                                                             const int *nd, int nd_max, const double *h_all, const int *shapes,
                                                             double *src_out, double *dst_out, int *kept, int *valid) {
     __shared__ int wcnt[4];
-    const int p = blockIdx.x, tid = threadIdx.x;
-    const double *h = h_all + 9 * (long)p;
-    double m_src[9], m_dst[9];
-    const bool inv_ok = common_mask_maps(h, m_src, m_dst);       // (every thread: two closed-form inverses)
-    const int hs = shapes[4 * p], ws = shapes[4 * p + 1], hd = shapes[4 * p + 2], wd = shapes[4 * p + 3];
-    const bool shape_ok = hs > 0 && ws > 0 && hd > 0 && wd > 0;
-    int kept_side[2];
-    for (int side = 0; side < 2; ++side) {
-        const int n_max = side ? nd_max : ns_max;
-        const int n = inv_ok && shape_ok ? clamp_count(side ? nd : ns, p, n_max) : 0;
-        const double *in = (side ? dst : src) + (long)p * n_max * 4;
-        double *out = (side ? dst_out : src_out) + (long)p * n_max * 4;
-        const double *m = side ? m_dst : m_src;
-        const int h_out = side ? hd : hs, w_out = side ? wd : ws, h_in = side ? hs : hd, w_in = side ? ws : wd;
-        int base = 0;
-        for (int r0 = 0; r0 < n; r0 += 256) {
-            const int r = r0 + tid;
-            double x = 0.0, y = 0.0, rad = 0.0, sc = 0.0;
-            bool keep = false;
-            if (r < n) {
-                x = in[4 * r]; y = in[4 * r + 1]; rad = in[4 * r + 2]; sc = in[4 * r + 3];
-                keep = point_in_mask(m, x, y, h_out, w_out, h_in, w_in);
-            }
-            const int q = compact_slot<256>(keep, wcnt, base);
-            if (keep) {
-                double *o = out + 4 * (long)q;
-                if (side) homography_point(h, x, y, rad, &o[0], &o[1], &o[2]);
-                else { o[0] = x; o[1] = y; o[2] = rad; }
-                o[3] = sc;
-            }
-        }
-        for (long k = 4 * (long)base + tid; k < 4 * (long)n_max; k += 256) out[k] = 0.0;
-        kept_side[side] = base;
-    }
-    if (tid == 0) {
-        kept[2 * p] = kept_side[0];
-        kept[2 * p + 1] = kept_side[1];
-        valid[p] = kept_side[0] > 0 && kept_side[1] > 0;         // the reference `continue`s otherwise (train_utils.py:355-362)
-    }
+    common_points_pair<false>(src, ns, ns_max, dst, nd, nd_max, h_all, shapes, src_out, dst_out, kept, valid, nullptr, nullptr,
+                              wcnt);
 }
 
 struct BatchIn {
@@ -264,12 +214,6 @@ RpbWs rpb_layout(char *base, int P, int ns_max, int max_edges) {
     w.out_val_s = c.take<unsigned>(e * 4); w.out_val_m = c.take<unsigned>(e * 4);
     w.total = c.used;
     return w;
-}
-
-int check_sizes(int P, int ns_max, int nd_max) {
-    if (P <= 0 || P > kMaxPairs || ns_max < 0 || nd_max < 0 || ns_max > kMaxPoints || nd_max > kMaxPoints) return BALF_ERR_ARG;
-    if ((long long)ns_max * nd_max > 0x7fffffffLL) return BALF_ERR_SHAPE;
-    return BALF_OK;
 }
 
 }  // namespace

@@ -68,9 +68,10 @@ def _detect_images(images, model, device, nms_size, num_points, border_size, mul
     return rows, count
 
 
-def _evaluate_chunk(seqs, model, device, nms_size, num_points, border_size, multi_scale, batch_size):
-    """Detect the images of some sequences and evaluate their pairs -> [P, 10] float64 on the host, one row per pair in
-    (sequence, destination) order: rep_s, rep_m, err_s, err_m, possible, valid, found_s, found_m, cand_s, cand_m."""
+def _chunk_pairs(seqs):
+    """The images of some sequences, each once, and their pairs in (sequence, destination) order -> (images, src_ids, dst_ids,
+    hs, shapes): pair k is images[src_ids[k]] / images[dst_ids[k]] with h_dst_2_src hs[k] and shapes[k] = (h_src, w_src, h_dst,
+    w_dst)."""
     images, src_ids, dst_ids, hs, shapes = [], [], [], [], []
     for sd in seqs:
         src = sd['im_src_RGB_norm']
@@ -82,6 +83,13 @@ def _evaluate_chunk(seqs, model, device, nms_size, num_points, border_size, mult
             images.append(im)
             hs.append(np.asarray(sd['h_dst_2_src'][k], dtype=np.float64).reshape(3, 3))
             shapes.append((src.shape[0], src.shape[1], im.shape[0], im.shape[1]))
+    return images, src_ids, dst_ids, hs, shapes
+
+
+def _evaluate_chunk(seqs, model, device, nms_size, num_points, border_size, multi_scale, batch_size):
+    """Detect the images of some sequences and evaluate their pairs -> [P, 10] float64 on the host, one row per pair in
+    (sequence, destination) order: rep_s, rep_m, err_s, err_m, possible, valid, found_s, found_m, cand_s, cand_m."""
+    images, src_ids, dst_ids, hs, shapes = _chunk_pairs(seqs)
     if not src_ids:
         return np.zeros((0, 10))
     rows, count = _detect_images(images, model, device, nms_size, num_points, border_size, multi_scale, batch_size)

@@ -360,6 +360,29 @@ int balf_repeatability_batch(const double *src_dev, const int32_t *ns_dev, int n
                              double eps, double dist_match_thresh, double radius_size, int max_edges, double *rep_dev,
                              int32_t *counts_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
 
+/* ---- matching score of the HSequences evaluation (the record fields mma, mma_corr, num_matches, num_mutual_corresp, avg_mma
+ * of balf/benchmark_test/test_utils.py:create_results; the reference ships no code that fills them: DESIGN.md 7h defines them) --
+ * balf_common_points_index_batch: balf_common_points_batch -- same arguments, same semantics, the same bits in the four
+ * shared outputs -- plus src_index_dev [P,ns_max] / dst_index_dev [P,nd_max] int32: the original row of each kept row, in kept
+ * order (strictly increasing), -1 past the kept count.  A per-image descriptor table is gathered through them.
+ *
+ * balf_match_accuracy_batch: the matches of P pairs verified against the homography.  src_dev [P,ns_max,4] / dst_dev
+ * [P,nd_max,4] float64 are the kept lists (source rows; destination rows warped into the source image), kept_dev [P,2] their
+ * lengths, match_idx_dev [P,cap,2] int32 the matches (row in src, row in dst) of which the first match_count_dev[p] are used
+ * (counts clamped to [0, cap] / [0, n_max]); this is what balf_match_smnn_batch writes.  thresholds_host: T pixel thresholds
+ * on the HOST, 1 <= T <= 16, >= 0 and strictly ascending; they are passed to the kernel as arguments (no upload).  Outputs:
+ * err_dev [P,cap] float64 = sqrt(dx*dx + dy*dy) between the two matched rows, each operation rounded once (no FMA); NaN for a
+ * slot past the count and for a match with an index outside [0, kept).  correct_dev [P,T] int32 = the matches with
+ * err <= thresholds[k] (a NaN counts for none).  Every slot of both outputs is written.  1 <= cap <= 65536, the other limits
+ * as above.  No workspace. */
+int balf_common_points_index_batch(const double *src_dev, const int32_t *ns_dev, int ns_max, const double *dst_dev,
+                                   const int32_t *nd_dev, int nd_max, int P, const double *h_dst_2_src_dev,
+                                   const int32_t *shapes_dev, double *src_out_dev, double *dst_out_dev, int32_t *kept_dev,
+                                   int32_t *valid_dev, int32_t *src_index_dev, int32_t *dst_index_dev, void *stream);
+int balf_match_accuracy_batch(const double *src_dev, int ns_max, const double *dst_dev, int nd_max, const int32_t *kept_dev,
+                              const int32_t *match_idx_dev, const int32_t *match_count_dev, int cap, int P,
+                              const double *thresholds_host, int T, double *err_dev, int32_t *correct_dev, void *stream);
+
 /* ---- batched synthetic-pair validation (check_val_repeatability, balf/utils/train_utils.py:205-306) -----------------------
  * balf_val_points: the point selection of that loop for P pairs x 2 sides, stream-ordered, nothing read back.  Per side
  *   nms    = the NMS map of the side's score map, no border frame:
