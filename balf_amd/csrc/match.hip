@@ -25,6 +25,10 @@ struct Best {
     int i1;
 };
 
+// d^2 clamped at 0; a NaN (a non-finite descriptor row) stays NaN -- fmaxf would turn it into 0, the best distance there is
+__device__ __forceinline__ float clamp_d2(float d) { return d < 0.0f ? 0.0f : d; }
+
+// a NaN distance compares false everywhere below: it is never the nearest nor the second-nearest neighbour
 __device__ __forceinline__ void best_insert(Best &b, float d, int idx) {
     if (d < b.d1 || (d == b.d1 && idx < b.i1)) {
         b.d2 = b.d1; b.d1 = d; b.i1 = idx;
@@ -91,7 +95,7 @@ __global__ __launch_bounds__(64) void match_nn_kernel(const float *a, int na, co
             for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[c][j], bv[c][j], acc, 0, 0, 0);
         if (c0 + n < nb) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) best_insert(best[r], fmaxf(arow[r] + bn - 2.0f * acc[r], 0.0f), c0 + n);
+            for (int r = 0; r < 4; ++r) best_insert(best[r], clamp_d2(arow[r] + bn - 2.0f * acc[r]), c0 + n);
         }
     }
 #pragma unroll

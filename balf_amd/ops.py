@@ -196,11 +196,11 @@ def extract_patches_batch(gray_u8: torch.Tensor, xy: torch.Tensor, count, scale:
 def match_smnn(desc1: torch.Tensor, desc2: torch.Tensor, th: float = 0.8) -> Tuple[torch.Tensor, torch.Tensor]:
     """``kornia.feature.match_smnn(desc1, desc2, th)`` (/root/reference/demo/demo_match.py:104-110): returns
     (dists [M,1] fp32, idxs [M,2] int64), mutual ratio-test matches sorted by the index in ``desc1``."""
+    desc1, desc2 = desc1.float().contiguous(), desc2.float().contiguous()      # strided views (desc[:n]) are copied
     require_gpu_tensor(desc1, "desc1")
     require_gpu_tensor(desc2, "desc2")
     if desc1.dim() != 2 or desc2.dim() != 2 or desc1.shape[1] != 128 or desc2.shape[1] != 128:
         raise BalfHipError("descriptors must be [N,128]")
-    desc1, desc2 = desc1.float().contiguous(), desc2.float().contiguous()
     n1, n2 = desc1.shape[0], desc2.shape[0]
     dev = desc1.device
     if n1 == 0 or n2 == 0:
@@ -222,11 +222,12 @@ def match_smnn_batch(desc1: torch.Tensor, n1: torch.Tensor, desc2: torch.Tensor,
     """``pairs`` independent :func:`match_smnn` problems in three launches: desc1 [P,K1,128] / desc2 [P,K2,128] with
     n1 / n2 [P] valid rows each -> (dist [P,cap] fp32, idx [P,cap,2] int32 (-1 padded), count [P] int32), cap =
     min(K1, K2); nothing is read back to the host (balf_match_smnn_batch)."""
+    # strided views (full[:, :k], full[::2]) are copied: the library strides pairs by K * 128 floats
+    desc1, desc2 = desc1.float().contiguous(), desc2.float().contiguous()
     require_gpu_tensor(desc1, "desc1")
     require_gpu_tensor(desc2, "desc2")
     if desc1.dim() != 3 or desc2.dim() != 3 or desc1.shape[2] != 128 or desc2.shape[2] != 128 or desc1.shape[0] != desc2.shape[0]:
         raise BalfHipError("descriptors must be [P,K,128] with the same number of pairs")
-    desc1, desc2 = desc1.float(), desc2.float()
     p, k1, k2 = desc1.shape[0], desc1.shape[1], desc2.shape[1]
     dev = desc1.device
     cap = min(k1, k2)

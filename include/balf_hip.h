@@ -275,6 +275,12 @@ int balf_hardnet_forward_ex(const void *packed_dev, const float *patches_dev, in
  * balf_match_smnn replaces kornia.feature.match_smnn(desc1, desc2, th) (demo_match.py:104-110): descriptors
  * [n,128] fp32; outputs idx_dev [min(n1,n2),2] (index in desc1, index in desc2; -1 padded, sorted by the first),
  * dist_dev [min(n1,n2)] (max of the two nearest/second-nearest distance ratios), count_dev [1].
+ * Squared distances are formed in fp32 as |a|^2 + |b|^2 - 2 a.b (fp32 MFMA operands), within
+ * 16 * 2^-24 * (|a| + |b|)^2 of the exact value; among exactly equal distances the lowest index is the
+ * nearest neighbour.  Non-finite rows: a distance that comes out NaN (a row with a NaN, or with an Inf whose products
+ * cancel) is never a nearest nor a second-nearest neighbour, as in torch.topk, where NaN sorts last -- such a row
+ * matches nothing and the matches among the other rows are those of the call without it.  An all-zero row is an
+ * ordinary descriptor.
  * kornia is a third-party dependency that is absent offline: both follow its published algorithm and are checked
  * against this repo's restatement only (parity unpinned). */
 size_t balf_extract_patches_workspace_bytes(int H, int W, float scale);
