@@ -282,7 +282,9 @@ extern "C" int balf_pyramid_level(const void *src_dev, int src_kind, int channel
         fh = (int)std::ceil((ty - 1) * a.sc_y) + 3 + 2 * R;
         if ((size_t)2 * fh * fw * sizeof(float) <= PYR_LDS_MAX) break;
     }
-    if (ty < 1) return BALF_ERR_ARG;           // an extreme reduction factor along x (in/out > ~120)
+    // even a one-row tile does not fit: fw > 65536 / (8 (3 + 2R)), i.e. a reduction factor along x of more than
+    // ~43.28 without blur (R = 0: ceil(63 in/out) > 2727) down to ~6.54 at R = 8 (ceil(63 in/out) > 412)
+    if (ty < 1) return BALF_ERR_ARG;
     a.ty = ty; a.fh = fh; a.fw = fw;
     a.dst = dst_dev;
     const size_t smem = (size_t)2 * fh * fw * sizeof(float);

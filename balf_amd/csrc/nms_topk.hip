@@ -424,12 +424,14 @@ __global__ __launch_bounds__(SEL_THREADS) void topk_select_kernel(const int2 *su
     int32_t *idx_o = idx_out + (long)b * K_row;
     float *sc_o = score_out + (long)b * K_row;
     if (taken) {
-        // budgeted form (balf_nms_topk_budget): K = min(cum_budget - taken[b], H*W), decided here per image; taken[b] grows
-        // by this image's count at the end.  Read by one thread and broadcast: thread 0 stores the new value before the
-        // slower waves would otherwise have read the old one.
+        // budgeted form (balf_nms_topk_budget): K = min(max(cum_budget - taken[b], 0), K_row, H*W), decided here per image;
+        // taken[b] grows by this image's count at the end.  taken[b] is a count another kernel wrote: a value below zero
+        // must not make K longer than the output row (and the LDS sized for it).  Read by one thread and broadcast: thread 0
+        // stores the new value before the slower waves would otherwise have read the old one.
         if (threadIdx.x == 0) {
             long kb = (long)cum_budget - taken[b];
             kb = kb < cap ? kb : cap;
+            kb = kb < K_row ? kb : K_row;
             *s_cnt = kb > 0 ? (int)kb : 0;
         }
         __syncthreads();

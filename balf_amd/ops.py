@@ -295,7 +295,7 @@ def build_pyramid(images: torch.Tensor, shapes, upsampled_levels: int, sigma: fl
 def nms_topk_budget(prob: torch.Tensor, crop_y: int, crop_x: int, h: int, w: int, border: int, nms_size: int,
                     cum_budget: int, k_max: int, taken: torch.Tensor, idx: torch.Tensor = None, score: torch.Tensor = None,
                     count: torch.Tensor = None):
-    """:func:`nms_topk` with each image's K decided on the device: K_b = min(cum_budget - taken[b], h*w), then
+    """:func:`nms_topk` with each image's K decided on the device: K_b = min(max(cum_budget - taken[b], 0), k_max, h*w), then
     ``taken[b] += count[b]`` (balf_nms_topk_budget).  ``taken`` [B] int32 on the GPU, zero before the first level.
     Returns (idx [B,k_max], score [B,k_max], count [B]); pass ``idx`` / ``score`` / ``count`` to write into given rows."""
     require_gpu_tensor(prob, "prob")

@@ -189,7 +189,11 @@ int balf_nms_threshold(const float *prob_dev, int B, int Hp, int Wp, int crop_y,
  * resampling to H_out x W_out with half-pixel centres: src = (o + 0.5) * in/out - 0.5 clamped below at 0, the upper
  * neighbour clamped to in - 1 (F.interpolate(mode='bilinear', align_corners=False)).  H_out = H_in, W_out = W_in without
  * blur is a copy: the level is then bit-identical to what balf_forward_u8 / pad_batch prepare.  fp32 arithmetic, the
- * sampling positions in float64. */
+ * sampling positions in float64: for sources in [0, 1] every pixel is within (4 R + 12) * 2^-24 of the float64 result.
+ * Reduction limit: a 64-pixel output row's source footprint and blur halo are staged in LDS, two planes of
+ * (3 + 2R) x (ceil(63 W_in / W_out) + 3 + 2R) floats in 64 KB at the least.  BALF_ERR_ARG beyond it: W_in / W_out above
+ * ~43.28 without blur (ceil(63 W_in / W_out) <= 2727), ~18.46 at R = 2 (<= 1163), ~6.54 at R = 8 (<= 412); H_in / H_out is
+ * not limited (the tile height shrinks from 8 rows to 1).  sigma >= 64, NaN or R > BALF_PYR_MAX_RADIUS: BALF_ERR_ARG. */
 #define BALF_PYR_SRC_U8 0
 #define BALF_PYR_SRC_F32 1
 #define BALF_PYR_SRC_LEVEL 2
@@ -198,8 +202,9 @@ int balf_nms_threshold(const float *prob_dev, int B, int Hp, int Wp, int crop_y,
 int balf_pyramid_level(const void *src_dev, int src_kind, int channels, int B, int H_in, int W_in, double sigma, int H_out,
                        int W_out, float *dst_dev, void *stream);
 
-/* balf_nms_topk with the K of each image decided ON THE DEVICE from a point budget: K_b = min(cum_budget - taken_dev[b], H*W)
- * (0 if negative), then taken_dev[b] += count_b.  Called once per level with cum_budget = the budget of the levels so far, a
+/* balf_nms_topk with the K of each image decided ON THE DEVICE from a point budget:
+ * K_b = min(max(cum_budget - taken_dev[b], 0), K_max, H*W) (never longer than a row, whatever taken_dev holds), then
+ * taken_dev[b] += count_b.  Called once per level with cum_budget = the budget of the levels so far, a
  * level that finds fewer points than its share passes the rest down -- nothing is read back.  taken_dev [B] int32, zeroed by
  * the caller before the first level.  Rows are K_max long (idx_dev / score_dev [B,K_max], -1 / 0 past count_dev[b]);
  * 0 <= cum_budget <= K_max <= BALF_MAX_TOPK; K_max may exceed H*W.  Selection as balf_nms_topk, its <= 0 fallback included
