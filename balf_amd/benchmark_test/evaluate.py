@@ -22,7 +22,11 @@ import numpy as np
 import torch
 
 from .._lib import BalfHipError, check, current_stream_ptr, lib, require_gpu_tensor
+from . import _chunked
+from ._chunked import detection_rows  # noqa: F401
+from .metrics_results import create_metrics_results
 from .repeatability_tools import RepeatabilityBatch, _counts, compute_repeatability_batch
+from .test_utils import RESIZE_RESULT_KEYS, create_resize_metrics_results
 
 
 class CommonPoints(NamedTuple):
@@ -168,6 +172,14 @@ def _thresholds(thresholds):
     return ths, (C.c_double * len(ths))(*ths)
 
 
+def _threshold_index(thresholds, pixel_threshold):
+    """-> (the thresholds as Python floats, the position of ``pixel_threshold`` among them)."""
+    ths, _ = _thresholds(thresholds)
+    if float(pixel_threshold) not in ths:
+        raise BalfHipError(f"pixel_threshold {pixel_threshold} is not one of the thresholds {ths}")
+    return ths, ths.index(float(pixel_threshold))
+
+
 def match_accuracy_batch(src, dst, kept, match_idx, match_count, thresholds):
     """The matches of P pairs verified against the homography (``balf_match_accuracy_batch``, include/balf_hip.h).  ``src``
     [P,Ns,4] / ``dst`` [P,Nd,4] float64: the kept source rows and the kept destination rows warped into the source image
@@ -232,10 +244,7 @@ def evaluate_matching_pairs(src_pts, src_count, src_desc, dst_pts, dst_count, ds
     A pair with ``valid == 0`` has M = 0; it is left out of every mean, as in the repeatability loop.  Returns device tensors,
     reads nothing back, and can be captured with ``torch.cuda.graph`` when every input is a device tensor."""
     from .. import ops
-    ths, _ = _thresholds(thresholds)
-    if float(pixel_threshold) not in ths:
-        raise BalfHipError(f"pixel_threshold {pixel_threshold} is not one of the thresholds {ths}")
-    k_star = ths.index(float(pixel_threshold))
+    ths, k_star = _threshold_index(thresholds, pixel_threshold)
     for d, pts, name in ((src_desc, src_pts, "src_desc"), (dst_desc, dst_pts, "dst_desc")):
         if not isinstance(d, torch.Tensor) or not isinstance(pts, torch.Tensor) or d.dim() != 3 or d.shape[2] != 128 or \
                 tuple(d.shape[:2]) != tuple(pts.shape[:2]):
@@ -294,18 +303,6 @@ def evaluate_resize_pairs(src_pts, src_count, dst_pts, dst_count, h, shapes, kee
                                               distance_thresh, h_inv=h_inv, order=order)
 
 
-def detection_rows(idx, score, count, w):
-    """``detect_batch_u8``'s (idx [B,K] flat ``y * w + x``, score [B,K], count [B]) -> rows [B,K,4] float64 (x, y, 1.0, score);
-    slots past an image's count are never read by the evaluation."""
-    i = idx.to(torch.int64).clamp_(min=0)
-    rows = torch.empty(idx.shape + (4,), dtype=torch.float64, device=idx.device)
-    rows[..., 0] = i % w
-    rows[..., 1] = torch.div(i, w, rounding_mode="floor")
-    rows[..., 2] = 1.0
-    rows[..., 3] = score
-    return rows
-
-
 def _as_rgb_u8(img):
     """A loader image (``*_BGR``: gray [H,W] / [H,W,1] or BGR [H,W,3] uint8) as the detector's input: gray as it is, colour
     with the channels reversed to RGB (the reference converts BGR to RGB before detection)."""
@@ -316,7 +313,7 @@ def _as_rgb_u8(img):
 
 
 def _resize_chunk(seqs, model, device, resize_shape, top_k, pixel_threshold, nms_size, border_size, batch_size):
-    """One chunk of sequences -> [P, 6] float64 on the host (one read), pairs in (sequence, destination) order."""
+    """One chunk of sequences -> the RESIZE_RESULT_KEYS per pair on the host (one read), in (sequence, destination) order."""
     from types import SimpleNamespace
     from ..datasets import dataset_utils
     from ..pipeline import detect_batch_u8
@@ -335,7 +332,7 @@ def _resize_chunk(seqs, model, device, resize_shape, top_k, pixel_threshold, nms
             hs.append(dataset_utils.adapt_homography_to_preprocessing(
                 {'homography': np.asarray(h), 'shape': np.array(src.shape[:2]), 'warped_shape': np.array(dst.shape[:2])}, args))
     if not hs:
-        return np.zeros((0, 6))
+        return _chunked.Table(RESIZE_RESULT_KEYS)
     if len({im.ndim for im in images}) != 1:                     # gray and colour in one chunk: gray replicated to 3 channels
         images = [im if im.ndim == 3 else np.repeat(im[:, :, None], 3, axis=2) for im in images]
     batch = dataset_utils.ratio_preserving_resize_batch(images, (th, tw), device)
@@ -345,12 +342,10 @@ def _resize_chunk(seqs, model, device, resize_shape, top_k, pixel_threshold, nms
         rows.append(detection_rows(idx, score, count, tw))
         counts.append(count)
     rows, counts = torch.cat(rows), torch.cat(counts)
-    i_s = torch.tensor(pair_src, dtype=torch.long, device=rows.device)
-    i_d = torch.tensor(pair_dst, dtype=torch.long, device=rows.device)
+    i_s, i_d = _chunked.pair_index(pair_src, pair_dst, rows.device)
     shapes = np.tile(np.asarray([th, tw, th, tw], dtype=np.int32), (len(hs), 1))
     r = evaluate_resize_pairs(rows[i_s], counts[i_s], rows[i_d], counts[i_d], np.stack(hs), shapes, top_k, pixel_threshold)
-    return torch.stack([r.repeatability, r.localization_err, r.common_src_num.double(), r.common_dst_num.double(),
-                        r.rep_src_num.double(), r.rep_dst_num.double()], dim=1).cpu().numpy()      # the one read of the chunk
+    return _chunked.host_table(r, RESIZE_RESULT_KEYS)
 
 
 @torch.no_grad()
@@ -373,39 +368,26 @@ def evaluate_resize_hsequences(dataloader, model, device, resize_shape=(240, 320
       ``nms_size``, ``border_size``; its rows are (row, col, prob) = (y, x, score);
     * per pair ``compute_resize_repeatability(rows_src, rows_dst, H_resized, resize_shape, resize_shape,
       keep_k_points=top_k_points, distance_thresh=pixel_threshold)``, all pairs of ``chunk_sequences`` sequences in one
-      stream-ordered call and ONE device-to-host read per chunk.  On that read the split-f16 guard is applied as
-      ``check_val_hsequences_repeatability`` does: a chunk whose forward was flagged (or during which the checkpoint was
-      switched to the fp32 kernels) is repeated.
+      stream-ordered call and ONE device-to-host read per chunk, on which the split-f16 guard is applied as
+      ``check_val_hsequences_repeatability`` does (``guard.run_guarded``: a flagged or switched chunk is repeated).
 
     Returns the ``create_resize_metrics_results`` record: the six lists with one entry per pair in (sequence, destination)
     order (float for the first two, int for the counts), ``sequences`` = the sequence names, ``top_k``, ``pixel_threshold``."""
-    from .test_utils import RESIZE_RESULT_KEYS, create_resize_metrics_results
     device = torch.device(device)
-    guard = getattr(model, "fp16_guard_check", None)
     chunk, batch_size = max(1, int(chunk_sequences)), max(1, int(batch_size))
-    names, out_rows = [], []
-    n_seq = len(dataloader.sequences)
-    for c0 in range(0, n_seq, chunk):
-        seqs = [dataloader.get_sequence_data(i) for i in range(c0, min(n_seq, c0 + chunk))]
-        names.extend(s['sequence_name'] for s in seqs)
-        chunk_args = (seqs, model, device, resize_shape, int(top_k_points), pixel_threshold, nms_size, border_size, batch_size)
-        on_fp32 = getattr(model, "effective_precision", None) == "fp32"
-        out = _resize_chunk(*chunk_args)
-        flagged = guard is not None and guard(synchronize=False)     # (the read above has passed every forward of the chunk)
-        if flagged or (not on_fp32 and getattr(model, "effective_precision", None) == "fp32"):
-            out = _resize_chunk(*chunk_args)
-        out_rows.append(out)
+    names, t = _chunked.run_sequence_chunks(dataloader, model, chunk, RESIZE_RESULT_KEYS, lambda seqs: _resize_chunk(
+        seqs, model, device, resize_shape, int(top_k_points), pixel_threshold, nms_size, border_size, batch_size))
     results = create_resize_metrics_results(names, top_k_points, pixel_threshold)
-    for r in (np.concatenate(out_rows) if out_rows else np.zeros((0, 6))):
-        for j, k in enumerate(RESIZE_RESULT_KEYS):
-            results[k].append(float(r[j]) if j < 2 else int(r[j]))
+    for k in RESIZE_RESULT_KEYS:
+        results[k].extend(map(float if k in ('repeatability', 'localization_err') else int, t[k]))
     return results
 
 
 # ---- the matching evaluation over a dataset (DESIGN.md 7h) ------------------------------------------------------------------------
-_MATCH_COLUMNS = ('rep_single_scale', 'rep_multi_scale', 'error_overlap_single_scale', 'error_overlap_multi_scale',
-                  'num_points_single_scale', 'num_points_multi_scale', 'candidates_single_scale', 'candidates_multi_scale',
-                  'valid', 'mma', 'mma_corr', 'avg_mma', 'num_matches', 'num_mutual_corresp')
+_MATCH_FIELDS = ('rep_single_scale', 'rep_multi_scale', 'error_overlap_single_scale', 'error_overlap_multi_scale',
+                 'num_points_single_scale', 'num_points_multi_scale', 'candidates_single_scale', 'candidates_multi_scale',
+                 'valid', 'mma', 'mma_corr', 'avg_mma', 'num_matches', 'num_mutual_corresp')
+_MATCH_COLUMNS = _MATCH_FIELDS + ('kept_src', 'kept_dst')
 
 
 def _gray_u8(sd_image_u8, image_rgb_norm, device):
@@ -425,57 +407,30 @@ def _gray_u8(sd_image_u8, image_rgb_norm, device):
     return t if t.dim() == 2 else ops.rgb_to_gray_u8(t)
 
 
-def _describe_images(grays, rows, count, descriptor, s_mult, batch_size):
-    """One descriptor per detected row: gray images (device, [H,W] uint8 each), rows [I,K,4] / count [I] of
-    ``_detect_images`` -> [I,K,128] float32 (zero rows past an image's count).  Images of one shape go through
-    ``ops.extract_patches_batch`` and ``HardNet.forward_slots`` together, ``batch_size`` at a time."""
-    from collections import OrderedDict
-    from .. import ops
-    desc = torch.zeros(rows.shape[:2] + (128,), dtype=torch.float32, device=rows.device)
-    groups = OrderedDict()
-    for i, g in enumerate(grays):
-        groups.setdefault(tuple(g.shape), []).append(i)
-    for ids in groups.values():
-        for b0 in range(0, len(ids), batch_size):
-            sel = ids[b0:b0 + batch_size]
-            at = torch.tensor(sel, dtype=torch.long, device=rows.device)
-            cnt = count[at]
-            patches = ops.extract_patches_batch(torch.stack([grays[i] for i in sel]), rows[at][:, :, :2].float().contiguous(),
-                                                cnt, float(s_mult))
-            desc[at] = descriptor.forward_slots(patches, cnt)
-    return desc
-
-
 def _matching_chunk(seqs, detector, descriptor, device, nms_size, num_points, border_size, s_mult, th, ths, pixel_threshold,
                     multi_scale, batch_size):
-    """Detect and describe the images of some sequences, each once, and evaluate their pairs -> [P, 16] float64 on the host
-    (one read): the _MATCH_COLUMNS, then the two kept counts; pairs in (sequence, destination) order."""
-    from ..utils import train_utils
-    images, src_ids, dst_ids, hs, shapes = train_utils._chunk_pairs(seqs)
+    """Detect and describe the images of some sequences, each once, and evaluate their pairs -> the _MATCH_COLUMNS per pair on
+    the host (one read; two when the candidate buffer has to grow); pairs in (sequence, destination) order."""
+    images, src_ids, dst_ids, hs, shapes = _chunked.chunk_pairs(seqs)
     if not src_ids:
-        return np.zeros((0, len(_MATCH_COLUMNS) + 2))
+        return _chunked.Table(_MATCH_COLUMNS)
     u8 = []
     for sd in seqs:
         u8.append(sd.get('im_src_BGR'))
         dst_u8 = sd.get('images_dst_BGR')
         u8.extend(dst_u8 if dst_u8 is not None else [None] * len(sd['images_dst_RGB_norm']))
-    rows, count = train_utils._detect_images(images, detector, device, nms_size, num_points, border_size, multi_scale,
-                                             batch_size)
-    desc = _describe_images([_gray_u8(a, im, device) for a, im in zip(u8, images)], rows, count, descriptor, s_mult, batch_size)
-    s_at = torch.tensor(src_ids, dtype=torch.long, device=device)
-    d_at = torch.tensor(dst_ids, dtype=torch.long, device=device)
+    rows, count = _chunked.detect_images(images, detector, device, nms_size, num_points, border_size, multi_scale, batch_size)
+    desc = _chunked.describe_images([_gray_u8(a, im, device) for a, im in zip(u8, images)], rows, count, descriptor, s_mult,
+                                    batch_size)
+    s_at, d_at = _chunked.pair_index(src_ids, dst_ids, device)
     args = (rows[s_at], count[s_at], desc[s_at], rows[d_at], count[d_at], desc[d_at], torch.from_numpy(np.stack(hs)).to(device),
             torch.tensor(shapes, dtype=torch.int32, device=device))
 
     def run(**kw):
         r = evaluate_matching_pairs(*args, th=th, thresholds=ths, pixel_threshold=pixel_threshold, **kw)
-        cols = [getattr(r, k).double() for k in _MATCH_COLUMNS] + [r.kept[:, 0].double(), r.kept[:, 1].double()]
-        return torch.stack(cols, dim=1).cpu().numpy()
+        return _chunked.host_table(r, _MATCH_FIELDS, kept_src=r.kept[:, 0], kept_dst=r.kept[:, 1])
 
-    out = run()                         # the one device-to-host read of the chunk
-    if (out[:, 4:6] < 0).any():         # some pair's candidates did not fit the default buffer: size it from the totals
-        out = run(max_edges=int(max(out[:, 6].sum(), out[:, 7].sum(), 1)))
-    return out
+    return _chunked.with_edge_retry(run)
 
 
 @torch.no_grad()
@@ -498,43 +453,23 @@ def evaluate_matching_hsequences(dataloader, detector, descriptor, device, num_p
       not described again for every destination --, images of one shape ``batch_size`` at a time; ``multi_scale`` as in
       ``check_val_hsequences_repeatability``.
     * The pairs of ``chunk_sequences`` sequences are evaluated in one stream-ordered :func:`evaluate_matching_pairs` call with
-      thresholds 1..10 and ONE device-to-host read per chunk.  On that read the split-f16 guard is applied as
-      ``check_val_hsequences_repeatability`` does: a chunk whose forward was flagged (or during which the checkpoint was
-      switched to the fp32 kernels) is repeated.
+      thresholds 1..10 and ONE device-to-host read per chunk, on which the split-f16 guard is applied as
+      ``check_val_hsequences_repeatability`` does (``guard.run_guarded``: a flagged or switched chunk is repeated).
 
     Returns ``create_metrics_results(sequence names, num_points, 0.6, pixel_threshold)`` (0.6 = 1 - the ``overlap_err`` of
     ``compute_repeatability``) with one entry per list and pair, in (sequence, destination) order; ``num_features`` holds
     the kept counts (source, destination).  A pair with an empty kept list is skipped, as the repeatability loop skips it
     (``continue``): it has no entry, so that a mean over a list is the mean the loop would have taken."""
-    from .test_utils import create_metrics_results
     device = torch.device(device)
-    guard = getattr(detector, "fp16_guard_check", None)
     chunk, batch_size = max(1, int(chunk_sequences)), max(1, int(batch_size))
-    ths = [float(t) for t in range(1, 11)]
-    if float(pixel_threshold) not in ths:
-        raise BalfHipError(f"pixel_threshold {pixel_threshold} is not one of the thresholds {ths}")
-    names, out_rows = [], []
-    n_seq = len(dataloader.sequences)
-    for c0 in range(0, n_seq, chunk):
-        seqs = [dataloader.get_sequence_data(i) for i in range(c0, min(n_seq, c0 + chunk))]
-        names.extend(s.get('sequence_name', dataloader.sequences[c0 + k]) for k, s in enumerate(seqs))
-        chunk_args = (seqs, detector, descriptor, device, nms_size, int(num_points), border_size, s_mult, th, ths,
-                      pixel_threshold, multi_scale, batch_size)
-        on_fp32 = getattr(detector, "effective_precision", None) == "fp32"
-        out = _matching_chunk(*chunk_args)
-        flagged = guard is not None and guard(synchronize=False)     # (the read above has passed every forward of the chunk)
-        if flagged or (not on_fp32 and getattr(detector, "effective_precision", None) == "fp32"):
-            out = _matching_chunk(*chunk_args)
-        out_rows.append(out)
+    ths, _ = _threshold_index(range(1, 11), pixel_threshold)
+    names, t = _chunked.run_sequence_chunks(dataloader, detector, chunk, _MATCH_COLUMNS, lambda seqs: _matching_chunk(
+        seqs, detector, descriptor, device, nms_size, int(num_points), border_size, s_mult, th, ths, pixel_threshold,
+        multi_scale, batch_size))
     results = create_metrics_results(names, num_points, 0.6, pixel_threshold)
-    floats = ('rep_single_scale', 'rep_multi_scale', 'error_overlap_single_scale', 'error_overlap_multi_scale', 'mma', 'mma_corr',
-              'avg_mma')
-    col = {k: j for j, k in enumerate(_MATCH_COLUMNS)}
-    for r in (np.concatenate(out_rows) if out_rows else np.zeros((0, len(_MATCH_COLUMNS) + 2))):
-        if r[col['valid']] == 0:
-            continue
-        for k in _MATCH_COLUMNS:
-            if k in results:
-                results[k].append(float(r[col[k]]) if k in floats else int(r[col[k]]))
-        results['num_features'].append((int(r[-2]), int(r[-1])))
+    valid = t['valid'] != 0
+    for k in _MATCH_FIELDS:
+        if k in results:
+            results[k].extend(map(int if k.startswith('num_') else float, t[k][valid]))      # (num_*: the counts)
+    results['num_features'].extend((int(a), int(b)) for a, b in zip(t['kept_src'][valid], t['kept_dst'][valid]))
     return results

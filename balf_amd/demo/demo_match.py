@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from .. import arch, ops
+from ..guard import run_guarded
 
 DEFAULT_ARGS = SimpleNamespace(border_size=15, nms_size=15, num_features=2048, s_mult=60, order_coord="xysr",
                                heatmap_confidence_threshold=0.001, sub_pixel=True, patch_size=4)
@@ -36,14 +37,10 @@ def _detect_gpu(args, im: np.ndarray, detector, device) -> torch.Tensor:
     def run():
         with torch.inference_mode():
             prob = detector.forward_u8(img.unsqueeze(0), want_logits=False)["prob"]
-            return ops.greedy_nms(prob, top, left, h, w, args.border_size, args.heatmap_confidence_threshold, args.nms_size, k,
-                                  args.patch_size if args.sub_pixel else 0)
-    idx, score, xy, count, total = run()
-    n = min(int(count[0].item()), int(args.num_features))       # (a device-to-host read: the stream has passed the forward)
-    # one image per call: the split-f16 status block is final here, for free -- a flagged call is repeated on the fp32 kernels
-    if getattr(detector, "fp16_guard_check", None) is not None and detector.fp16_guard_check(synchronize=False):
-        idx, score, xy, count, total = run()
-        n = min(int(count[0].item()), int(args.num_features))
+            idx, _, xy, count, _ = ops.greedy_nms(prob, top, left, h, w, args.border_size, args.heatmap_confidence_threshold,
+                                                  args.nms_size, k, args.patch_size if args.sub_pixel else 0)
+        return idx, xy, min(int(count[0].item()), int(args.num_features))   # (a device-to-host read: past the forward)
+    idx, xy, n = run_guarded(detector, run)     # (a flagged call is repeated on the fp32 kernels before anything is returned)
     if args.sub_pixel:
         pts = xy[0, :n]
     else:

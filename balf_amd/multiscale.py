@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib, arch, ops
+from .guard import run_guarded
 
 
 @dataclass
@@ -154,7 +155,7 @@ def extract_multiscale_detections(image_RGB_norm, model, device, nms_size=15, nu
     """One ``[H,W,3]`` float image in [0, 1] on the host -> ``[n, 4]`` float64 rows (x, y, radius, score) (``yxsr``: y
     first), n <= num_points, sorted by score: what the HSequences extraction feeds ``compute_repeatability`` /
     ``apply_homography_to_points``.  Like ``pipeline.extract_detections``, a call whose split-f16 forward was flagged is
-    repeated on the fp32 kernels before anything is returned."""
+    repeated on the fp32 kernels before anything is returned (``guard.run_guarded``: one forward per level)."""
     img = np.ascontiguousarray(image_RGB_norm)
     if img.ndim != 3 or img.shape[2] != 3:
         raise ValueError(f"expected an [H,W,3] image, got {img.shape}")
@@ -162,9 +163,9 @@ def extract_multiscale_detections(image_RGB_norm, model, device, nms_size=15, nu
         img = img.astype(np.float64)
     x = torch.from_numpy(img).to(device)[None].to(torch.float32).contiguous()
     args = (num_points, border_size, nms_size, scale_factor_levels, pyramid_levels, upsampled_levels, order_coord)
-    pts, count = _detect(model, x, *args)
-    n = int(count[0])                  # (a device-to-host read: the stream has passed every level's forward)
-    if getattr(model, "fp16_guard_check", None) is not None and model.fp16_guard_check(synchronize=False):
+
+    def run():
         pts, count = _detect(model, x, *args)
-        n = int(count[0])
+        return pts, int(count[0])      # (a device-to-host read: the stream has passed every level's forward)
+    pts, n = run_guarded(model, run)
     return pts[0, :n].cpu().numpy()

@@ -14,13 +14,11 @@ Training (``train_model``, losses, optimiser; train_utils.py:20-160) is out of s
 """
 from __future__ import annotations
 
-from collections import OrderedDict
-
 import numpy as np
 import torch
 
-from .. import multiscale
-from ..benchmark_test import evaluate, geometry_tools, repeatability_tools
+from ..benchmark_test import _chunked, evaluate, geometry_tools, repeatability_tools
+from ..guard import run_guarded
 from ..pipeline import detect_batch, extract_detections, pad_image_on_device  # noqa: F401
 from . import test_utils
 
@@ -37,78 +35,24 @@ def compute_repeatability_with_maximum_filter(src_scores_np, dst_scores_np, homo
             [r['error_overlap_multi_scale']], [r['possible_matches']])
 
 
-
-def _detect_images(images, model, device, nms_size, num_points, border_size, multi_scale, batch_size):
-    """[H,W,3] float images on the host -> (rows [I,K,4] float64, count [I] int32) on the device: rows (x, y, radius, score)
-    as ``extract_detections`` (radius 1.0) or ``extract_multiscale_detections`` returns them, rows past the count unused.
-    Images of one shape go through the detector together, ``batch_size`` at a time (detection is batch-invariant)."""
-    rows = torch.zeros((len(images), num_points, 4), dtype=torch.float64, device=device)
-    count = torch.zeros((len(images),), dtype=torch.int32, device=device)
-    groups = OrderedDict()
-    for i, im in enumerate(images):
-        groups.setdefault((im.shape[0], im.shape[1]), []).append(i)
-    for (h, w), ids in groups.items():
-        for b0 in range(0, len(ids), batch_size):
-            sel = ids[b0:b0 + batch_size]
-            at = torch.tensor(sel, dtype=torch.long, device=device)
-            if multi_scale:
-                x = torch.stack([torch.from_numpy(np.ascontiguousarray(images[i] if images[i].dtype in (np.float64, np.float32, np.float16)
-                                                                       else images[i].astype(np.float64))).to(device)
-                                 for i in sel]).to(torch.float32)
-                pts, cnt = multiscale.detect_batch_multiscale(model, x, num_points=num_points, border_size=border_size,
-                                                              nms_size=nms_size)
-                rows[at] = pts
-            else:
-                x = torch.cat([pad_image_on_device(images[i], device) for i in sel])
-                idx, score, cnt, _ = detect_batch(model, x, h, w, border_size, nms_size, num_points)
-                idx = idx.to(torch.int64)
-                rows[at] = torch.stack([(idx % w).double(), (idx // w).double(), torch.ones_like(score, dtype=torch.float64),
-                                        score.double()], dim=2)
-            count[at] = cnt
-    return rows, count
-
-
-def _chunk_pairs(seqs):
-    """The images of some sequences, each once, and their pairs in (sequence, destination) order -> (images, src_ids, dst_ids,
-    hs, shapes): pair k is images[src_ids[k]] / images[dst_ids[k]] with h_dst_2_src hs[k] and shapes[k] = (h_src, w_src, h_dst,
-    w_dst)."""
-    images, src_ids, dst_ids, hs, shapes = [], [], [], [], []
-    for sd in seqs:
-        src = sd['im_src_RGB_norm']
-        si = len(images)
-        images.append(src)
-        for k, im in enumerate(sd['images_dst_RGB_norm']):
-            src_ids.append(si)
-            dst_ids.append(len(images))
-            images.append(im)
-            hs.append(np.asarray(sd['h_dst_2_src'][k], dtype=np.float64).reshape(3, 3))
-            shapes.append((src.shape[0], src.shape[1], im.shape[0], im.shape[1]))
-    return images, src_ids, dst_ids, hs, shapes
+_REP_FIELDS = ('rep_single_scale', 'rep_multi_scale', 'error_overlap_single_scale', 'error_overlap_multi_scale',
+               'possible_matches', 'num_points_single_scale', 'num_points_multi_scale', 'candidates_single_scale',
+               'candidates_multi_scale')
+_MEANS = _REP_FIELDS[:5]       # what both validations return the means of, in this order
+_SEQ_COLUMNS = _REP_FIELDS + ('valid',)
 
 
 def _evaluate_chunk(seqs, model, device, nms_size, num_points, border_size, multi_scale, batch_size):
-    """Detect the images of some sequences and evaluate their pairs -> [P, 10] float64 on the host, one row per pair in
-    (sequence, destination) order: rep_s, rep_m, err_s, err_m, possible, valid, found_s, found_m, cand_s, cand_m."""
-    images, src_ids, dst_ids, hs, shapes = _chunk_pairs(seqs)
+    """Detect the images of some sequences and evaluate their pairs -> the _SEQ_COLUMNS on the host, one row per pair in
+    (sequence, destination) order."""
+    images, src_ids, dst_ids, hs, shapes = _chunked.chunk_pairs(seqs)
     if not src_ids:
-        return np.zeros((0, 10))
-    rows, count = _detect_images(images, model, device, nms_size, num_points, border_size, multi_scale, batch_size)
-    s_at = torch.tensor(src_ids, dtype=torch.long, device=device)
-    d_at = torch.tensor(dst_ids, dtype=torch.long, device=device)
+        return _chunked.Table(_SEQ_COLUMNS)
+    rows, count = _chunked.detect_images(images, model, device, nms_size, num_points, border_size, multi_scale, batch_size)
+    s_at, d_at = _chunked.pair_index(src_ids, dst_ids, device)
     args = (rows[s_at], count[s_at], rows[d_at], count[d_at], torch.from_numpy(np.stack(hs)).to(device),
             torch.tensor(shapes, dtype=torch.int32, device=device))
-
-    def run(**kw):
-        r = evaluate.evaluate_pairs(*args, **kw)
-        return torch.stack([r.rep_single_scale, r.rep_multi_scale, r.error_overlap_single_scale, r.error_overlap_multi_scale,
-                            r.possible_matches.double(), r.valid.double(), r.num_points_single_scale.double(),
-                            r.num_points_multi_scale.double(), r.candidates_single_scale.double(),
-                            r.candidates_multi_scale.double()], dim=1).cpu().numpy()
-
-    out = run()                         # the one device-to-host read of the chunk
-    if (out[:, 6:8] < 0).any():         # some pair's candidates did not fit the default buffer: size it from the totals
-        out = run(max_edges=int(max(out[:, 8].sum(), out[:, 9].sum(), 1)))
-    return out
+    return _chunked.with_edge_retry(lambda **kw: _chunked.host_table(evaluate.evaluate_pairs(*args, **kw), _SEQ_COLUMNS))
 
 
 @torch.no_grad()
@@ -123,32 +67,19 @@ def check_val_hsequences_repeatability(dataloader, model, device, tb_log, cur_ep
     ``batch_size`` at a time (detection is deterministic and batch-invariant), and the pairs of ``chunk_sequences``
     sequences are evaluated together on the device (``benchmark_test.evaluate.evaluate_pairs``); the per-pair results are
     read once per chunk.  On that read the split-f16 guard is applied as ``extract_detections`` does: a chunk whose forward
-    was flagged is repeated (on the fp32 kernels).  ``multi_scale=True`` detects with ``multiscale.detect_batch_multiscale``
-    (``pyramid_plan`` defaults; ``num_points`` / ``nms_size`` / ``border_size`` as given), the multi-scale HSequences
-    protocol, equal to the same loop over ``extract_multiscale_detections``.  ``tb_log`` must be None: the reference's
-    image logging is not ported.  ``cell_size`` and ``cur_epoch`` are unused, as in the reference."""
+    was flagged, or during which the checkpoint was switched to the fp32 kernels, is repeated (``guard.run_guarded``).
+    ``multi_scale=True`` detects with ``multiscale.detect_batch_multiscale`` (``pyramid_plan`` defaults; ``num_points`` /
+    ``nms_size`` / ``border_size`` as given), the multi-scale HSequences protocol, equal to the same loop over
+    ``extract_multiscale_detections``.  ``tb_log`` must be None: the reference's image logging is not ported.
+    ``cell_size`` and ``cur_epoch`` are unused, as in the reference."""
     if tb_log is not None:
         raise NotImplementedError("check_val_hsequences_repeatability: tensorboard image logging is not ported; pass tb_log=None")
     device = torch.device(device)
-    guard = getattr(model, "fp16_guard_check", None)
-    rep_s, rep_m, error_overlap_s, error_overlap_m, possible_matches = [], [], [], [], []
-    n_seq = len(dataloader.sequences)
-    for c0 in range(0, n_seq, max(1, int(chunk_sequences))):
-        seqs = [dataloader.get_sequence_data(i) for i in range(c0, min(n_seq, c0 + max(1, int(chunk_sequences))))]
-        chunk_args = (seqs, model, device, nms_size, num_points, border_size, multi_scale, int(batch_size))
-        out = _evaluate_chunk(*chunk_args)
-        if guard is not None and guard(synchronize=False):     # (the read above has passed every forward of the chunk)
-            out = _evaluate_chunk(*chunk_args)
-        for r in out:
-            if r[5] == 0:
-                continue
-            rep_s.append(float(r[0]))
-            rep_m.append(float(r[1]))
-            error_overlap_s.append(float(r[2]))
-            error_overlap_m.append(float(r[3]))
-            possible_matches.append(int(r[4]))
-    return np.asarray(rep_s).mean(), np.asarray(rep_m).mean(), np.asarray(error_overlap_s).mean(), \
-        np.asarray(error_overlap_m).mean(), np.asarray(possible_matches).mean()
+    chunk, batch_size = max(1, int(chunk_sequences)), max(1, int(batch_size))
+    _, t = _chunked.run_sequence_chunks(dataloader, model, chunk, _SEQ_COLUMNS, lambda seqs: _evaluate_chunk(
+        seqs, model, device, nms_size, num_points, border_size, multi_scale, batch_size))
+    valid = t['valid'] != 0            # (the reference's loop skips a pair with an empty kept list)
+    return tuple(t[k][valid].mean() for k in _MEANS)
 
 
 _VAL_CONF_THRESH = 0.015      # get_nms_score_map_from_score_map(..., conf_thresh=0.015), train_utils.py:242-243
@@ -156,35 +87,25 @@ _VAL_CONF_THRESH = 0.015      # get_nms_score_map_from_score_map(..., conf_thres
 
 def _evaluate_val_chunk(pairs, model, device, nms_size, num_points, batch_size, max_edges=None):
     """``pairs``: (image_src [3,Hs,Ws], image_dst [3,Hd,Wd], h_dst_2_src [3,3]) tensors.  Forward them (pairs of one shape
-    ``batch_size`` at a time) and evaluate both legs from that forward -> [P, 2, 9] float64 on the host (leg 0 greedy, leg 1
-    window): rep_s, rep_m, err_s, err_m, possible, found_s, found_m, cand_s, cand_m."""
-    out = torch.zeros((len(pairs), 2, 9), dtype=torch.float64, device=device)
-    groups = OrderedDict()
-    for i, (src, dst, _) in enumerate(pairs):
-        groups.setdefault((tuple(src.shape), tuple(dst.shape)), []).append(i)
+    ``batch_size`` at a time) and evaluate both legs from that forward -> the _REP_FIELDS on the host, values [P, 2, 9] (leg 0
+    greedy, leg 1 window)."""
+    out = torch.zeros((len(pairs), 2, len(_REP_FIELDS)), dtype=torch.float64, device=device)
     kw = {} if max_edges is None else {"max_edges": int(max_edges)}
-    for ids in groups.values():
-        for b0 in range(0, len(ids), batch_size):
-            sel = ids[b0:b0 + batch_size]
-            prob_src = model(torch.stack([pairs[i][0] for i in sel]).to(device), want_logits=False)["prob"]
-            prob_dst = model(torch.stack([pairs[i][1] for i in sel]).to(device), want_logits=False)["prob"]
-            h = torch.stack([pairs[i][2].reshape(3, 3) for i in sel]).to(device=device, dtype=torch.float64)
-            at = torch.tensor(sel, dtype=torch.long, device=device)
-            for leg_id, leg in enumerate(("greedy", "window")):
-                r = evaluate.evaluate_val_pairs(prob_src, prob_dst, h, nms_size, num_points, leg=leg,
-                                                conf_thresh=_VAL_CONF_THRESH, **kw)
-                out[at, leg_id] = torch.stack([r.rep_single_scale, r.rep_multi_scale, r.error_overlap_single_scale,
-                                               r.error_overlap_multi_scale, r.possible_matches.double(),
-                                               r.num_points_single_scale.double(), r.num_points_multi_scale.double(),
-                                               r.candidates_single_scale.double(), r.candidates_multi_scale.double()], dim=1)
-    return out.cpu().numpy()            # the one device-to-host read of the chunk
+    for sel in _chunked.batches_by_shape(pairs, lambda p: (tuple(p[0].shape), tuple(p[1].shape)), batch_size):
+        prob_src = model(torch.stack([pairs[i][0] for i in sel]).to(device), want_logits=False)["prob"]
+        prob_dst = model(torch.stack([pairs[i][1] for i in sel]).to(device), want_logits=False)["prob"]
+        h = torch.stack([pairs[i][2].reshape(3, 3) for i in sel]).to(device=device, dtype=torch.float64)
+        at = torch.tensor(sel, dtype=torch.long, device=device)
+        for leg_id, leg in enumerate(("greedy", "window")):
+            r = evaluate.evaluate_val_pairs(prob_src, prob_dst, h, nms_size, num_points, leg=leg, conf_thresh=_VAL_CONF_THRESH,
+                                            **kw)
+            out[at, leg_id] = _chunked.stack_columns(r, _REP_FIELDS)
+    return _chunked.Table(_REP_FIELDS, out.cpu().numpy())       # the one device-to-host read of the chunk
 
 
 def _val_chunk(*args):
-    out = _evaluate_val_chunk(*args)
-    if (out[:, :, 5:7] < 0).any():      # some pair's candidates did not fit the default buffer: size it from the totals
-        out = _evaluate_val_chunk(*args, max_edges=int(max(out[:, :, 7].sum(axis=0).max(), out[:, :, 8].sum(axis=0).max(), 1)))
-    return out
+    """:func:`_evaluate_val_chunk`, repeated with a larger candidate buffer when the default one was too small."""
+    return _chunked.with_edge_retry(lambda **kw: _evaluate_val_chunk(*args, **kw))
 
 
 @torch.no_grad()
@@ -207,28 +128,19 @@ def check_val_repeatability(dataloader, model, device, tb_log, cur_epoch, cell_s
     destination points, repeatability -- ``benchmark_test.evaluate.evaluate_val_pairs``, both legs from the SAME forward.
     Pairs of one shape are forwarded ``batch_size`` at a time and the results of ``chunk_pairs`` pairs are read with one
     device-to-host copy.  On that read the split-f16 guard is applied as ``check_val_hsequences_repeatability`` does (a
-    chunk whose forward was flagged, or during which the checkpoint was switched to the fp32 kernels, is repeated on them), and a chunk whose candidate pairs did not fit the
-    default buffer is repeated with a buffer sized from the reported totals.  ``h_dst_2_src`` is used as float64.
+    chunk whose forward was flagged, or during which the checkpoint was switched to the fp32 kernels, is repeated on them),
+    and a chunk whose candidate pairs did not fit the default buffer is repeated with a buffer sized from the reported totals.  ``h_dst_2_src`` is used as float64.
     ``tb_log`` must be None: the reference's image logging is not ported.  ``cell_size`` and ``cur_epoch``
     are unused, as in the reference.  An empty loader raises ValueError (the reference fails with a NameError)."""
     if tb_log is not None:
         raise NotImplementedError("check_val_repeatability: tensorboard image logging is not ported; pass tb_log=None")
     device = torch.device(device)
-    guard = getattr(model, "fp16_guard_check", None)
     chunk_pairs, batch_size = max(1, int(chunk_pairs)), max(1, int(batch_size))
-    rows, pairs = [], []
+    values, pairs = [], []
 
     def flush():
         args = (list(pairs), model, device, nms_size, num_points, batch_size)
-        on_fp32 = getattr(model, "effective_precision", None) == "fp32"
-        out = _val_chunk(*args)
-        # (the read above has passed every forward of the chunk.)  A chunk runs several forwards, and a later one may already
-        # have looked at an earlier one's status block and switched the checkpoint to the fp32 kernels, after the flagged score
-        # map went into the selection: a switch during the chunk repeats it just as a flag found now does.
-        flagged = guard is not None and guard(synchronize=False)
-        if flagged or (not on_fp32 and getattr(model, "effective_precision", None) == "fp32"):
-            out = _val_chunk(*args)
-        rows.append(out)
+        values.append(run_guarded(model, lambda: _val_chunk(*args)).values)
         pairs.clear()
 
     for batch in dataloader:
@@ -238,10 +150,9 @@ def check_val_repeatability(dataloader, model, device, tb_log, cur_epoch, cell_s
             flush()
     if pairs:
         flush()
-    if not rows:
+    if not values:
         raise ValueError("check_val_repeatability: the dataloader is empty")
-    out = np.concatenate(rows)
-    greedy, last = np.ascontiguousarray(out[:, 0].T), out[-1, 1]          # (contiguous: the summation order of a 1-D array)
-    return (greedy[0].mean(), greedy[1].mean(), greedy[2].mean(), greedy[3].mean(), greedy[4].mean(),
-            np.asarray([last[0]]).mean(), np.asarray([last[1]]).mean(), np.asarray([last[2]]).mean(),
-            np.asarray([last[3]]).mean(), np.asarray([last[4]]).mean())
+    t = _chunked.Table(_REP_FIELDS, np.concatenate(values))
+    # leg 0 (greedy): means over all pairs (contiguous copies: the summation order of a 1-D array); leg 1 (window): the LAST pair alone
+    return tuple(np.ascontiguousarray(t[k][:, 0]).mean() for k in _MEANS) + \
+        tuple(np.asarray([t[k][-1, 1]]).mean() for k in _MEANS)

@@ -8,10 +8,10 @@ import pytest
 import torch
 
 from balf_amd import _lib, arch
-from balf_amd.benchmark_test import evaluate
+from balf_amd.benchmark_test import _chunked, evaluate
 from balf_amd.model import get_model
 from balf_amd.third_party.hardnet.hardnet_pytorch import HardNet
-from balf_amd.utils import synth, train_utils
+from balf_amd.utils import synth
 from tests import matching_common as MC
 from tests.golden import cases
 
@@ -186,9 +186,9 @@ def _detect_describe(images_norm, nets, num_points):
     detector, descriptor = nets
     dev = torch.device(DEV)
     with torch.no_grad():
-        rows, count = train_utils._detect_images(images_norm, detector, dev, 15, num_points, 15, False, 16)
+        rows, count = _chunked.detect_images(images_norm, detector, dev, 15, num_points, 15, False, 16)
         grays = [evaluate._gray_u8(None, im, dev) for im in images_norm]
-        desc = evaluate._describe_images(grays, rows, count, descriptor, 60, 16)
+        desc = _chunked.describe_images(grays, rows, count, descriptor, 60, 16)
     return rows, count, desc
 
 
