@@ -169,3 +169,20 @@ def tensor_key(t):
         return (t.data_ptr(), t._version)
     except RuntimeError:
         return (t.data_ptr(), -1)
+
+
+def pack_state_dict(sd, n, name_of, numel_of, nbytes, pack, what):
+    """The ``n`` tensors of ``sd`` that the library names (``name_of(i)``, ``numel_of(i)`` elements each), as contiguous fp32
+    on the host, through ``pack(pointers, n, out, nbytes)`` -> the packed blob, ``nbytes`` of uint8 on the host."""
+    import torch
+    host = []
+    for i in range(n):
+        name = name_of(i).decode()
+        t = sd[name].detach().to("cpu", torch.float32).contiguous()
+        if t.numel() != numel_of(i):
+            raise BalfHipError(f"{name}: {t.numel()} elements, library expects {numel_of(i)}")
+        host.append(t)
+    ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in host])
+    blob = torch.empty(nbytes, dtype=torch.uint8)
+    check(pack(ptrs, n, blob.data_ptr(), nbytes), what)
+    return blob

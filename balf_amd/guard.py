@@ -1,5 +1,5 @@
 """The one retry rule of every caller that consumes a split-f16 forward's results before the guard has looked at them
-(``MLP_MA_DECODER._guarded_call``).  Imports none of its callers."""
+(``model/fp16_guard.py``).  Imports none of its callers."""
 
 
 def run_guarded(model, run):

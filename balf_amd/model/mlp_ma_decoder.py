@@ -10,8 +10,6 @@ There is no CPU path; a CPU tensor raises.
 """
 from __future__ import annotations
 
-import ctypes as C
-import os
 import warnings
 from operator import attrgetter, is_ as _IS
 
@@ -20,6 +18,7 @@ import torch.nn as nn
 
 from .. import _lib, arch, ops
 from .._lib import BalfHipError, check, lib
+from . import fp16_guard
 
 # The packed-weight cache must notice every way a checkpoint can change under it, and a single-image call (the
 # reference's only calling pattern, /root/reference/demo/demo_match.py:29) must not pay for that: walking the 167 state
@@ -92,58 +91,6 @@ def _down(cin, c, a):
     return d
 
 
-_GUARD_SLOTS = 8
-
-
-class _PendingCall:
-    """A guarded split-f16 forward that has not been looked at yet.  Holds NO tensor: scalars, an event recorded behind the
-    call and weak references to its input and outputs, so that a batch the caller has dropped is freed at once (ADVICE r5:
-    the closure kept here before pinned ~1.3 GB at 32 x 1080p until the next forward)."""
-    __slots__ = ("ev", "wkey", "slot", "seq", "kind", "dims", "refs")
-
-    def __init__(self, ev, wkey, slot, seq, kind, dims, refs):
-        self.ev, self.wkey, self.slot, self.seq, self.kind, self.dims, self.refs = ev, wkey, slot, seq, kind, dims, refs
-
-
-class _Fp16Guard:
-    """The status blocks of the split-f16 forwards on one device (include/balf_hip.h: balf_forward_status): a RING of
-    _GUARD_SLOTS blocks of four ints in PINNED HOST memory.  Every guarded call gets a block of its own, so that a word raised by
-    call A is attributed to A however far the host has run ahead (with one shared block a flag of A was charged to whatever call
-    happened to be pending when the host looked); the kernels store into it when a softmax denominator is not finite or
-    a stage output reaches the largest f16, the host reads it without a copy.  `pending`: the calls not yet looked at, oldest
-    first."""
-
-    def __init__(self, device):
-        import collections
-        with torch.inference_mode(False):   # (a NORMAL tensor even when the first forward runs under torch.inference_mode(): an
-            # inference tensor could not be cleared from outside that mode later)
-            self.words = torch.zeros(_GUARD_SLOTS * _lib.STATUS_WORDS, dtype=torch.int32).pin_memory()
-        self.device = device
-        self.pending = collections.deque()
-        self.seq = 0
-
-    def ptr(self, slot: int) -> int:
-        return self.words.data_ptr() + slot * _lib.STATUS_WORDS * 4
-
-    def read_and_clear(self, slot: int):
-        v = self.words[slot * _lib.STATUS_WORDS:(slot + 1) * _lib.STATUS_WORDS]
-        w = v.tolist()
-        if any(w):
-            v.zero_()
-        return w
-
-
-def _guard_mode() -> str:
-    """BALF_FP16_GUARD = lazy (default) | sync | off.  lazy: the status block of a split-f16 forward is looked at when the
-    NEXT forward of the module starts (or in fp16_guard_check()), never with a synchronisation on the hot path; sync: before
-    the forward returns (one stream synchronisation per call, the flagged batch is re-run before anyone sees it); off: the
-    kernels get no status block."""
-    m = os.environ.get("BALF_FP16_GUARD", "lazy")
-    if m not in ("lazy", "sync", "off"):
-        raise ValueError(f"BALF_FP16_GUARD must be lazy, sync or off, got {m!r}")
-    return m
-
-
 class MLP_MA_DECODER(nn.Module):
     def __init__(self, model_cfg, precision: str = "fp16"):
         super().__init__()
@@ -164,7 +111,8 @@ class MLP_MA_DECODER(nn.Module):
         self._packed = {}              # precision -> (weights key, device blob)
         self._fp16_verdict = None      # (weights key, precision the split-f16 request resolves to for these weights)
         self._effective = None
-        self._guard = {}               # device -> _Fp16Guard (status block of the split-f16 forwards, see _guarded_call)
+        self._validating = False       # inside validate_fp16: no probes, no status block, no look
+        self._guard = fp16_guard.Fp16Guard()       # the status blocks of the split-f16 forwards; acts through _on_flag
 
     # ---- weights -> packed device blob -------------------------------------------------------
     @staticmethod
@@ -173,9 +121,6 @@ class MLP_MA_DECODER(nn.Module):
             return {"fp32": _lib.PREC_FP32, "fp16": _lib.PREC_FP16}[precision]
         except KeyError:
             raise ValueError(f"precision must be 'fp32' or 'fp16', got {precision!r}")
-
-    def _precision_code(self) -> int:
-        return self._code_of(self.precision)
 
     @property
     def effective_precision(self) -> str:
@@ -242,51 +187,36 @@ class MLP_MA_DECODER(nn.Module):
         if hit is not None and hit[0] == wkey:
             return hit[1]
         l = lib()
-        sd = self.state_dict()
-        n = l.balf_num_state_tensors()
-        host = []
-        for i in range(n):
-            name = l.balf_state_tensor_name(i).decode()
-            t = sd[name].detach().to("cpu", torch.float32).contiguous()
-            if t.numel() != l.balf_state_tensor_numel(i):
-                raise BalfHipError(f"{name}: {t.numel()} elements, library expects {l.balf_state_tensor_numel(i)}")
-            host.append(t)
-        ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in host])
         nbytes = l.balf_packed_weights_bytes(prec)
         if nbytes == 0:
             raise BalfHipError(f"precision {precision!r} is not available in this build of libbalf_hip.so")
-        blob = torch.empty(nbytes, dtype=torch.uint8)
-        check(l.balf_pack_weights(ptrs, n, prec, blob.data_ptr(), nbytes), "balf_pack_weights")
-        blob = blob.to(device)
+        blob = _lib.pack_state_dict(self.state_dict(), l.balf_num_state_tensors(), l.balf_state_tensor_name,
+                                    l.balf_state_tensor_numel, nbytes,
+                                    lambda ptrs, n, out, size: l.balf_pack_weights(ptrs, n, prec, out, size),
+                                    "balf_pack_weights").to(device)
         self._packed[precision] = (wkey, blob)
         return blob
 
     def _resolve(self, device):
-        """-> (precision to run, its blob).  Once per set of weights, when the split-f16 path is requested: the default
-        path carries every MFMA operand as two f16 halves, and an activation or weight beyond +-6.5e4 turns into inf/NaN
-        without any trap (split16.h).  A checkpoint is therefore tried on three small images (noise, black, white) against
-        the exact-fp32 kernels; if the score maps disagree or are not finite THESE WEIGHTS run on the fp32 kernels (still
-        the HIP library, ~2.5x slower) and the module says so -- or raises with BALF_FP16_STRICT=1.  The requested
+        """-> (precision to run, its blob, the weights key).  Once per set of weights, when the split-f16 path is requested:
+        the default path carries every MFMA operand as two f16 halves, and an activation or weight beyond +-6.5e4 turns into
+        inf/NaN without any trap (split16.h).  A checkpoint is therefore tried on three small images (noise, black, white)
+        against the exact-fp32 kernels; if the score maps disagree or are not finite THESE WEIGHTS run on the fp32 kernels
+        (still the HIP library, ~2.5x slower) and the module says so -- or raises with BALF_FP16_STRICT=1.  The requested
         precision is left alone: the next checkpoint is judged afresh."""
-        g = self._guard.get(device)
-        if g is not None and g.pending and not getattr(self, "_validating", False) and not torch.cuda.is_current_stream_capturing():
-            self._guard_look(g, final=False)                     # lazy look at the finished calls' status blocks (no wait;
-            #                                                      not under graph capture: an event query would invalidate it)
         wkey = self._weights_key(device)
         prec = self.precision
-        if prec == "fp16" and not getattr(self, "_validating", False) and self._fp16_verdict is not None \
-                and self._fp16_verdict[0] == wkey and self._fp16_verdict[1] == "fp32" \
-                and os.environ.get("BALF_FP16_CHECK", "1") == "0":
-            prec = "fp32"                                        # (a guard verdict holds even where the load-time probes are off)
-        elif prec == "fp16" and not getattr(self, "_validating", False) and os.environ.get("BALF_FP16_CHECK", "1") != "0":
+        if prec == "fp16" and not self._validating:
             v = self._fp16_verdict
-            if v is None or v[0] != wkey:
-                self._fp16_verdict = v = (wkey, self._check_fp16_range(device))
-            prec = v[1]
+            if fp16_guard.check_enabled():
+                if v is None or v[0] != wkey:
+                    self._fp16_verdict = v = (wkey, self._check_fp16_range(device))
+                prec = v[1]
+            elif v is not None and v[0] == wkey:
+                prec = v[1]                                      # (a guard verdict holds even where the load-time probes are off)
         self._code_of(prec)
         self._effective = prec
-        self._last_wkey = wkey           # (the guard below tags the call with it: one key computation per forward)
-        return prec, self.packed_weights(device, prec, wkey)
+        return prec, self.packed_weights(device, prec, wkey), wkey
 
     def _check_fp16_range(self, device) -> str:
         g = torch.Generator(device="cpu").manual_seed(1)
@@ -297,7 +227,7 @@ class MLP_MA_DECODER(nn.Module):
             self.validate_fp16(x.to(device))
             return "fp16"
         except BalfHipError as e:
-            if os.environ.get("BALF_FP16_STRICT") == "1":
+            if fp16_guard.strict():
                 raise
             warnings.warn(f"balf_amd: this checkpoint is outside the range of the split-f16 path ({e}); "
                           "running it with the exact-fp32 MFMA kernels (effective_precision='fp32')", RuntimeWarning)
@@ -317,100 +247,70 @@ class MLP_MA_DECODER(nn.Module):
         b, _, h, w = x.shape
         if h % 64 or w % 64:
             raise ValueError(f"H and W must be multiples of 64 (pad with mod_padding_symmetric), got {h}x{w}")
-        x = x.contiguous().float()
-        dev = x.device
+        return self._forward("f32", (b, h, w), x.contiguous().float(), b, h, w, want_logits)
+
+    def _forward(self, kind, dims, src, b, hp, wp, want_logits):
+        """The body of ``forward`` / ``forward_u8`` on a checked input: ``dims`` are the kernel's own (see _launch), ``hp x wp``
+        the padded size of the outputs.  The status block of a split-f16 call and what happens when it is raised:
+        fp16_guard.Fp16Guard.submit, _on_flag."""
+        dev = src.device
         _lib.require_mi355x(dev)
         l = lib()
-        prec, blob = self._resolve(dev)
-        prob = torch.empty((b, h, w), dtype=torch.float32, device=dev)
-        logits = torch.empty((b, 65, h // 8, w // 8), dtype=torch.float32, device=dev) if want_logits else None
-        nbytes = l.balf_forward_workspace_bytes(b, h, w)
-
-        self._guarded_call(dev, prec, blob, "f32", (b, h, w, nbytes), (x, prob, logits))
+        # (under hipGraph capture -- torch.cuda.graph -- the call is recorded without a status block and nothing is looked at: events
+        # of a capture cannot be queried, a query would invalidate it and a replay has no host side that could look; validate such
+        # a pipeline once with validate_fp16)
+        quiet = self._validating or torch.cuda.is_current_stream_capturing()
+        if not quiet:
+            self._guard.look(dev, self._on_flag)                 # lazy look at the finished calls' status blocks (no wait)
+        prec, blob, wkey = self._resolve(dev)
+        prob = torch.empty((b, hp, wp), dtype=torch.float32, device=dev)
+        logits = torch.empty((b, 65, hp // 8, wp // 8), dtype=torch.float32, device=dev) if want_logits else None
+        dims += (l.balf_forward_workspace_bytes(b, hp, wp),)
+        self._guard.submit(dev, prec == "fp16" and not quiet,
+                           lambda status: self._launch(kind, dims, blob, prec, status, src, prob, logits),
+                           self._on_flag, (wkey, kind, dims), (src, prob, logits))
         return {"logits": logits, "prob": prob}
 
     def _launch(self, kind, dims, blob, prec, status, src, prob, logits):
-        """One balf_forward_status / balf_forward_u8_status on the current stream of prob's device (``status``: pointer or None)."""
+        """One balf_forward_status / balf_forward_u8_status on the current stream of prob's device (``status``: pointer or
+        None) -> that stream."""
         l = lib()
         dev = prob.device
         ws = ops._workspace("forward", dev, dims[-1])
         lg = logits.data_ptr() if logits is not None else None
+        stream = torch.cuda.current_stream(dev)
         with torch.cuda.device(dev):
             if kind == "f32":
                 b, h, w, _ = dims
                 check(l.balf_forward_status(blob.data_ptr(), self._code_of(prec), src.data_ptr(), b, h, w, lg, prob.data_ptr(),
-                                            ws.data_ptr(), ws.numel(), status, _lib.current_stream_ptr(dev)), "balf_forward")
+                                            ws.data_ptr(), ws.numel(), status, stream.cuda_stream), "balf_forward")
             else:
                 ch, b, h, w, _ = dims
                 check(l.balf_forward_u8_status(blob.data_ptr(), self._code_of(prec), src.data_ptr(), ch, b, h, w, lg,
-                                               prob.data_ptr(), ws.data_ptr(), ws.numel(), status,
-                                               _lib.current_stream_ptr(dev)), "balf_forward_u8")
+                                               prob.data_ptr(), ws.data_ptr(), ws.numel(), status, stream.cuda_stream),
+                      "balf_forward_u8")
+        return stream
 
     # ---- the split-f16 path on inputs nobody has seen (VERDICT r4 item 3) ----------------------
-    def _guarded_call(self, dev, prec, blob, kind, dims, tensors):
-        """Run one forward (``_launch(kind, dims, ...)`` on ``tensors`` = (input, prob, logits or None)).  On the split-f16
-        path the kernels get a status block of the call's own (a ring of _GUARD_SLOTS); what it says is acted on according to
-        BALF_FP16_GUARD (see _guard_mode): a flagged batch is re-run on the exact-fp32 kernels INTO THE SAME OUTPUT TENSORS, the
-        module warns (BALF_FP16_STRICT=1: raises) and these weights run on the fp32 kernels from then on (effective_precision
-        says so).  ``sync``: that happens before the forward returns -- nobody sees a flagged value.  ``lazy`` (default): the
-        look happens when a later forward starts (or in fp16_guard_check()), never with a wait on the hot path; the repair is
-        stream-ordered, so GPU work enqueued AFTER it sees the repaired tensors, but what was enqueued between the flagged call
-        and the look (the NMS of pipeline.detect_batch, a copy to the host) has used the split path's values: the warning names
-        the call and says how many later ones had been enqueued -- repeat those, or run with BALF_FP16_GUARD=sync where that
-        matters.  Only weak references are kept: outputs the caller has dropped are not repaired (and not kept alive)."""
-        mode = _guard_mode()
-        if prec != "fp16" or mode == "off" or getattr(self, "_validating", False) or torch.cuda.is_current_stream_capturing():
-            # (under hipGraph capture -- torch.cuda.graph -- the call is recorded without a status block: events of a capture cannot
-            # be queried and a replay has no host side that could look; validate such a pipeline once with validate_fp16)
-            self._launch(kind, dims, blob, prec, None, *tensors)
-            return
-        g = self._guard.get(dev)
-        if g is None:
-            g = self._guard[dev] = _Fp16Guard(dev)
-        if len(g.pending) >= _GUARD_SLOTS:                       # the host is a whole ring ahead: the oldest call's block is
-            g.pending[0].ev.synchronize()                        # needed again -- wait for that call (only) and look at it
-            self._guard_look(g, final=False)
-        slot = g.seq % _GUARD_SLOTS
-        g.seq += 1
-        self._launch(kind, dims, blob, prec, g.ptr(slot), *tensors)
-        import weakref
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(dev))
-        refs = tuple(weakref.ref(t) if t is not None else None for t in tensors)
-        g.pending.append(_PendingCall(ev, self._last_wkey, slot, g.seq, kind, dims, refs))
-        if mode == "sync":
-            ev.synchronize()
-            self._guard_look(g, final=True)
-
-    def _guard_look(self, g, final: bool):
-        """Look at the status blocks of the pending calls the stream has passed, oldest first (``final``: it has passed all)."""
-        while g.pending:
-            p = g.pending[0]
-            if not final and not p.ev.query():
-                return                  # still running: its block is its own, a later look sees it
-            g.pending.popleft()
-            words = g.read_and_clear(p.slot)
-            if any(words):
-                self._guard_act(g, p, words, later=len(g.pending))
-
-    def _guard_act(self, g, p, words, later: int):
+    def _on_flag(self, p, words, later: int) -> bool:
+        """A guarded call's status block holds a word (fp16_guard.Fp16Guard) -> whether the fp32 verdict was set."""
         # Any word is a reason to leave the split path: beyond 65504 the high half saturates and the low half alone (11 bits)
         # carries the excess -- ~3e-4 relative instead of 2^-20 --, beyond ~1.3e5 the products turn into inf / NaN.
         msg = (f"an operand of the split-f16 path left the range of its f16 halves on a caller's input (guarded call #{p.seq}, "
                f"status words score={words[0]} range={words[1]} se={words[2]}: non-finite score map / stage output >= 65504 / "
                "non-finite squeeze-excite)")
-        if os.environ.get("BALF_FP16_STRICT") == "1":
+        if fp16_guard.strict():
             raise BalfHipError(msg + "; use precision='fp32' for this checkpoint")
         # these weights run on the exact-fp32 kernels from now on ...
-        dev = g.device
-        same_weights = self._weights_key(dev) == p.wkey
+        wkey, kind, dims = p.what
+        same_weights = self._weights_key(p.device) == wkey
         if same_weights:
-            self._fp16_verdict = (p.wkey, "fp32")
+            self._fp16_verdict = (wkey, "fp32")
         src, prob, logits = (r() if r is not None else None for r in p.refs)
         repaired = False
         if src is not None and prob is not None and same_weights:
             # ... and the flagged batch is computed again into the tensors the caller still holds
-            self._launch(p.kind, p.dims, self.packed_weights(dev, "fp32", p.wkey), "fp32", None, src, prob, logits)
+            self._launch(kind, dims, self.packed_weights(p.device, "fp32", wkey), "fp32", None, src, prob, logits)
             repaired = True
         del src, prob, logits
         self._effective = "fp32"
@@ -421,20 +321,14 @@ class MLP_MA_DECODER(nn.Module):
                     "the split path's values: repeat it, or run with BALF_FP16_GUARD=sync")
         warnings.warn("balf_amd: " + msg + how + ", and this checkpoint runs on the fp32 kernels from now on "
                       "(effective_precision='fp32')", RuntimeWarning)
+        return same_weights
 
     def fp16_guard_check(self, synchronize: bool = True) -> bool:
-        """Act on the status blocks of the split-f16 forwards so far now (see _guarded_call); ``synchronize`` waits for them.
+        """Act on the status blocks of the split-f16 forwards so far now (see Fp16Guard.submit); ``synchronize`` waits for them.
         Returns True when a flag was found and acted on -- a caller that has already used that call's results (copied them to
         the host like pipeline.extract_detections and demo_match.detect, the reference's one-image-per-call pattern, or fed them
         to further kernels like pipeline.detect_batch) repeats its call then."""
-        hit = False
-        for g in self._guard.values():
-            if g.pending and synchronize:
-                g.pending[-1].ev.synchronize()
-            before = self._fp16_verdict
-            self._guard_look(g, final=synchronize)
-            hit = hit or (self._fp16_verdict is not before and self._fp16_verdict is not None and self._fp16_verdict[1] == "fp32")
-        return hit
+        return self._guard.check(self._on_flag, synchronize)
 
     def stage_view(self, b: int, h: int, w: int, device=None):
         """Validation aid: after ``forward`` / ``forward_u8`` of a batch whose PADDED shape is ``[b,3,h,w]`` on the current
@@ -477,7 +371,7 @@ class MLP_MA_DECODER(nn.Module):
         that are merely small (a residual branch at 2^-12, near-constant channels) measured 3e-6
         (tests/test_checkpoint_family_gpu.py, profiles/checkpoint_family.json)."""
         keep = self.precision
-        nested = getattr(self, "_validating", False)
+        nested = self._validating
         try:
             self._validating = True
             self.precision = "fp32"
@@ -510,13 +404,4 @@ class MLP_MA_DECODER(nn.Module):
         b, h, w = images.shape[:3]
         ch = 1 if images.dim() == 3 else 3
         hp, wp, _, _ = arch.padded_hw(h, w)
-        dev = images.device
-        _lib.require_mi355x(dev)
-        l = lib()
-        prec, blob = self._resolve(dev)
-        prob = torch.empty((b, hp, wp), dtype=torch.float32, device=dev)
-        logits = torch.empty((b, 65, hp // 8, wp // 8), dtype=torch.float32, device=dev) if want_logits else None
-        nbytes = l.balf_forward_workspace_bytes(b, hp, wp)
-
-        self._guarded_call(dev, prec, blob, "u8", (ch, b, h, w, nbytes), (images, prob, logits))
-        return {"logits": logits, "prob": prob}
+        return self._forward("u8", (ch, b, h, w), images, b, hp, wp, want_logits)

@@ -453,7 +453,7 @@ def test_lazy_guard_attributes_the_flag_to_its_call_and_holds_no_tensor(monkeypa
         return m
     # (a)
     m = fresh()
-    first = m._guard[torch.device("cuda:0")].seq
+    first = m._guard.rings[torch.device("cuda:0")].seq
     with W.catch_warnings():
         W.simplefilter("error")
         torch.cuda._sleep(int(4e8))                      # the stream is busy (~0.2 s): all three calls are enqueued before any finishes
@@ -468,7 +468,7 @@ def test_lazy_guard_attributes_the_flag_to_its_call_and_holds_no_tensor(monkeypa
     torch.cuda.synchronize()
     assert torch.equal(out_a["prob"], want_a)
     assert torch.equal(out_b["prob"], b_before) and torch.equal(out_c["prob"], b_before)
-    assert m.effective_precision == "fp32" and not m._guard[torch.device("cuda:0")].pending
+    assert m.effective_precision == "fp32" and not m._guard.rings[torch.device("cuda:0")].pending
     # (b)
     m = fresh()
     big = xb.repeat(8, 1, 1, 1).contiguous()
@@ -488,6 +488,47 @@ def test_lazy_guard_attributes_the_flag_to_its_call_and_holds_no_tensor(monkeypa
     assert torch.cuda.memory_allocated() <= base + 4096, "the pending guard entry keeps the dropped outputs alive"
     with pytest.warns(RuntimeWarning, match="could not be repaired"):
         assert m.fp16_guard_check(synchronize=True)
+
+
+def test_lazy_guard_with_the_ring_full_waits_for_the_oldest_call_and_charges_its_flag(monkeypatch):
+    """The host runs a whole ring ahead: flagged call A, then ten calm calls behind a busy stream with no synchronisation.  The ninth
+    call finds all eight blocks pending, waits for A alone and looks at it before A's block is handed out again: the warning --
+    raised inside that forward -- names A and the seven calls behind it, A's tensor is repaired, the calls after the switch run on
+    the fp32 kernels, and nothing is left pending after the final check (which has nothing left to report)."""
+    from balf_amd.model import get_model
+    sd, bright = _scaled_checkpoint_and_images()
+    monkeypatch.delenv("BALF_FP16_STRICT", raising=False)
+    monkeypatch.setenv("BALF_FP16_GUARD", "lazy")
+    dev = torch.device("cuda:0")
+    ref = get_model.load_model(arch.DEFAULT_MODEL_CFG)
+    ref.load_state_dict(sd)
+    ref.precision = "fp32"
+    ref = ref.eval().to(dev)
+    calm = cases.forward_input(1, 128, 128, 3).to(dev)
+    xb = bright.to(dev)
+    want_a = ref(xb, want_logits=False)["prob"]
+    want_calm = ref(calm, want_logits=False)["prob"]
+    m = get_model.load_model(arch.DEFAULT_MODEL_CFG)
+    m.load_state_dict(sd)
+    m = m.eval().to(dev)
+    split_calm = m(calm, want_logits=False)["prob"].clone()
+    torch.cuda.synchronize()
+    assert m.effective_precision == "fp16"
+    ring = m._guard.rings[dev]
+    first = ring.seq
+    with pytest.warns(RuntimeWarning) as rec:
+        torch.cuda._sleep(int(4e8))                      # the stream is busy (~0.2 s): nothing finishes while the host enqueues
+        out_a = m(xb, want_logits=False)
+        outs = [m(calm, want_logits=False)["prob"] for _ in range(10)]
+    text = " ".join(str(r.message) for r in rec)
+    assert f"guarded call #{first + 1}" in text and "7 later forward(s)" in text and "same output tensors" in text, text
+    assert ring.seq == first + 9                         # A, eight calm calls on the split path; the last two ran unguarded
+    assert m.effective_precision == "fp32"
+    assert not m.fp16_guard_check(synchronize=True) and not ring.pending
+    torch.cuda.synchronize()
+    assert torch.equal(out_a["prob"], want_a)
+    assert all(torch.equal(o, split_calm) for o in outs[:8])          # enqueued before the switch: left alone
+    assert all(torch.equal(o, want_calm) for o in outs[8:])           # enqueued after it: the fp32 kernels
 
 
 def test_single_image_callers_repeat_a_flagged_call(monkeypatch):
