@@ -46,9 +46,12 @@ struct RrArgs {
     int *kept_n;                            // [P, 2]
 };
 
-// order-preserving map of a float64 onto unsigned: a < b  <=>  key(a) < key(b); never 0 (0 marks a dropped row)
+// order-preserving map of a float64 onto unsigned: a < b  <=>  key(a) < key(b); never 0 (0 marks a dropped row).  -0.0 takes
+// the key of +0.0: the two compare equal, so between them the lower row index decides, as in NumPy's stable argsort.  NaN has
+// no place in the order: probs are finite by contract.
 __device__ __forceinline__ unsigned long long prob_key(double v) {
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    if ((b << 1) == 0ull) b = 0ull;                              // -0.0 -> +0.0
     const unsigned long long k = (b >> 63) ? ~b : (b | 0x8000000000000000ull);
     return k ? k : 1ull;
 }

@@ -349,8 +349,11 @@ int balf_common_region_masks(const double *h_dst_2_src_host, int h_src, int w_sr
  * those balf_common_region_masks computes for the pair with border 15, evaluated at the point only (the two inverse maps are
  * computed on the device in the same operations).  Kept rows keep their order: src_out_dev [P,ns_max,4] the kept source rows,
  * dst_out_dev [P,nd_max,4] the kept destination rows warped as balf_apply_homography does (score carried); rows past the kept
- * count are 0.  kept_dev [P,2] = kept counts (source, destination); valid_dev[P] = both > 0.  A singular h_dst_2_src keeps
- * nothing.  No workspace.
+ * count are 0.  kept_dev [P,2] = kept counts (source, destination); valid_dev[P] = both > 0.  A singular h_dst_2_src (the
+ * closed-form determinant is exactly 0) and a pair whose shapes_dev row has an entry <= 0 keep nothing: kept (0, 0), valid 0,
+ * every output row of the pair 0 (and every index -1); the other pairs of the batch are not affected.  Images smaller than
+ * 31 x 31 have empty masks (the 15-pixel frame); a coordinate that is NaN, infinite or rounds outside [-n, n) drops its row.
+ * No workspace.
  *
  * balf_repeatability_batch: balf_repeatability for each pair, bit-identical to it.  Rows of src_dev / dst_dev start with
  * (x, y, radius), src_stride / dst_stride doubles apart (>= 3); pair p's rows start at row p * ns_max / p * nd_max, its counts
@@ -434,7 +437,9 @@ int balf_val_points(const float *prob_src_dev, int h_src, int w_src, const float
  *                     goes on UNWARPED;
  *   source rows:      warped with h; the WARPED (row, col, prob) goes on when inside (h_dst, w_dst);
  *   select_k_best:    the keep_k_points rows of highest prob of each side (all when fewer).  Ties at the cut: higher prob
- *                     first, then the lower original index (the reference cuts with NumPy's unstable argsort);
+ *                     first, then the lower original index (the reference cuts with NumPy's unstable argsort); -0.0 and
+ *                     +0.0 are equal probs.  Probs are finite: a NaN prob is outside the contract (its place in the order
+ *                     is unspecified);
  *   N1 x N2 Euclidean distances sqrt(dy*dy + dx*dx) (float64, no fused operation), row minima (when N2 != 0) and column minima
  *   (when N1 != 0), count1 / count2 = minima <= distance_thresh, summed in one fixed order (a pair's result does not depend on
  *   P or on its place in the batch).
