@@ -88,6 +88,8 @@ PROTOTYPES = {
     "balf_synth_pairs_workspace_bytes": (_sz, [_i, _i]),
     "balf_synth_pairs": (_i, [_vp, _sz, _vp, _vp, _i, _vp, _vp, _vp, _fp, _i, _vp, _i, _i, _fp, _fp, _fp, _fp, _vp, _vp, _sz,
                              _vp]),
+    "balf_detector_loss_workspace_bytes": (_sz, [_i, _i, _i]),
+    "balf_detector_loss": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _fp, _fp, _vp, _fp, _vp, _sz, _vp]),
     "balf_profile_num_slots": (_i, []),
     "balf_profile_slot_name": (C.c_char_p, [_i]),
     "balf_profile_begin": (_i, []),

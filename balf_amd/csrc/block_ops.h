@@ -36,7 +36,11 @@ struct WorkspaceCursor {
 };
 
 // ---- wave level (64 lanes, all active) ----------------------------------------------------------------------------------------
-__device__ __forceinline__ int wave_sum(int v) {
+// (summed in the type of the argument: a bool or a comparison would be summed as such, hence the list)
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
+    static_assert(std::is_same<T, int>::value || std::is_same<T, unsigned>::value || std::is_same<T, float>::value ||
+                      std::is_same<T, double>::value, "wave_sum: int, unsigned, float or double");
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
@@ -61,13 +65,14 @@ __device__ __forceinline__ int clamp_count(const int *c, long at, int n_max) {
 
 // ---- workgroup level ----------------------------------------------------------------------------------------------------------
 // Sum of v over the workgroup, returned to every thread.  Two barriers: before s_red is written (frees it), after.
-template <int THREADS>
-__device__ __forceinline__ int block_sum(int v, int *s_red /*[THREADS / 64]*/) {
+// (int counts, and the float64 sums of detector_loss.hip: one fixed order, butterfly in the wave, then wave 0 upwards)
+template <int THREADS, typename T>
+__device__ __forceinline__ T block_sum(T v, T *s_red /*[THREADS / 64]*/) {
     v = wave_sum(v);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
     __syncthreads();
-    int t = 0;
+    T t = 0;
 #pragma unroll
     for (int w = 0; w < THREADS / 64; ++w) t += s_red[w];
     return t;

@@ -3,7 +3,7 @@ is the HIP library's).  Every function requires CUDA tensors and raises otherwis
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -521,3 +521,54 @@ def synth_pairs(packed: torch.Tensor, offsets: torch.Tensor, sizes: torch.Tensor
                                  out[2].data_ptr(), out[3].data_ptr(), out[4].data_ptr(), ws.data_ptr(), ws.numel(),
                                  current_stream_ptr(dev)), "balf_synth_pairs")
     return tuple(out)
+
+
+class DetectorLoss(NamedTuple):
+    loss: torch.Tensor                        # [] float32
+    per_image: Optional[torch.Tensor]         # [B] float32
+    labels: Optional[torch.Tensor]            # [B,Hc,Wc] int32
+    dlogits: Optional[torch.Tensor]           # [B,65,Hc,Wc] float32
+
+
+def detector_loss(logits: torch.Tensor, keypoint_map: torch.Tensor, valid_mask=None, noise=None, want_per_image: bool = False,
+                  want_labels: bool = False, want_grad: bool = False) -> DetectorLoss:
+    """The reference's detector_loss (/root/reference/balf/loss/loss_function.py:7-26) for grid_size 8 and, with
+    ``want_grad``, its gradient with respect to the logits: balf_detector_loss in include/balf_hip.h.  ``logits``
+    [B,65,Hc,Wc], ``keypoint_map`` and ``valid_mask`` (None = all ones) [B,1,8Hc,8Wc], ``noise`` (None = no tie-break noise)
+    [B,65,Hc,Wc], all float32 and contiguous on one GPU.  Fields that were not requested are None."""
+    # shapes, dtypes and contiguity from the tensors' metadata first: a wrong call is refused before any device is touched
+    if logits.dim() != 4 or logits.shape[1] != 65:
+        raise BalfHipError(f"logits must be [B,65,Hc,Wc] (the 65-channel head, cell size 8), got {tuple(logits.shape)}")
+    b, _, hc, wc = logits.shape
+    if not 1 <= b <= 65535 or hc < 1 or wc < 1 or hc * wc > 1 << 24:
+        raise BalfHipError(f"detector_loss: 1 <= B <= 65535 and 1 <= Hc * Wc <= 2^24, got {tuple(logits.shape)}")
+    for t, name, shape in ((logits, "logits", None), (keypoint_map, "keypoint_map", (b, 1, 8 * hc, 8 * wc)),
+                           (valid_mask, "valid_mask", (b, 1, 8 * hc, 8 * wc)), (noise, "noise", (b, 65, hc, wc))):
+        if t is None:
+            continue
+        if t.dtype != torch.float32:
+            raise BalfHipError(f"{name} must be float32, got {t.dtype}")
+        if shape is not None and tuple(t.shape) != shape:
+            raise BalfHipError(f"{name} must be {list(shape)} for logits {list(logits.shape)}, got {list(t.shape)}")
+        if not t.is_contiguous():
+            raise BalfHipError(f"{name} must be contiguous")
+    dev = logits.device
+    for t, name in ((logits, "logits"), (keypoint_map, "keypoint_map"), (valid_mask, "valid_mask"), (noise, "noise")):
+        if t is not None:
+            require_gpu_tensor(t, name)
+            if t.device != dev:
+                raise BalfHipError(f"{name} is on {t.device}, logits on {dev}")
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    per_image = torch.empty((b,), dtype=torch.float32, device=dev) if want_per_image else None
+    labels = torch.empty((b, hc, wc), dtype=torch.int32, device=dev) if want_labels else None
+    dlogits = torch.empty_like(logits) if want_grad else None
+    ws = _workspace("detector_loss", dev, lib().balf_detector_loss_workspace_bytes(b, hc, wc))
+
+    def ptr(t):
+        return t.data_ptr() if t is not None else None
+
+    with torch.cuda.device(dev):
+        check(lib().balf_detector_loss(logits.data_ptr(), keypoint_map.data_ptr(), ptr(valid_mask), ptr(noise), b, hc, wc,
+                                       loss.data_ptr(), ptr(per_image), ptr(labels), ptr(dlogits), ws.data_ptr(), ws.numel(),
+                                       current_stream_ptr(dev)), "balf_detector_loss")
+    return DetectorLoss(loss, per_image, labels, dlogits)

@@ -1,5 +1,6 @@
 """The inference / evaluation helpers of /root/reference/balf/utils/train_utils.py with every stage on the GPU.
-Training (``train_model``, losses, optimiser; train_utils.py:20-160) is out of scope.
+Training (``train_model``, the network's backward, optimiser; train_utils.py:20-160) is out of scope; the loss it optimises
+is :mod:`balf_amd.loss.loss_function`.
 
 * ``extract_detections`` (train_utils.py:416-454) -- see :mod:`balf_amd.pipeline`.
 * ``compute_repeatability_with_maximum_filter`` (train_utils.py:170-196): window-max NMS of both score maps, common-
@@ -11,6 +12,8 @@ Training (``train_model``, losses, optimiser; train_utils.py:20-160) is out of s
   reference selects checkpoints by (train.py:87,113), pairs forwarded in batches and both of its evaluations (greedy NMS
   and window NMS) run by the batched core from the same forward.  Its tensorboard logging -- and with it
   ``prob_to_score_maps_tensor_batch`` / ``apply_nms_fast`` (train_utils.py:162-168) -- is not ported.
+* ``check_val_anchor_loss``: the quantity ``train_model`` logs as ``total_loss`` (train_utils.py:104-120), evaluated over a
+  validation loader without gradients.  The reference has no such function: it only sees the loss while training.
 """
 from __future__ import annotations
 
@@ -19,6 +22,7 @@ import torch
 
 from ..benchmark_test import _chunked, evaluate, geometry_tools, repeatability_tools
 from ..guard import run_guarded
+from ..loss import loss_function
 from ..pipeline import detect_batch, extract_detections, pad_image_on_device  # noqa: F401
 from . import test_utils
 
@@ -156,3 +160,50 @@ def check_val_repeatability(dataloader, model, device, tb_log, cur_epoch, cell_s
     # leg 0 (greedy): means over all pairs (contiguous copies: the summation order of a 1-D array); leg 1 (window): the LAST pair alone
     return tuple(np.ascontiguousarray(t[k][:, 0]).mean() for k in _MEANS) + \
         tuple(np.asarray([t[k][-1, 1]]).mean() for k in _MEANS)
+
+
+def _anchor_loss_chunk(batches, model, device, grid_size, batch_size):
+    """``batches``: (images_src, images_dst, heatmap_src, heatmap_dst) of some loader batches -> src_anchor_loss +
+    dst_anchor_loss of each: the two float32 losses are added into a float64 device tensor, which is read once at the end
+    -> float64 NumPy array, one value per batch."""
+    out = torch.zeros((len(batches),), dtype=torch.float64, device=device)
+    for i, (images_src, images_dst, heat_src, heat_dst) in enumerate(batches):
+        for images, heat in ((images_src, heat_src), (images_dst, heat_dst)):
+            images = images.to(device)
+            logits = torch.cat([model(images[at:at + batch_size], want_logits=True)["logits"]
+                                for at in range(0, len(images), batch_size)])
+            out[i] += loss_function.detector_loss(heat.to(device).contiguous(), logits, grid_size=grid_size, device=device,
+                                                  noise=False)
+    return out.cpu().numpy()                                    # the one device-to-host read of the chunk
+
+
+@torch.no_grad()
+def check_val_anchor_loss(dataloader, model, device, grid_size=8, batch_size=16, chunk_pairs=64):
+    """The quantity ``train_model`` logs as ``total_loss`` (train_utils.py:104-120), ``src_anchor_loss + dst_anchor_loss``
+    (``loss_function.detector_loss`` of each side's heat map against that side's logits, no valid mask), evaluated on every
+    loader batch and averaged over the batches -> a Python float.  ``dataloader`` yields the 6-tuples of
+    ``check_val_repeatability``; here EVERY element of a batch counts (the loss is a mean over the batch), images are
+    forwarded ``batch_size`` at a time.  ``grid_size`` must be 8 (see ``loss_function.detector_loss``).  ``noise=False``: the
+    lowest channel wins a tie among the key points of a cell, so an epoch's value is reproducible (the reference's training
+    step draws a random tie-break).  The per-batch sums stay on the device as float64 and are read once per ``chunk_pairs``
+    batches; the mean is taken over all of them on the host, so the value does not depend on ``chunk_pairs``.  Each chunk runs
+    under ``guard.run_guarded`` as the other validation loops do: a chunk whose split-f16 forward was flagged is repeated on
+    the fp32 kernels.  An empty loader raises ValueError."""
+    device = torch.device(device)
+    chunk_pairs, batch_size = max(1, int(chunk_pairs)), max(1, int(batch_size))
+    values, batches = [], []
+
+    def flush():
+        args = (list(batches), model, device, grid_size, batch_size)
+        values.append(run_guarded(model, lambda: _anchor_loss_chunk(*args)))
+        batches.clear()
+
+    for batch in dataloader:
+        batches.append(tuple(batch[:4]))
+        if len(batches) == chunk_pairs:
+            flush()
+    if batches:
+        flush()
+    if not values:
+        raise ValueError("check_val_anchor_loss: the dataloader is empty")
+    return float(np.concatenate(values).mean())

@@ -520,6 +520,43 @@ int balf_synth_pairs(const unsigned char *packed_dev, size_t packed_bytes, const
                      int top_k, int patch, float *img_src_dev, float *img_dst_dev, float *heat_src_dev, float *heat_dst_dev,
                      int32_t *dst_max_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
 
+/* ---- detector (anchor) loss: labels, masked cross-entropy and its gradient (balf/loss/loss_function.py:7-26) ------------
+ * balf_detector_loss: the reference's detector_loss for grid_size 8 (the 65-channel head, the only one arch.py supports; the
+ * reference's train_model passes grid_size=16, which its own 65-channel head cannot satisfy), stream-ordered, nothing read
+ * back, capturable, statement by statement.  A cell is one element of the [Hc,Wc] plane; n = Hc * Wc.
+ * Inputs (float32): logits_dev [B,65,Hc,Wc] as balf_forward writes them; keypoint_map_dev [B,1,8Hc,8Wc]; valid_mask_dev
+ * [B,1,8Hc,8Wc] or NULL = all ones (loss_function.py:16; bit-identical to a mask of ones); noise_dev [B,65,Hc,Wc], the random
+ * tie-break the reference draws itself (:13), or NULL = no noise.  The arithmetic is the library's, the random numbers the caller's.
+ *   labels (:8-13)    channel c = dy * 8 + dx of a cell is pixel (8y + dy, 8x + dx) (tensor_op.pixel_shuffle_inv with one input
+ *                     channel).  v_c = fl32(fl32(2 * kp) + noise[c]) for c < 64, the dustbin v_64 = fl32(1 + noise[64]); label =
+ *                     the FIRST index of the maximum (torch.argmax).  One exact doubling and one rounding per value: labels are
+ *                     bit-identical to the reference for every finite input.  Without noise the lowest channel among several
+ *                     key points of a cell wins, a key-point value of 0.5 ties the dustbin and wins, and an empty cell gets 64.
+ *                     NaN inputs are outside the contract.
+ *   cell mask (:16-18) vm = the product of the cell's 64 mask values, multiplied in channel order in float32: exact in any
+ *                     order for masks of zeros and ones, which is the contract; for other values the order is this one and
+ *                     parity with torch.prod is unpinned.
+ *   cross-entropy (:21) ce = lse(logits[:, cell]) - logits[label, cell]; the log-sum-exp subtracts the maximum first (a logit of
+ *                     100 does not overflow): float32 exponentials of (logit - max), summed and finished in float64.
+ *   per image (:23)   num_b = sum(ce * vm), den_b = sum(fl32(vm + 1e-6f)), both in float64 in ONE fixed order that depends on
+ *                     (Hc, Wc) alone -- no floating-point atomics; an image's value does not depend on B or on its place in
+ *                     the batch.  per_image[b] = fl32(num_b / den_b); a fully masked image gives 0 (den = n * 1e-6).
+ *   loss (:24)        fl32(mean_b(num_b / den_b)), the mean in float64 in index order.
+ *   gradient          dlogits[b,c,cell] = fl32((softmax_c - [c == label]) * vm / (den_b * B)): d loss / d logits.
+ * Outputs: loss_dev [1] float32; per_image_dev [B] float32, labels_dev [B,Hc,Wc] int32, dlogits_dev [B,65,Hc,Wc] float32, each
+ * may be NULL and is then neither computed nor written.  The results do not depend on which outputs are requested.
+ * Four launches whatever is requested (cell masks and denominator partial sums; denominators; the pass over the logits, which
+ * are read ONCE and stay in registers between the log-sum-exp and the gradient; the per-image ratios and the loss).  Every
+ * word of the workspace that is read has been written by the same call; nothing needs clearing.  keypoint_map_dev and
+ * valid_mask_dev are read with 16-byte loads when they are 16-byte aligned, with 4-byte loads otherwise (same results).
+ * Limits: 1 <= B <= 65535 (BALF_ERR_ARG); Hc, Wc >= 1 (BALF_ERR_ARG), Hc * Wc <= 2^24 (BALF_ERR_SHAPE); logits_dev,
+ * keypoint_map_dev, loss_dev and workspace_dev must not be NULL and workspace_dev must be 8-byte aligned (BALF_ERR_ARG); a workspace smaller than
+ * balf_detector_loss_workspace_bytes(B, Hc, Wc) (0 for sizes outside the limits) gives BALF_ERR_WORKSPACE. */
+size_t balf_detector_loss_workspace_bytes(int B, int Hc, int Wc);
+int balf_detector_loss(const float *logits_dev, const float *keypoint_map_dev, const float *valid_mask_dev,
+                       const float *noise_dev, int B, int Hc, int Wc, float *loss_dev, float *per_image_dev,
+                       int32_t *labels_dev, float *dlogits_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+
 /* ---- measurement aid (not part of the data path) ---------------------------------------------
  * Between balf_profile_begin() and balf_profile_end() every kernel launch of the library is bracketed
  * by a hipEvent pair on its launch stream.  balf_profile_end() waits for those events and returns,
