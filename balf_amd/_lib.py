@@ -90,6 +90,11 @@ PROTOTYPES = {
                              _vp]),
     "balf_detector_loss_workspace_bytes": (_sz, [_i, _i, _i]),
     "balf_detector_loss": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _fp, _fp, _vp, _fp, _vp, _sz, _vp]),
+    "balf_head_train_workspace_bytes": (_sz, [C.c_long]),
+    "balf_head_train_saved_bytes": (_sz, [C.c_long]),
+    "balf_head_train_forward": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, C.c_double, _i, _fp, _fp, _fp, _fp, _fp,
+                                    C.c_double, _vp, _vp, _sz, _vp]),
+    "balf_head_train_backward": (_i, [_fp, _fp, _fp, _fp, _fp, _vp, _i, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _sz, _vp]),
     "balf_profile_num_slots": (_i, []),
     "balf_profile_slot_name": (C.c_char_p, [_i]),
     "balf_profile_begin": (_i, []),

@@ -249,6 +249,41 @@ class MLP_MA_DECODER(nn.Module):
             raise ValueError(f"H and W must be multiples of 64 (pad with mod_padding_symmetric), got {h}x{w}")
         return self._forward("f32", (b, h, w), x.contiguous().float(), b, h, w, want_logits)
 
+    def encode(self, x: torch.Tensor, chunk=None) -> torch.Tensor:
+        """The frozen encoder's output: ``x2`` of down4, the input of ``down4.conv2``, [B,H/8,W/8,256] float32 NHWC, detached --
+        what ``model.head_train.TrainableHead`` trains on.  The existing forward runs with ``want_logits=False`` on ``chunk``
+        images at a time (default and upper bound: ``balf_forward_micro_batch``, so that the whole chunk is resident in the
+        workspace) and the stage-4 view is taken after each chunk.  The encoder has no training-mode layer: this works whatever
+        ``self.training`` says and leaves the flag alone.  A split-f16 forward is guarded as every forward is; a caller that
+        uses the features before the guard has looked calls ``fp16_guard_check`` and encodes again on a flag OR when
+        ``effective_precision`` became 'fp32' meanwhile (a later forward's look may already have consumed the flag:
+        ``utils.train_utils.train_head`` does both).  The stage-4 view reads the same fp32 buffers on either path
+        (stage_view.hip), so the precision code passed below cannot misread a chunk whose verdict flipped in flight."""
+        if x.dim() != 4 or x.shape[1] != 3:                     # (forward's own checks, in forward's order)
+            raise ValueError(f"expected [B,3,H,W], got {tuple(x.shape)}")
+        if not x.is_cuda:
+            raise BalfHipError("balf_amd has no CPU path: move the model and the input to the GPU")
+        b, _, h, w = x.shape
+        if h % 64 or w % 64:
+            raise ValueError(f"H and W must be multiples of 64 (pad with mod_padding_symmetric), got {h}x{w}")
+        if b < 1:
+            raise ValueError("encode: an empty batch")
+        x = x.contiguous().float()
+        l = lib()
+        mb = l.balf_forward_micro_batch(b, h, w)
+        chunk = mb if chunk is None else max(1, min(int(chunk), mb))
+        out = torch.empty((b, h // 8, w // 8, 256), dtype=torch.float32, device=x.device)
+        with torch.no_grad():
+            for at in range(0, b, chunk):
+                nb = min(chunk, b - at)
+                self._forward("f32", (nb, h, w), x[at:at + nb], nb, h, w, False)
+                ws = ops._workspace("forward", x.device, l.balf_forward_workspace_bytes(nb, h, w))
+                with torch.cuda.device(x.device):
+                    check(l.balf_forward_stage_view(self._code_of(self.effective_precision), ws.data_ptr(), ws.numel(), nb, h, w, 4,
+                                                    out[at:at + nb].data_ptr(), _lib.current_stream_ptr(x.device)),
+                          "balf_forward_stage_view")
+        return out
+
     def _forward(self, kind, dims, src, b, hp, wp, want_logits):
         """The body of ``forward`` / ``forward_u8`` on a checked input: ``dims`` are the kernel's own (see _launch), ``hp x wp``
         the padded size of the outputs.  The status block of a split-f16 call and what happens when it is raised:

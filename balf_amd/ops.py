@@ -572,3 +572,113 @@ def detector_loss(logits: torch.Tensor, keypoint_map: torch.Tensor, valid_mask=N
                                        loss.data_ptr(), ptr(per_image), ptr(labels), ptr(dlogits), ws.data_ptr(), ws.numel(),
                                        current_stream_ptr(dev)), "balf_detector_loss")
     return DetectorLoss(loss, per_image, labels, dlogits)
+
+
+class HeadTrainForward(NamedTuple):
+    logits: torch.Tensor                      # [B,65,Hc,Wc] float32
+    prob: Optional[torch.Tensor]              # [B,8Hc,8Wc] float32
+    saved: torch.Tensor                       # opaque uint8 block for head_train_backward
+
+
+class HeadTrainBackward(NamedTuple):
+    dw2: torch.Tensor                         # [256,256]
+    db2: torch.Tensor                         # [256]
+    dwd: torch.Tensor                         # [65,256]
+    dbd: torch.Tensor                         # [65]
+    dgamma: torch.Tensor                      # [65]
+    dbeta: torch.Tensor                       # [65]
+    dx2: Optional[torch.Tensor]               # [B,Hc,Wc,256]
+
+
+_HEAD_PARAM_SHAPES = {"w2": (256, 256), "b2": (256,), "wd": (65, 256), "bd": (65,), "gamma": (65,), "beta": (65,),
+                      "running_mean": (65,), "running_var": (65,), "stats": (2, 65)}
+
+
+def _head_train_checks(x2, named):
+    """Shapes, dtypes and contiguity from the tensors' metadata, then the devices: a wrong call is refused before any device is
+    touched.  ``named``: (tensor or None, name, shape) triples, x2 first.  -> (B, Hc, Wc)."""
+    if x2.dim() != 4 or x2.shape[3] != 256:
+        raise BalfHipError(f"x2 must be [B,Hc,Wc,256] (the stage-4 activation, NHWC), got {tuple(x2.shape)}")
+    b, hc, wc, _ = x2.shape
+    if not 1 <= b <= 65535 or hc < 1 or wc < 1 or not 2 <= b * hc * wc <= 1 << 24:
+        raise BalfHipError(f"head_train: 1 <= B <= 65535 and 2 <= B * Hc * Wc <= 2^24, got {tuple(x2.shape)}")
+    for t, name, shape in named:
+        if t is None:
+            continue
+        if t.dtype != torch.float32 and name != "saved":
+            raise BalfHipError(f"{name} must be float32, got {t.dtype}")
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise BalfHipError(f"{name} must be {list(shape)}, got {list(t.shape)}")
+        if not t.is_contiguous():
+            raise BalfHipError(f"{name} must be contiguous")
+    for t, name, _ in named:
+        if t is not None:
+            require_gpu_tensor(t, name)
+            if t.device != x2.device:
+                raise BalfHipError(f"{name} is on {t.device}, x2 on {x2.device}")
+    return b, hc, wc
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def head_train_forward(x2: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, wd: torch.Tensor, bd: torch.Tensor,
+                       gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5, stats=None, want_prob=True,
+                       running_mean=None, running_var=None, momentum: float = 0.1, saved=None) -> HeadTrainForward:
+    """down4.conv2 -> ReLU -> detector_head.dense -> BatchNorm2d on ``x2`` [B,Hc,Wc,256] (balf_head_train_forward in
+    include/balf_hip.h).  ``stats`` None: batch statistics (training mode), and ``running_mean`` / ``running_var`` [65], when
+    given, are updated in place by the kernel; ``stats`` [2,65] (mean, variance): normalise with them (eval mode).  All tensors
+    float32 and contiguous on one GPU.  ``want_prob`` may be a contiguous float32 [B,8Hc,8Wc] tensor to write into.  ``saved``: a
+    uint8 block to reuse (at least balf_head_train_saved_bytes), else allocated."""
+    s = _HEAD_PARAM_SHAPES
+    prob = want_prob if isinstance(want_prob, torch.Tensor) else None
+    prob_shape = (x2.shape[0], 8 * x2.shape[1], 8 * x2.shape[2]) if x2.dim() == 4 else None
+    b, hc, wc = _head_train_checks(x2, ((x2, "x2", None), (prob, "prob", prob_shape), (w2, "w2", s["w2"]), (b2, "b2", s["b2"]),
+                                        (wd, "wd", s["wd"]),
+                                        (bd, "bd", s["bd"]), (gamma, "gamma", s["gamma"]), (beta, "beta", s["beta"]),
+                                        (stats, "stats", s["stats"]), (running_mean, "running_mean", s["running_mean"]),
+                                        (running_var, "running_var", s["running_var"]), (saved, "saved", None)))
+    dev, n = x2.device, b * hc * wc
+    l = lib()
+    need = l.balf_head_train_saved_bytes(n)
+    if saved is None:
+        saved = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif saved.dtype != torch.uint8 or saved.numel() < need:
+        raise BalfHipError(f"saved must be a uint8 tensor of at least {need} bytes")
+    logits = torch.empty((b, 65, hc, wc), dtype=torch.float32, device=dev)
+    if prob is None and want_prob:
+        prob = torch.empty((b, 8 * hc, 8 * wc), dtype=torch.float32, device=dev)
+    ws = _workspace("head_train", dev, l.balf_head_train_workspace_bytes(n))
+    with torch.cuda.device(dev):
+        check(l.balf_head_train_forward(x2.data_ptr(), w2.data_ptr(), b2.data_ptr(), wd.data_ptr(), bd.data_ptr(),
+                                        gamma.data_ptr(), beta.data_ptr(), b, hc, wc, float(eps), 0 if stats is None else 1,
+                                        _ptr(stats), logits.data_ptr(), _ptr(prob), _ptr(running_mean), _ptr(running_var),
+                                        float(momentum), saved.data_ptr(), ws.data_ptr(), ws.numel(), current_stream_ptr(dev)),
+              "balf_head_train_forward")
+    return HeadTrainForward(logits, prob, saved)
+
+
+def head_train_backward(dlogits: torch.Tensor, x2: torch.Tensor, w2: torch.Tensor, wd: torch.Tensor, gamma: torch.Tensor,
+                        saved: torch.Tensor, want_dx2=False) -> HeadTrainBackward:
+    """The backward of ``head_train_forward`` in training mode (balf_head_train_backward): ``dlogits`` [B,65,Hc,Wc] and the
+    ``saved`` block of that forward -> the six parameter gradients and, with ``want_dx2``, the gradient of ``x2``
+    (``want_dx2`` may be a contiguous float32 tensor of x2's shape to write into)."""
+    s = _HEAD_PARAM_SHAPES
+    dx2 = want_dx2 if isinstance(want_dx2, torch.Tensor) else None
+    shape = (x2.shape[0], 65, x2.shape[1], x2.shape[2]) if x2.dim() == 4 else None
+    b, hc, wc = _head_train_checks(x2, ((x2, "x2", None), (dlogits, "dlogits", shape), (w2, "w2", s["w2"]), (wd, "wd", s["wd"]),
+                                        (gamma, "gamma", s["gamma"]), (saved, "saved", None), (dx2, "dx2", tuple(x2.shape))))
+    dev, n = x2.device, b * hc * wc
+    l = lib()
+    if saved.dtype != torch.uint8 or saved.numel() < l.balf_head_train_saved_bytes(n):
+        raise BalfHipError("saved must be the uint8 block that head_train_forward returned for this shape")
+    if dx2 is None and want_dx2:
+        dx2 = torch.empty_like(x2)
+    out = [torch.empty(s[k], dtype=torch.float32, device=dev) for k in ("w2", "b2", "wd", "bd", "gamma", "beta")]
+    ws = _workspace("head_train", dev, l.balf_head_train_workspace_bytes(n))
+    with torch.cuda.device(dev):
+        check(l.balf_head_train_backward(dlogits.data_ptr(), x2.data_ptr(), w2.data_ptr(), wd.data_ptr(), gamma.data_ptr(),
+                                         saved.data_ptr(), b, hc, wc, *[t.data_ptr() for t in out], _ptr(dx2), ws.data_ptr(),
+                                         ws.numel(), current_stream_ptr(dev)), "balf_head_train_backward")
+    return HeadTrainBackward(*out, dx2)

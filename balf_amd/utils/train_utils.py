@@ -1,6 +1,7 @@
 """The inference / evaluation helpers of /root/reference/balf/utils/train_utils.py with every stage on the GPU.
-Training (``train_model``, the network's backward, optimiser; train_utils.py:20-160) is out of scope; the loss it optimises
-is :mod:`balf_amd.loss.loss_function`.
+Of training (``train_model``, train_utils.py:79-160) the head's part is here: ``train_head`` fits the trainable tail on the
+features of the frozen encoder (:mod:`balf_amd.model.head_train`) against :mod:`balf_amd.loss.loss_function`; the encoder's
+backward is out of scope, optimisers are torch's.
 
 * ``extract_detections`` (train_utils.py:416-454) -- see :mod:`balf_amd.pipeline`.
 * ``compute_repeatability_with_maximum_filter`` (train_utils.py:170-196): window-max NMS of both score maps, common-
@@ -14,6 +15,7 @@ is :mod:`balf_amd.loss.loss_function`.
   ``prob_to_score_maps_tensor_batch`` / ``apply_nms_fast`` (train_utils.py:162-168) -- is not ported.
 * ``check_val_anchor_loss``: the quantity ``train_model`` logs as ``total_loss`` (train_utils.py:104-120), evaluated over a
   validation loader without gradients.  The reference has no such function: it only sees the loss while training.
+* ``train_head``: one epoch of ``train_model``'s step (train_utils.py:104-124) for the head alone, encoder frozen.
 """
 from __future__ import annotations
 
@@ -207,3 +209,71 @@ def check_val_anchor_loss(dataloader, model, device, grid_size=8, batch_size=16,
     if not values:
         raise ValueError("check_val_anchor_loss: the dataloader is empty")
     return float(np.concatenate(values).mean())
+
+
+def _guarded_features(model, encode_chunk):
+    """``encode_chunk()`` -> its features, final with respect to the split-f16 guard: after the chunk's forwards are enqueued
+    the guard is asked with a wait (``fp16_guard_check(synchronize=True)``), and the chunk is encoded again, ONCE, when that
+    look finds a flag or when the checkpoint was switched to the fp32 kernels while the chunk was in flight.  The second
+    condition is ``guard.run_guarded``'s: ``fp16_guard_check`` says True only when THIS look finds the flag, and a chunk is many
+    forwards, each of which starts with a look at the earlier ones (and a full ring forces one) -- a flag consumed there sets
+    the verdict, cannot repair a score map nobody holds any more, and leaves the flagged forward's features as they are.  The
+    repeat runs on the fp32 kernels, which set no flag."""
+    on_fp32 = getattr(model, "effective_precision", None) == "fp32"
+    features = encode_chunk()
+    flagged = model.fp16_guard_check(synchronize=True)
+    if flagged or (not on_fp32 and getattr(model, "effective_precision", None) == "fp32"):
+        features = encode_chunk()
+    return features
+
+
+def train_head(dataloader, model, head, optimizer, device, grid_size=8, chunk_batches=16, noise=None) -> float:
+    """One epoch of the reference's training step (train_utils.py:104-124) for the trainable tail alone: ``model``'s encoder is
+    frozen and runs on the forward kernels (``model.encode``), ``head`` (``model.head_train.TrainableHead``) runs forward in
+    training mode and backward on the library, ``optimizer`` (torch's, over ``head.parameters()``) steps once per loader batch.
+    ``dataloader`` yields the reference's 6-tuples ``(images_src, images_dst, heatmap_src, heatmap_dst, h_src_2_dst,
+    h_dst_2_src)``; images ``[B,3,H,W]`` with H, W multiples of 64.  Per chunk of ``chunk_batches`` batches: every source and
+    destination batch is encoded, the split-f16 guard is asked (``fp16_guard_check(synchronize=True)``), and on a flag -- found
+    by that look, or consumed by a forward of the chunk itself, which shows as ``effective_precision`` having become 'fp32' --
+    the chunk is encoded again, once: the checkpoint is on the fp32 kernels by then.  Only then the head steps run: ``loss =
+    detector_loss(src) + detector_loss(dst)``, ``zero_grad``, ``backward``, ``step``.  The features do not depend on the head's
+    updates, so the retry needs no snapshot and never repeats an optimiser step.  The per-batch losses stay on the device and
+    are read once per chunk; the return value is their mean, taken on the host.  ``noise`` as in
+    ``loss_function.detector_loss`` (None draws the reference's random tie-break).  ``grid_size`` must be 8; an empty loader
+    raises ValueError.  ``head`` is left in training mode; ``head.commit(model)`` writes the result back."""
+    if grid_size != loss_function.GRID_SIZE:
+        raise ValueError(f"train_head: only grid_size={loss_function.GRID_SIZE} (the 65-channel head) is supported, got {grid_size}")
+    device = torch.device(device)
+    chunk_batches = max(1, int(chunk_batches))
+    values, batches = [], []
+
+    def encode_chunk():
+        return [(model.encode(b[0].to(device)), model.encode(b[1].to(device))) for b in batches]
+
+    def flush():
+        features = _guarded_features(model, encode_chunk)
+        losses = torch.zeros((len(batches),), dtype=torch.float32, device=device)
+        for i, (feat_src, feat_dst) in enumerate(features):
+            loss = None
+            for feat, heat in ((feat_src, batches[i][2]), (feat_dst, batches[i][3])):
+                logits = head(feat, want_prob=False)["logits"]
+                side = loss_function.detector_loss(heat.to(device).contiguous(), logits, grid_size=grid_size, device=device,
+                                                   noise=noise)
+                loss = side if loss is None else loss + side
+            optimizer.zero_grad()
+            loss.backward()
+            optimizer.step()
+            losses[i] = loss.detach()
+        values.append(losses.cpu().numpy())                     # the one device-to-host read of the chunk
+        batches.clear()
+
+    head.train()
+    for batch in dataloader:
+        batches.append(tuple(batch[:4]))
+        if len(batches) == chunk_batches:
+            flush()
+    if batches:
+        flush()
+    if not values:
+        raise ValueError("train_head: the dataloader is empty")
+    return float(np.concatenate(values).astype(np.float64).mean())

@@ -557,6 +557,55 @@ int balf_detector_loss(const float *logits_dev, const float *keypoint_map_dev, c
                        const float *noise_dev, int B, int Hc, int Wc, float *loss_dev, float *per_image_dev,
                        int32_t *labels_dev, float *dlogits_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
 
+/* ---- the trainable tail of the detector: training-mode head and its backward ------------------------------
+ * down4.conv2 (Linear 256 -> 256) -> ReLU -> detector_head.dense (Linear 256 -> 65) -> detector_head.norm (BatchNorm2d with
+ * BATCH statistics), and the backward from dlogits (balf_detector_loss writes it) to the six parameter gradients and to the
+ * gradient of the stage-4 activation x2.  N = B * Hc * Wc pixels.  X = x2_dev [N,256] float32 NHWC, what
+ * balf_forward_stage_view(stage = 4) writes.  The parameters are plain float32 device tensors in PyTorch layout, NOT the packed
+ * blob (they change every step): w2_dev [256,256], b2_dev [256], wd_dev [65,256], bd_dev [65], gamma_dev, beta_dev [65].
+ *   forward    h = X W2^T + b2;  a = max(h, 0);  z = a Wd^T + bd  [N,65]
+ *              mu_c = mean_N z, var_c = the biased variance, both from float64 sums of z and z * z;  r_c = 1 / sqrt(var_c + eps)
+ *              in float64;  xhat = fl32((z - mu) * r) (float64 inside);  logits[b,c,y,x] = fma(gamma_c, xhat, beta_c), NCHW
+ *              [B,65,Hc,Wc] as balf_forward writes them.
+ *              prob_dev (NULL ok) [B,8Hc,8Wc]: softmax over the 65 logits (maximum taken out), dustbin dropped, pixel-shuffled.
+ *              running_mean_dev / running_var_dev (each NULL ok) [65]: rm <- (1 - m) rm + m mu, rv <- (1 - m) rv + m var N / (N - 1),
+ *              evaluated in float64, m = momentum.
+ *              use_stats = 1: normalise with stats_in_dev [2,65] (mean, then variance) instead of the batch's -- the eval mode of
+ *              the same kernels: no statistics pass, no running-statistics update, and no backward is defined for it.
+ *   backward   g = dlogits_dev [B,65,Hc,Wc]:  dbeta = sum_N g,  dgamma = sum_N g xhat  (float64, xhat = (z - mu) r kept in float64:
+ *              the three terms of dz cancel almost completely when N is small),
+ *              dz = gamma r (g - dbeta / N - xhat dgamma / N)  (float64 inside, stored as float32)
+ *              dWd = dz^T a,  dbd = sum dz,  da = dz Wd,  dh = da [h > 0] (0 at h == 0, as torch),  dW2 = dh^T X,  db2 = sum dh,
+ *              dx2 = dh W2  (dx2_dev NULL ok).
+ * saved_dev: an opaque caller-owned block of balf_head_train_saved_bytes(N) bytes that the forward writes and the backward of
+ * the same (B, Hc, Wc) reads: a [N,256], z itself, channel-major [65,N] (never recomputed from the logits: gamma_c may be 0),
+ * and mu, r as float64.
+ * Arithmetic: the six matrix products run on v_mfma_f32_16x16x4_f32, exact float32 fma chains with k ascending; the 65-wide
+ * side is padded inside the kernel (pad elements are never loaded, never stored, and enter a tile as 0).  No floating-point
+ * atomics: the statistics, dbeta, dgamma and dbd are float64 partial sums per workgroup of 1024 pixels, added per channel by one
+ * wave in a fixed order; db2 likewise over blocks of rows; dW2 and dWd are summed over S = ceil(N / rows) slices of the pixels,
+ * rows = 256 * ceil(ceil(N / 256) / 64) (S <= 64), each slice an fma chain into its own slab of the workspace, the slabs added
+ * in float64 in slice order.  Every order is a function of N alone: two calls on the same input give bit-identical outputs.
+ * An output that is not requested (prob, the running statistics, dx2) is neither computed nor written, and the others do not
+ * change with that.  Stream-ordered, nothing synchronised or read back, capturable; every word of the workspace and of saved
+ * that is read was written before, by the same call or (saved) by the forward.
+ * Launches: forward 5 (4 with use_stats), backward 12 (13 with dx2).
+ * Limits: 1 <= B <= 65535, Hc, Wc >= 1 and N >= 2 (BALF_ERR_ARG: one value per channel has no variance, torch raises there
+ * too); N <= 2^24 (BALF_ERR_SHAPE); the required pointers (everything not marked NULL ok; stats_in_dev with use_stats) must not
+ * be NULL, saved_dev and workspace_dev must be 8-byte aligned, eps >= 0 (BALF_ERR_ARG); a workspace smaller than
+ * balf_head_train_workspace_bytes(N) gives BALF_ERR_WORKSPACE.  Both size queries return 0 for N outside [2, 2^24]. */
+size_t balf_head_train_workspace_bytes(long N);
+size_t balf_head_train_saved_bytes(long N);
+int balf_head_train_forward(const float *x2_dev, const float *w2_dev, const float *b2_dev, const float *wd_dev,
+                            const float *bd_dev, const float *gamma_dev, const float *beta_dev, int B, int Hc, int Wc, double eps,
+                            int use_stats, const float *stats_in_dev, float *logits_dev, float *prob_dev, float *running_mean_dev,
+                            float *running_var_dev, double momentum, void *saved_dev, void *workspace_dev, size_t workspace_bytes,
+                            void *stream);
+int balf_head_train_backward(const float *dlogits_dev, const float *x2_dev, const float *w2_dev, const float *wd_dev,
+                             const float *gamma_dev, const void *saved_dev, int B, int Hc, int Wc, float *dw2_dev, float *db2_dev,
+                             float *dwd_dev, float *dbd_dev, float *dgamma_dev, float *dbeta_dev, float *dx2_dev,
+                             void *workspace_dev, size_t workspace_bytes, void *stream);
+
 /* ---- measurement aid (not part of the data path) ---------------------------------------------
  * Between balf_profile_begin() and balf_profile_end() every kernel launch of the library is bracketed
  * by a hipEvent pair on its launch stream.  balf_profile_end() waits for those events and returns,
