@@ -1,0 +1,476 @@
+// balf_rcab_train_forward / balf_rcab_train_backward (include/balf_hip.h): stage 4's ResidualChannelAttentionBlock in training
+// form,  y -> LayerNorm -> conv1 (Linear 256 -> 256) -> LeakyReLU(0.2) -> conv2 (Linear 256 -> 256) -> squeeze-excite scale,
+// x2 = t * s_image + r,  and its backward from dx2 to the ten parameter gradients and dy.  N = B * Hc * Wc pixels.
+//
+// Four kinds of kernels:
+//   * gemm_kernel (train_gemm.h, shared with head_train.hip) for the six 256 x 256 products; dwc1 / dwc2 through the slab split
+//     and the float64 slab sum.
+//   * LayerNorm row kernels: a pixel's 256 channels on one wave, four consecutive channels per lane; every sum over the channels
+//     is (v0 + v1) + (v2 + v3) on the lane and then the xor butterfly 32, 16, .. 1, which leaves the same bits on every lane.  The
+//     variance is taken from the centred values.  The backward recomputes xhat = (y - mean) * rstd with the forward's own
+//     operations from the saved (mean, rstd), so it is the forward's xhat bit for bit, ln_g = 0 or not.
+//   * column kernels, a channel per thread over a block of pixel rows, float64 partial sums per workgroup: over the rows of ONE
+//     image (img_sum_kernel: the SE mean m_i and ds_i = sum g t; the grid is (row blocks of an image, image), so no block ever
+//     holds rows of two images, wherever an image starts), and over all rows (dt_kernel, col_sum_kernel, ln_bwd_kernel).
+//   * the squeeze-excite arithmetic in float64: se_fwd_kernel / se_bwd_kernel, a workgroup per image, and se_wgrad_kernel, a
+//     thread per element of dws0 / dws2 / dbs0 / dbs2 that walks the images in image order.
+// No floating-point atomics; every order is a function of (B, Hc, Wc) alone.
+// saved: n, a, t [N,256], (mean, rstd) [N,2], and per image m [256], e [64], s [256] as float64 plus s as float32.
+#include "train_gemm.h"
+
+namespace balf {
+namespace {
+
+constexpr int kC = 256;                     // channels
+constexpr int kH = 64;                      // squeeze-excite hidden units
+constexpr int kMaxN = 1 << 24;              // pixels: up to 2^32 elements in a [N,256] matrix, indexed in size_t
+constexpr int kLnFwdPix = 16;               // pixels per workgroup of the LayerNorm forward (four per wave)
+constexpr float kLnEps = 1e-5f;
+constexpr int kMaxImgParts = 1024;          // row blocks per image of img_sum_kernel
+
+struct Layout {
+    int B, hw, N, S, rows, col_rows, PC;    // S slices of rows pixels; PC blocks of col_rows rows over all pixels
+    int img_rows, PI;                       // PI blocks of img_rows rows per image
+    // saved
+    float *n, *a, *t, *stat, *sf;           // stat [N][2]: mean, rstd; sf [B][256]
+    double *m, *e, *s;                      // [B][256], [B][64], [B][256]
+    // workspace
+    double *img_part;                       // [B][PI][256]
+    double *col_part;                       // [2][PC][256]
+    double *dq, *de;                        // [B][256], [B][64]
+    float *dmh;                             // [B][256]: dm / (Hc * Wc)
+    float *dt, *dh, *slab;                  // dt [N,256], later dn; dh [N,256]; slab [S][256][256]
+};
+
+Layout make_layout(int B, int hw, char *saved, char *work, size_t *saved_bytes, size_t *work_bytes) {
+    Layout l{};
+    l.B = B; l.hw = hw;
+    const int N = l.N = B * hw;
+    l.rows = rows_per_slice(N);
+    l.S = balf_ceil_div(N, l.rows);
+    l.col_rows = l.rows / 16 > 64 ? l.rows / 16 : 64;       // 64 rows per workgroup, or what keeps PC at 1024
+    l.PC = balf_ceil_div(N, l.col_rows);
+    const int per = balf_ceil_div(hw, kMaxImgParts);
+    l.img_rows = per > 64 ? per : 64;
+    l.PI = balf_ceil_div(hw, l.img_rows);
+    const size_t act = (size_t)N * kC * sizeof(float);
+    WorkspaceCursor sv{saved, 0};
+    l.n = sv.take<float>(act);
+    l.a = sv.take<float>(act);
+    l.t = sv.take<float>(act);
+    l.stat = sv.take<float>((size_t)N * 2 * sizeof(float));
+    l.m = sv.take<double>((size_t)B * kC * sizeof(double));
+    l.e = sv.take<double>((size_t)B * kH * sizeof(double));
+    l.s = sv.take<double>((size_t)B * kC * sizeof(double));
+    l.sf = sv.take<float>((size_t)B * kC * sizeof(float));
+    if (saved_bytes) *saved_bytes = sv.used;
+    WorkspaceCursor ws{work, 0};
+    l.img_part = ws.take<double>((size_t)B * l.PI * kC * sizeof(double));
+    l.col_part = ws.take<double>((size_t)2 * l.PC * kC * sizeof(double));
+    l.dq = ws.take<double>((size_t)B * kC * sizeof(double));
+    l.de = ws.take<double>((size_t)B * kH * sizeof(double));
+    l.dmh = ws.take<float>((size_t)B * kC * sizeof(float));
+    l.dt = ws.take<float>(act);
+    l.dh = ws.take<float>(act);
+    l.slab = ws.take<float>((size_t)l.S * kC * kC * sizeof(float));
+    if (work_bytes) *work_bytes = ws.used;
+    return l;
+}
+
+__device__ __forceinline__ gf4 ld4(const float *p) { return *reinterpret_cast<const gf4 *>(p); }
+__device__ __forceinline__ void st4(float *p, gf4 v) { *reinterpret_cast<gf4 *>(p) = v; }
+// (vec, uniform: the array is 16-byte aligned; else four 4-byte accesses)
+__device__ __forceinline__ gf4 ld4(const float *p, bool vec) { return vec ? ld4(p) : gf4{p[0], p[1], p[2], p[3]}; }
+__device__ __forceinline__ void st4(float *p, gf4 v, bool vec) {
+    if (vec) { st4(p, v); return; }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) p[j] = v[j];
+}
+// the sum over a pixel's 256 channels, four of them on each lane -> every lane
+__device__ __forceinline__ float chan_sum(gf4 v) { return wave_sum((v[0] + v[1]) + (v[2] + v[3])); }
+
+// ---- LayerNorm ----------------------------------------------------------------------------------------------------------------
+// a wave per pixel: n = xhat * ln_g + ln_b, stat = (mean, rstd)
+__global__ __launch_bounds__(256) void ln_fwd_kernel(const float *y, const float *ln_g, const float *ln_b, int N, float *n_out,
+                                                     float *stat) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const gf4 gg = ld4(ln_g + 4 * lane), bb = ld4(ln_b + 4 * lane);
+#pragma unroll
+    for (int i = 0; i < kLnFwdPix / 4; ++i) {
+        const int p = blockIdx.x * kLnFwdPix + 4 * i + wave;   // (uniform in the wave)
+        if (p >= N) break;
+        const size_t at = (size_t)p * kC + 4 * lane;
+        const gf4 v = ld4(y + at);
+        const float mean = chan_sum(v) * (1.0f / kC);
+        const gf4 d = v - mean;
+        const float var = chan_sum(d * d) * (1.0f / kC);
+        const float rstd = 1.0f / sqrtf(var + kLnEps);
+        const gf4 xh = d * rstd;
+        gf4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = fmaf(xh[j], gg[j], bb[j]);
+        st4(n_out + at, o);
+        if (lane == 0) { stat[2 * (size_t)p] = mean; stat[2 * (size_t)p + 1] = rstd; }
+    }
+}
+
+struct LnBwdArgs {
+    int N, rows;
+    bool vec_g, vec_dy;                     // g / dy is 16-byte aligned
+    const float *dn, *y, *stat, *ln_g, *g;
+    float *dy;
+    double *part_g, *part_b;                // [PC][256] each
+};
+
+// rows [blockIdx.x * rows, ..) of the pixels, a wave per pixel (wave w takes every fourth row from w): the float64 partials of
+// dln_g = sum dn * xhat and dln_b = sum dn, the four waves added in wave order; with WANT_DY
+// dy = g + rstd * (u - mean_c u - xhat * mean_c(u * xhat)), u = dn * ln_g
+template <bool WANT_DY>
+__global__ __launch_bounds__(256) void ln_bwd_kernel(LnBwdArgs a) {
+    __shared__ double s_part[2][4][kC];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int r0 = blockIdx.x * a.rows, r1 = min(a.N, r0 + a.rows);
+    const gf4 gg = ld4(a.ln_g + 4 * lane);
+    double sg[4] = {0.0, 0.0, 0.0, 0.0}, sb[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int p = r0 + wave; p < r1; p += 4) {
+        const size_t at = (size_t)p * kC + 4 * lane;
+        const gf4 dn = ld4(a.dn + at), v = ld4(a.y + at);
+        const float mean = a.stat[2 * (size_t)p], rstd = a.stat[2 * (size_t)p + 1];
+        const gf4 d = v - mean;
+        const gf4 xh = d * rstd;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            sg[j] += (double)dn[j] * (double)xh[j];
+            sb[j] += (double)dn[j];
+        }
+        if constexpr (WANT_DY) {
+            const gf4 u = dn * gg;
+            const float mu = chan_sum(u) * (1.0f / kC), mux = chan_sum(u * xh) * (1.0f / kC);
+            const gf4 gv = ld4(a.g + at, a.vec_g);
+            gf4 o;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j] = gv[j] + rstd * ((u[j] - mu) - xh[j] * mux);
+            st4(a.dy + at, o, a.vec_dy);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        s_part[0][wave][4 * lane + j] = sg[j];
+        s_part[1][wave][4 * lane + j] = sb[j];
+    }
+    __syncthreads();
+    const int c = threadIdx.x;
+    a.part_g[(size_t)blockIdx.x * kC + c] = ((s_part[0][0][c] + s_part[0][1][c]) + s_part[0][2][c]) + s_part[0][3][c];
+    a.part_b[(size_t)blockIdx.x * kC + c] = ((s_part[1][0][c] + s_part[1][1][c]) + s_part[1][2][c]) + s_part[1][3][c];
+}
+
+// ---- sums over the pixels of one image ----------------------------------------------------------------------------------------
+// part[image][block][c] = float64 sum over rows [block * rows, ..) OF THE IMAGE of x[row][c] (PROD: x * w, the product in
+// float64, where it is exact); grid (PI, B), a column per thread
+template <bool PROD>
+__global__ __launch_bounds__(kC) void img_sum_kernel(const float *x, const float *w, int hw, int rows, double *part) {
+    const int img = blockIdx.y;
+    const int o0 = blockIdx.x * rows, o1 = min(hw, o0 + rows);
+    const size_t base = (size_t)img * (size_t)hw;
+    double s[4] = {0.0, 0.0, 0.0, 0.0};                      // row o goes to chain (o - o0) % 4: four loads in flight
+    auto term = [&](int o) {
+        const size_t at = (base + o) * kC + threadIdx.x;
+        return PROD ? (double)x[at] * (double)w[at] : (double)x[at];
+    };
+    int o = o0;
+    for (; o + 4 <= o1; o += 4) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) s[i] += term(o + i);
+    }
+    for (int i = 0; o < o1; ++o, ++i) s[i] += term(o);
+    part[((size_t)img * gridDim.x + blockIdx.x) * kC + threadIdx.x] = (s[0] + s[1]) + (s[2] + s[3]);
+}
+
+struct SeArgs {
+    int hw, PI;
+    const double *img_part;
+    const float *ws0, *bs0, *ws2, *bs2;
+    double *m, *e, *s, *dq, *de;
+    float *sf, *dmh;
+};
+
+__device__ __forceinline__ double img_part_sum(const SeArgs &a, int img, int c) {
+    double v = 0.0;
+    for (int k = 0; k < a.PI; ++k) v += a.img_part[((size_t)img * a.PI + k) * kC + c];
+    return v;
+}
+
+// a workgroup per image: m = mean t, e = relu(m ws0^T + bs0), s = sigmoid(e ws2^T + bs2), float64, k ascending
+__global__ __launch_bounds__(kC) void se_fwd_kernel(SeArgs a) {
+    __shared__ double s_m[kC], s_e[kH];
+    const int img = blockIdx.x, c = threadIdx.x;
+    const double m = img_part_sum(a, img, c) / (double)a.hw;
+    s_m[c] = m;
+    a.m[(size_t)img * kC + c] = m;
+    __syncthreads();
+    if (c < kH) {
+        double v = 0.0;
+        for (int k = 0; k < kC; ++k) v += s_m[k] * (double)a.ws0[c * kC + k];
+        v += (double)a.bs0[c];
+        v = v > 0.0 ? v : 0.0;
+        s_e[c] = v;
+        a.e[(size_t)img * kH + c] = v;
+    }
+    __syncthreads();
+    double v = 0.0;
+    for (int j = 0; j < kH; ++j) v += s_e[j] * (double)a.ws2[c * kH + j];
+    v += (double)a.bs2[c];
+    const double s = 1.0 / (1.0 + exp(-v));
+    a.s[(size_t)img * kC + c] = s;
+    a.sf[(size_t)img * kC + c] = (float)s;
+}
+
+// a workgroup per image: ds = sum g t, dq = ds s (1 - s), de = (dq ws2) [e > 0], dm = de ws0 -> dq, de, dm / hw
+__global__ __launch_bounds__(kC) void se_bwd_kernel(SeArgs a) {
+    __shared__ double s_q[kC], s_e[kH];
+    const int img = blockIdx.x, c = threadIdx.x;
+    const double s = a.s[(size_t)img * kC + c];
+    const double dq = img_part_sum(a, img, c) * s * (1.0 - s);
+    s_q[c] = dq;
+    a.dq[(size_t)img * kC + c] = dq;
+    __syncthreads();
+    if (c < kH) {
+        double v = 0.0;
+        for (int k = 0; k < kC; ++k) v += s_q[k] * (double)a.ws2[k * kH + c];
+        v = a.e[(size_t)img * kH + c] > 0.0 ? v : 0.0;
+        s_e[c] = v;
+        a.de[(size_t)img * kH + c] = v;
+    }
+    __syncthreads();
+    double v = 0.0;
+    for (int j = 0; j < kH; ++j) v += s_e[j] * (double)a.ws0[j * kC + c];
+    a.dmh[(size_t)img * kC + c] = (float)(v / (double)a.hw);
+}
+
+struct SeGradArgs {
+    int B;
+    const double *dq, *de, *m, *e;
+    float *dws0, *dbs0, *dws2, *dbs2;
+};
+
+// a thread per output element, the images in image order: dws2 = sum dq^T e, dws0 = sum de^T m, dbs2 = sum dq, dbs0 = sum de
+__global__ __launch_bounds__(256) void se_wgrad_kernel(SeGradArgs a) {
+    int i = blockIdx.x * 256 + threadIdx.x;
+    double v = 0.0;
+    if (i < kC * kH) {
+        const int c = i / kH, j = i - c * kH;
+        for (int b = 0; b < a.B; ++b) v += a.dq[(size_t)b * kC + c] * a.e[(size_t)b * kH + j];
+        a.dws2[i] = (float)v;
+        return;
+    }
+    i -= kC * kH;
+    if (i < kH * kC) {
+        const int j = i / kC, c = i - j * kC;
+        for (int b = 0; b < a.B; ++b) v += a.de[(size_t)b * kH + j] * a.m[(size_t)b * kC + c];
+        a.dws0[i] = (float)v;
+        return;
+    }
+    i -= kH * kC;
+    if (i < kC) {
+        for (int b = 0; b < a.B; ++b) v += a.dq[(size_t)b * kC + i];
+        a.dbs2[i] = (float)v;
+        return;
+    }
+    i -= kC;
+    if (i < kH) {
+        for (int b = 0; b < a.B; ++b) v += a.de[(size_t)b * kH + i];
+        a.dbs0[i] = (float)v;
+    }
+}
+
+// ---- element kernels ----------------------------------------------------------------------------------------------------------
+// x2 = fma(t, s_image, r), four channels per thread
+__global__ __launch_bounds__(256) void scale_add_kernel(const float *t, const float *sf, const float *r, size_t quads, int hw, float *x2) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= quads) return;
+    const size_t p = i / (kC / 4);
+    const int c = 4 * (int)(i - p * (kC / 4));
+    const gf4 tv = ld4(t + 4 * i), rv = ld4(r + 4 * i), sv = ld4(sf + (p / (size_t)hw) * kC + c);
+    gf4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = fmaf(tv[j], sv[j], rv[j]);
+    st4(x2 + 4 * i, o);
+}
+
+// rows [blockIdx.x * rows, ..) of the pixels, a column per thread: dt = fma(g, s_image, dm_image / hw), stored, and its float64
+// column sums (dbc2) as this block's partial
+__global__ __launch_bounds__(kC) void dt_kernel(const float *g, const float *sf, const float *dmh, int N, int hw, int rows, float *dt,
+                                                double *part) {
+    const int r0 = blockIdx.x * rows, r1 = min(N, r0 + rows), c = threadIdx.x;
+    double s[4] = {0.0, 0.0, 0.0, 0.0};                      // row r goes to chain (r - r0) % 4
+    auto one = [&](int r) {
+        const size_t at = (size_t)r * kC + c, im = (size_t)(r / hw) * kC + c;
+        const float v = fmaf(g[at], sf[im], dmh[im]);
+        dt[at] = v;
+        return (double)v;
+    };
+    int r = r0;
+    for (; r + 4 <= r1; r += 4) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) s[i] += one(r + i);
+    }
+    for (int i = 0; r < r1; ++r, ++i) s[i] += one(r);
+    part[(size_t)blockIdx.x * kC + c] = (s[0] + s[1]) + (s[2] + s[3]);
+}
+
+int check_sizes(int B, int Hc, int Wc) {
+    if (B < 1 || B > kMaxPairs || Hc < 1 || Wc < 1) return BALF_ERR_ARG;
+    const long n = (long)B * (long)Hc * (long)Wc;
+    if (n > (long)kMaxN) return BALF_ERR_SHAPE;
+    if (n < 2) return BALF_ERR_ARG;         // the limits of the head, whose input this block produces
+    return BALF_OK;
+}
+
+bool misaligned(const void *p, unsigned mask) { return ((uintptr_t)p & mask) != 0; }
+
+// C[pixel][n] = epilogue(sum_k A[pixel][k] * W(k, n)): TRANSPOSED = false reads W[n][k] (x W^T), true reads W[k][n] (x W)
+template <int EPI, bool TRANSPOSED>
+void pixel_gemm(const float *A, const float *W, int N, float *C, const float *bias, const float *mask, hipStream_t st) {
+    GemmArgs g{};
+    g.A = A; g.a_sm = kC; g.a_sk = 1;
+    g.B = W; g.b_sn = TRANSPOSED ? 1 : kC; g.b_sk = TRANSPOSED ? kC : 1;
+    g.M = N; g.Nn = kC; g.K = kC; g.k_rows = kC;
+    g.C = C; g.c_sm = kC; g.bias = bias; g.mask = mask;
+    launch_gemm<true, !TRANSPOSED, false, EPI>(g, st);
+}
+
+// out[o][k] = fl32(sum_pixel D[pixel][o] * X[pixel][k]) in S slices of the pixels, the slabs added in float64
+void weight_grad(const float *D, const float *X, const Layout &l, float *out, hipStream_t st) {
+    GemmArgs g{};
+    g.A = D; g.a_sm = 1; g.a_sk = kC;
+    g.B = X; g.b_sn = 1; g.b_sk = kC;
+    g.M = kC; g.Nn = kC; g.K = l.N; g.k_rows = l.rows;
+    g.C = l.slab; g.c_sm = kC; g.c_sz = (size_t)kC * kC;
+    launch_gemm<false, false, false, EPI_STORE>(g, st);
+    slab_sum_kernel<<<kC * kC / 256, 256, 0, st>>>(l.slab, l.S, kC * kC, out);
+}
+
+}  // namespace
+}  // namespace balf
+
+using namespace balf;
+
+extern "C" size_t balf_rcab_train_workspace_bytes(int B, int Hc, int Wc) {
+    if (check_sizes(B, Hc, Wc) != BALF_OK) return 0;
+    size_t bytes = 0;
+    make_layout(B, Hc * Wc, nullptr, nullptr, nullptr, &bytes);
+    return bytes;
+}
+
+extern "C" size_t balf_rcab_train_saved_bytes(int B, int Hc, int Wc) {
+    if (check_sizes(B, Hc, Wc) != BALF_OK) return 0;
+    size_t bytes = 0;
+    make_layout(B, Hc * Wc, nullptr, nullptr, &bytes, nullptr);
+    return bytes;
+}
+
+extern "C" int balf_rcab_train_forward(const float *y_dev, const float *r_dev, const float *ln_g_dev, const float *ln_b_dev,
+                                       const float *wc1_dev, const float *bc1_dev, const float *wc2_dev, const float *bc2_dev,
+                                       const float *ws0_dev, const float *bs0_dev, const float *ws2_dev, const float *bs2_dev, int B,
+                                       int Hc, int Wc, float *x2_dev, void *saved_dev, void *workspace_dev, size_t workspace_bytes,
+                                       void *stream) {
+    if (!y_dev || !r_dev || !ln_g_dev || !ln_b_dev || !wc1_dev || !bc1_dev || !wc2_dev || !bc2_dev || !ws0_dev || !bs0_dev || !ws2_dev ||
+        !bs2_dev || !x2_dev || !saved_dev || !workspace_dev)
+        return BALF_ERR_ARG;
+    // 16-byte loads and stores of whole channel quads; the float64 blocks of saved and workspace
+    if (misaligned(y_dev, 15) || misaligned(r_dev, 15) || misaligned(x2_dev, 15) || misaligned(ln_g_dev, 15) || misaligned(ln_b_dev, 15) ||
+        misaligned(saved_dev, 15) || misaligned(workspace_dev, 15))
+        return BALF_ERR_ARG;
+    const int rc = check_sizes(B, Hc, Wc);
+    if (rc != BALF_OK) return rc;
+    if (workspace_bytes < balf_rcab_train_workspace_bytes(B, Hc, Wc)) return BALF_ERR_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int hw = Hc * Wc, N = B * hw;
+    const Layout l = make_layout(B, hw, static_cast<char *>(saved_dev), static_cast<char *>(workspace_dev), nullptr, nullptr);
+
+    ln_fwd_kernel<<<balf_ceil_div(N, kLnFwdPix), 256, 0, st>>>(y_dev, ln_g_dev, ln_b_dev, N, l.n, l.stat);
+    BALF_LAUNCH_CHECK();
+    pixel_gemm<EPI_BIAS_N_LRELU, false>(l.n, wc1_dev, N, l.a, bc1_dev, nullptr, st);       // a = lrelu(n wc1^T + bc1)
+    BALF_LAUNCH_CHECK();
+    pixel_gemm<EPI_BIAS_N, false>(l.a, wc2_dev, N, l.t, bc2_dev, nullptr, st);             // t = a wc2^T + bc2
+    BALF_LAUNCH_CHECK();
+    img_sum_kernel<false><<<dim3(l.PI, B), kC, 0, st>>>(l.t, nullptr, hw, l.img_rows, l.img_part);
+    BALF_LAUNCH_CHECK();
+    SeArgs s{};
+    s.hw = hw; s.PI = l.PI; s.img_part = l.img_part;
+    s.ws0 = ws0_dev; s.bs0 = bs0_dev; s.ws2 = ws2_dev; s.bs2 = bs2_dev;
+    s.m = l.m; s.e = l.e; s.s = l.s; s.sf = l.sf;
+    se_fwd_kernel<<<B, kC, 0, st>>>(s);
+    BALF_LAUNCH_CHECK();
+    const size_t quads = (size_t)N * (kC / 4);
+    scale_add_kernel<<<(unsigned)((quads + 255) / 256), 256, 0, st>>>(l.t, l.sf, r_dev, quads, hw, x2_dev);
+    BALF_LAUNCH_CHECK();
+    return BALF_OK;
+}
+
+extern "C" int balf_rcab_train_backward(const float *dx2_dev, const float *y_dev, const float *ln_g_dev, const float *wc1_dev,
+                                        const float *wc2_dev, const float *ws0_dev, const float *ws2_dev, const void *saved_dev, int B,
+                                        int Hc, int Wc, float *dln_g_dev, float *dln_b_dev, float *dwc1_dev, float *dbc1_dev,
+                                        float *dwc2_dev, float *dbc2_dev, float *dws0_dev, float *dbs0_dev, float *dws2_dev,
+                                        float *dbs2_dev, float *dy_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
+    if (!dx2_dev || !y_dev || !ln_g_dev || !wc1_dev || !wc2_dev || !ws0_dev || !ws2_dev || !saved_dev || !dln_g_dev || !dln_b_dev ||
+        !dwc1_dev || !dbc1_dev || !dwc2_dev || !dbc2_dev || !dws0_dev || !dbs0_dev || !dws2_dev || !dbs2_dev || !workspace_dev)
+        return BALF_ERR_ARG;
+    if (misaligned(y_dev, 15) || misaligned(ln_g_dev, 15) || misaligned(saved_dev, 15) || misaligned(workspace_dev, 15)) return BALF_ERR_ARG;
+    const int rc = check_sizes(B, Hc, Wc);
+    if (rc != BALF_OK) return rc;
+    if (workspace_bytes < balf_rcab_train_workspace_bytes(B, Hc, Wc)) return BALF_ERR_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int hw = Hc * Wc, N = B * hw;
+    const Layout l = make_layout(B, hw, static_cast<char *>(const_cast<void *>(saved_dev)), static_cast<char *>(workspace_dev), nullptr,
+                                 nullptr);
+    double *part0 = l.col_part, *part1 = l.col_part + (size_t)l.PC * kC;
+
+    // the squeeze-excite: ds_i = sum_p g t, then dq, de, dm per image and the four SE gradients over the images
+    img_sum_kernel<true><<<dim3(l.PI, B), kC, 0, st>>>(dx2_dev, l.t, hw, l.img_rows, l.img_part);
+    BALF_LAUNCH_CHECK();
+    SeArgs s{};
+    s.hw = hw; s.PI = l.PI; s.img_part = l.img_part;
+    s.ws0 = ws0_dev; s.ws2 = ws2_dev;
+    s.m = l.m; s.e = l.e; s.s = l.s; s.sf = l.sf; s.dq = l.dq; s.de = l.de; s.dmh = l.dmh;
+    se_bwd_kernel<<<B, kC, 0, st>>>(s);
+    BALF_LAUNCH_CHECK();
+    SeGradArgs sg{};
+    sg.B = B; sg.dq = l.dq; sg.de = l.de; sg.m = l.m; sg.e = l.e;
+    sg.dws0 = dws0_dev; sg.dbs0 = dbs0_dev; sg.dws2 = dws2_dev; sg.dbs2 = dbs2_dev;
+    se_wgrad_kernel<<<balf_ceil_div(2 * kC * kH + kC + kH, 256), 256, 0, st>>>(sg);
+    BALF_LAUNCH_CHECK();
+
+    // dt = g s_i + dm_i / hw, dbc2 = sum dt, dwc2 = dt^T a
+    dt_kernel<<<l.PC, kC, 0, st>>>(dx2_dev, l.sf, l.dmh, N, hw, l.col_rows, l.dt, part0);
+    BALF_LAUNCH_CHECK();
+    partial_sum_kernel<<<kC / 4, 256, 0, st>>>(part0, kC, l.PC, 1, (size_t)kC, dbc2_dev, nullptr);
+    BALF_LAUNCH_CHECK();
+    weight_grad(l.dt, l.a, l, dwc2_dev, st);
+    BALF_LAUNCH_CHECK();
+    // dh = (dt wc2) * (a > 0 ? 1 : 0.2), dbc1 = sum dh, dwc1 = dh^T n
+    pixel_gemm<EPI_LRELU_MASK, true>(l.dt, wc2_dev, N, l.dh, nullptr, l.a, st);
+    BALF_LAUNCH_CHECK();
+    col_sum_kernel<<<l.PC, kC, 0, st>>>(l.dh, N, l.col_rows, part0);
+    BALF_LAUNCH_CHECK();
+    partial_sum_kernel<<<kC / 4, 256, 0, st>>>(part0, kC, l.PC, 1, (size_t)kC, dbc1_dev, nullptr);
+    BALF_LAUNCH_CHECK();
+    weight_grad(l.dh, l.n, l, dwc1_dev, st);
+    BALF_LAUNCH_CHECK();
+    // dn = dh wc1 (over dt, which nobody reads any more), then the LayerNorm: dln_g, dln_b and, if asked for, dy
+    float *dn = l.dt;
+    pixel_gemm<EPI_STORE, true>(l.dh, wc1_dev, N, dn, nullptr, nullptr, st);
+    BALF_LAUNCH_CHECK();
+    LnBwdArgs b{};
+    b.N = N; b.rows = l.col_rows; b.dn = dn; b.y = y_dev; b.stat = l.stat; b.ln_g = ln_g_dev; b.g = dx2_dev; b.dy = dy_dev;
+    b.part_g = part0; b.part_b = part1;
+    b.vec_g = !misaligned(dx2_dev, 15); b.vec_dy = !misaligned(dy_dev, 15);
+    if (dy_dev) ln_bwd_kernel<true><<<l.PC, 256, 0, st>>>(b);
+    else ln_bwd_kernel<false><<<l.PC, 256, 0, st>>>(b);
+    BALF_LAUNCH_CHECK();
+    partial_sum_kernel<<<kC / 4, 256, 0, st>>>(part0, kC, l.PC, 1, (size_t)kC, dln_g_dev, nullptr);
+    BALF_LAUNCH_CHECK();
+    partial_sum_kernel<<<kC / 4, 256, 0, st>>>(part1, kC, l.PC, 1, (size_t)kC, dln_b_dev, nullptr);
+    BALF_LAUNCH_CHECK();
+    return BALF_OK;
+}

@@ -4,6 +4,7 @@
 // separately observable modules (forward hooks on down1..down4), and a wrong kernel should fail at the stage that has it.
 #include "det_common.h"
 #include "split16.h"
+#include "train_gemm.h"
 
 namespace balf {
 namespace {
@@ -36,6 +37,12 @@ __global__ void view_x2_kernel(const float *T, const float *R, const float *scal
     const int c = (int)(i % C);
     const long img = (i / C) / per_img;
     out[i] = fmaf(T[i], scale[img * C + c], R[i]);
+}
+
+// y = r - x0 in place over x0 (balf_forward_rcab_inputs)
+__global__ void rcab_y_kernel(const float *r, float *y, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) y[i] = r[i] - y[i];
 }
 
 }  // namespace
@@ -74,6 +81,43 @@ extern "C" int balf_forward_stage_view(int precision, const void *workspace_dev,
                            reinterpret_cast<const float *>(ws + pl.off_R), reinterpret_cast<const float *>(ws + pl.off_scale),
                            per_img, (long)n, C, out_dev);
     }
+    BALF_LAUNCH_CHECK();
+    return BALF_OK;
+}
+
+// The inputs of stage 4's RCAB for training (balf_rcab_train_forward): r = y + x0 is what the forward keeps (R of the plan), x0 =
+// relu(down4.conv.0(stage-3 output)) is computed again here with the training GEMM, and y = r - x0.  The forward kernels and
+// their buffers are read, never changed.  Scratch: the stage-3 view (split-f16 path) goes to the front of r_out, x0 to y_out.
+extern "C" int balf_forward_rcab_inputs(int precision, const void *workspace_dev, size_t workspace_bytes, int B, int Hp, int Wp,
+                                        const float *conv0_w_dev, const float *conv0_b_dev, float *y_dev, float *r_dev, void *stream) {
+    using namespace balf;
+    if (!workspace_dev || !conv0_w_dev || !conv0_b_dev || !y_dev || !r_dev || B <= 0) return BALF_ERR_ARG;
+    if (precision != BALF_PREC_FP32 && precision != BALF_PREC_FP16) return BALF_ERR_ARG;
+    if (Hp <= 0 || Wp <= 0 || Hp % 64 || Wp % 64) return BALF_ERR_SHAPE;
+    const Plan pl = make_plan(B, Hp, Wp);
+    if (workspace_bytes < pl.total) return BALF_ERR_WORKSPACE;
+    if (B > pl.mb) return BALF_ERR_ARG;                          // only the last micro-batch of a forward is resident
+    const char *ws = static_cast<const char *>(workspace_dev);
+    hipStream_t st = (hipStream_t)stream;
+    const int C3 = kC[2], C4 = kC[3];
+    const size_t pix = (size_t)B * (Hp / 8) * (Wp / 8), n = pix * C4;
+    const float *x3 = reinterpret_cast<const float *>(ws + pl.off_X[2]);
+    if (precision == BALF_PREC_FP16) {
+        hipLaunchKernelGGL(view_frag_kernel, dim3((unsigned)((pix * C3 + 255) / 256)), dim3(256), 0, st, ws + pl.off_X[2], (long)pix, C3,
+                           kFmt32[3] ? 1 : 0, r_dev);
+        BALF_LAUNCH_CHECK();
+        x3 = r_dev;
+    }
+    // x0[pixel][o] = relu(sum_k x3[pixel][k] * W[o][k] + b[o])
+    GemmArgs g{};
+    g.A = x3; g.a_sm = C3; g.a_sk = 1;
+    g.B = conv0_w_dev; g.b_sn = C3; g.b_sk = 1;
+    g.M = (int)pix; g.Nn = C4; g.K = C3; g.k_rows = C3;
+    g.C = y_dev; g.c_sm = C4; g.bias = conv0_b_dev;
+    launch_gemm<true, true, false, EPI_BIAS_N_RELU>(g, st);
+    BALF_LAUNCH_CHECK();
+    if (hipMemcpyAsync(r_dev, ws + pl.off_R, n * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return BALF_ERR_LAUNCH;
+    hipLaunchKernelGGL(rcab_y_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, r_dev, y_dev, n);
     BALF_LAUNCH_CHECK();
     return BALF_OK;
 }

@@ -1,0 +1,170 @@
+// The shared pieces of the training kernels (head_train.hip, rcab_train.hip, and the x0 recomputation of stage_view.hip):
+//   * gemm_kernel: ONE LDS-tiled GEMM on v_mfma_f32_16x16x4_f32 (exact fp32 fma chains, k ascending).  A workgroup of four waves
+//     owns a 64 x 64 tile of C[m][n] = sum_k A(m,k) * B(k,n), a wave a 32 x 32 quarter (2 x 2 MFMA tiles); K goes through LDS in
+//     steps of 16 with the next step's operands fetched into registers before the MFMAs of this one.  The operands are addressed
+//     by (row stride, k stride); whatever lies outside M, Nn or the K range is never loaded and enters the tile as 0, and a
+//     16-row MFMA tile wholly outside is skipped.  A weight gradient sums over the pixels: its K range is cut into S slices
+//     (rows_per_slice(N)), slice s writes slab s of the workspace, and slab_sum_kernel adds the S slabs in float64 in slice order.
+//   * the float64 sums over pixels: col_sum_kernel (per-workgroup partials of the columns of a [N,256] matrix) and
+//     partial_sum_kernel (a wave per output adds the partials in one fixed order: lanes strided, then the butterfly).
+// An epilogue is a template value: a new one adds an instantiation and leaves the code of the others as it was.
+#pragma once
+#include "block_ops.h"
+
+namespace balf {
+namespace {
+
+typedef float gf4 __attribute__((ext_vector_type(4)));
+
+constexpr int kTrainC = 256;                // the channel count of every [N,256] matrix here
+constexpr int kTile = 64, kTK = 16, kPitch = kTile + 4;
+constexpr int kMaxSlices = 64;              // slabs of a weight gradient
+
+// rows (pixels) per K slice of dW2 / dWd: 256, or the multiple of 256 that keeps the slices at kMaxSlices
+int rows_per_slice(int N) {
+    const int chunks = balf_ceil_div(N, 256);
+    return 256 * balf_ceil_div(chunks, kMaxSlices);
+}
+
+// ---- the GEMM -----------------------------------------------------------------------------------------------------------------
+// EPI_BIAS_N: + bias[n];  EPI_BIAS_N_LRELU: + bias[n], then v > 0 ? v : 0.2 v;  EPI_LRELU_MASK: mask > 0 ? v : 0.2 v (the LeakyReLU's
+// derivative from its OUTPUT: the output has the sign of the input, and 0.2 at 0 as torch)
+enum { EPI_STORE = 0, EPI_BIAS_N_RELU = 1, EPI_BIAS_M = 2, EPI_RELU_MASK = 3, EPI_BIAS_N = 4, EPI_BIAS_N_LRELU = 5, EPI_LRELU_MASK = 6 };
+
+struct GemmArgs {
+    const float *A, *B;
+    size_t a_sm, a_sk, b_sn, b_sk;          // element (m, k) of A is A[m * a_sm + k * a_sk], (k, n) of B is B[n * b_sn + k * b_sk]
+    int M, Nn, K, k_rows;                   // slice z sums k in [z * k_rows, min(K, (z + 1) * k_rows))
+    float *C;
+    size_t c_sm, c_sz;                      // C[z * c_sz + m * c_sm + n]
+    const float *bias, *mask;               // the epilogue's: bias[n] or bias[m]; mask as C (EPI_RELU_MASK)
+};
+
+// A_K / B_K: the operand is contiguous along k (else along m / n) -- decides which way the 256 threads walk its 64 x 16 tile
+// PIX_N: the long dimension (pixels) is n and takes grid x
+template <bool A_K, bool B_K, bool PIX_N, int EPI>
+__global__ __launch_bounds__(256) void gemm_kernel(GemmArgs g) {
+    __shared__ float sA[kTK][kPitch], sB[kTK][kPitch];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, q = lane >> 4, li = lane & 15;
+    const int m0 = (PIX_N ? blockIdx.y : blockIdx.x) * kTile, n0 = (PIX_N ? blockIdx.x : blockIdx.y) * kTile;
+    const int kb = blockIdx.z * g.k_rows, ke = min(g.K, kb + g.k_rows);
+    const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
+    // (uniform per wave) the 16-wide MFMA tiles of this wave that hold a row / column inside the matrix
+    const bool live_m[2] = {m0 + wm < g.M, m0 + wm + 16 < g.M}, live_n[2] = {n0 + wn < g.Nn, n0 + wn + 16 < g.Nn};
+
+    int am[4], ak[4], bn[4], bk[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int e = t + 256 * i;
+        am[i] = A_K ? e >> 4 : e & 63;
+        ak[i] = A_K ? e & 15 : e >> 6;
+        bn[i] = B_K ? e >> 4 : e & 63;
+        bk[i] = B_K ? e & 15 : e >> 6;
+    }
+    float ra[4], rb[4];
+    auto fetch = [&](int k0) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int m = m0 + am[i], ka = k0 + ak[i], n = n0 + bn[i], kk = k0 + bk[i];
+            ra[i] = (m < g.M && ka < ke) ? g.A[(size_t)m * g.a_sm + (size_t)ka * g.a_sk] : 0.0f;
+            rb[i] = (n < g.Nn && kk < ke) ? g.B[(size_t)n * g.b_sn + (size_t)kk * g.b_sk] : 0.0f;
+        }
+    };
+    gf4 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = gf4{0.0f, 0.0f, 0.0f, 0.0f};
+
+    if (kb < ke) fetch(kb);
+    for (int k0 = kb; k0 < ke; k0 += kTK) {
+        __syncthreads();                                        // the MFMAs of the step before have read the tiles
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            sA[ak[i]][am[i]] = ra[i];
+            sB[bk[i]][bn[i]] = rb[i];
+        }
+        __syncthreads();
+        if (k0 + kTK < ke) fetch(k0 + kTK);
+#pragma unroll
+        for (int ks = 0; ks < kTK / 4; ++ks) {
+            const int k = 4 * ks + q;
+            const float a0 = sA[k][wm + li], a1 = sA[k][wm + 16 + li], b0 = sB[k][wn + li], b1 = sB[k][wn + 16 + li];
+            if (live_m[0] && live_n[0]) acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, acc[0][0], 0, 0, 0);
+            if (live_m[0] && live_n[1]) acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b1, acc[0][1], 0, 0, 0);
+            if (live_m[1] && live_n[0]) acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b0, acc[1][0], 0, 0, 0);
+            if (live_m[1] && live_n[1]) acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, acc[1][1], 0, 0, 0);
+        }
+    }
+    // the accumulator holds column n = lane & 15 and rows 4 * (lane >> 4) + r of its 16 x 16 tile
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int m = m0 + wm + 16 * i + 4 * q + r, n = n0 + wn + 16 * j + li;
+                if (m >= g.M || n >= g.Nn) continue;
+                const size_t at = (size_t)m * g.c_sm + (size_t)n;
+                float v = acc[i][j][r];
+                if (EPI == EPI_BIAS_N_RELU) v = fmaxf(v + g.bias[n], 0.0f);
+                if (EPI == EPI_BIAS_M) v = v + g.bias[m];
+                if (EPI == EPI_RELU_MASK) v = g.mask[at] > 0.0f ? v : 0.0f;
+                if (EPI == EPI_BIAS_N) v = v + g.bias[n];
+                if (EPI == EPI_BIAS_N_LRELU) { v = v + g.bias[n]; v = v > 0.0f ? v : 0.2f * v; }
+                if (EPI == EPI_LRELU_MASK) v = g.mask[at] > 0.0f ? v : 0.2f * v;
+                g.C[(size_t)blockIdx.z * g.c_sz + at] = v;
+            }
+}
+
+template <bool A_K, bool B_K, bool PIX_N, int EPI>
+void launch_gemm(const GemmArgs &g, hipStream_t st) {
+    const int mt = balf_ceil_div(g.M, kTile), nt = balf_ceil_div(g.Nn, kTile), zs = balf_ceil_div(g.K, g.k_rows);
+    const dim3 grid(PIX_N ? nt : mt, PIX_N ? mt : nt, zs);
+    gemm_kernel<A_K, B_K, PIX_N, EPI><<<grid, 256, 0, st>>>(g);
+}
+
+// out[i] = fl32(sum over the S slabs, slab 0 first, in float64)
+__global__ __launch_bounds__(256) void slab_sum_kernel(const float *slab, int S, int count, float *out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    double s = 0.0;
+    for (int z = 0; z < S; ++z) s += (double)slab[(size_t)z * count + i];
+    out[i] = (float)s;
+}
+
+// ---- float64 sums over pixels ----------------------------------------------------------------------------------------------
+// sum of P partials part[i * stride], to every lane of the wave: lanes strided over the partials, then the butterfly
+__device__ __forceinline__ double wave_sum_strided(const double *part, int P, size_t stride) {
+    double s = 0.0;
+    for (int i = threadIdx.x & 63; i < P; i += 64) s += part[(size_t)i * stride];
+    return wave_sum(s);
+}
+
+// one wave per output: out[c] = fl32(sum_p part[c * stride_c + p * stride_p]), out64[c] the float64 sum (either may be NULL)
+__global__ __launch_bounds__(256) void partial_sum_kernel(const double *part, int count, int P, size_t stride_c, size_t stride_p,
+                                                          float *out, double *out64) {
+    const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (c >= count) return;
+    const double s = wave_sum_strided(part + (size_t)c * stride_c, P, stride_p);
+    if ((threadIdx.x & 63) == 0) {
+        if (out) out[c] = (float)s;
+        if (out64) out64[c] = s;
+    }
+}
+
+// float64 column sums of rows [blockIdx.x * rows, ...) of a [N,256] matrix, a column per thread
+__global__ __launch_bounds__(kTrainC) void col_sum_kernel(const float *x, int N, int rows, double *part) {
+    const int r0 = blockIdx.x * rows, r1 = min(N, r0 + rows);
+    double s[4] = {0.0, 0.0, 0.0, 0.0};                      // row r goes to chain (r - r0) % 4: four loads in flight
+    int r = r0;
+    for (; r + 4 <= r1; r += 4) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) s[i] += (double)x[(size_t)(r + i) * kTrainC + threadIdx.x];
+    }
+    for (int i = 0; r < r1; ++r, ++i) s[i] += (double)x[(size_t)r * kTrainC + threadIdx.x];
+    part[(size_t)blockIdx.x * kTrainC + threadIdx.x] = (s[0] + s[1]) + (s[2] + s[3]);
+}
+
+}  // namespace
+}  // namespace balf

@@ -249,8 +249,12 @@ class MLP_MA_DECODER(nn.Module):
             raise ValueError(f"H and W must be multiples of 64 (pad with mod_padding_symmetric), got {h}x{w}")
         return self._forward("f32", (b, h, w), x.contiguous().float(), b, h, w, want_logits)
 
-    def encode(self, x: torch.Tensor, chunk=None) -> torch.Tensor:
-        """The frozen encoder's output: ``x2`` of down4, the input of ``down4.conv2``, [B,H/8,W/8,256] float32 NHWC, detached --
+    def encode(self, x: torch.Tensor, chunk=None, level: str = "x2"):
+        """``level="rcab"``: one block earlier -- ``(y, r)``, the input of stage 4's channel-attention block and y + the long
+        shortcut, each [B,H/8,W/8,256] float32 NHWC, what ``model.tail_train.TrainableTail`` trains on (balf_forward_rcab_inputs
+        with the module's own ``down4.conv.0``); chunked and guarded exactly as the default level, which is:
+
+        The frozen encoder's output: ``x2`` of down4, the input of ``down4.conv2``, [B,H/8,W/8,256] float32 NHWC, detached --
         what ``model.head_train.TrainableHead`` trains on.  The existing forward runs with ``want_logits=False`` on ``chunk``
         images at a time (default and upper bound: ``balf_forward_micro_batch``, so that the whole chunk is resident in the
         workspace) and the stage-4 view is taken after each chunk.  The encoder has no training-mode layer: this works whatever
@@ -268,21 +272,30 @@ class MLP_MA_DECODER(nn.Module):
             raise ValueError(f"H and W must be multiples of 64 (pad with mod_padding_symmetric), got {h}x{w}")
         if b < 1:
             raise ValueError("encode: an empty batch")
+        if level not in ("x2", "rcab"):
+            raise ValueError(f"encode: level must be 'x2' or 'rcab', got {level!r}")
         x = x.contiguous().float()
         l = lib()
         mb = l.balf_forward_micro_batch(b, h, w)
         chunk = mb if chunk is None else max(1, min(int(chunk), mb))
         out = torch.empty((b, h // 8, w // 8, 256), dtype=torch.float32, device=x.device)
+        if level == "rcab":
+            r = torch.empty_like(out)
+            conv0 = self.down4.conv[0]
+            w0, b0 = conv0.weight.detach().float().contiguous(), conv0.bias.detach().float().contiguous()
         with torch.no_grad():
             for at in range(0, b, chunk):
                 nb = min(chunk, b - at)
                 self._forward("f32", (nb, h, w), x[at:at + nb], nb, h, w, False)
                 ws = ops._workspace("forward", x.device, l.balf_forward_workspace_bytes(nb, h, w))
+                if level == "rcab":
+                    ops.rcab_inputs(self._code_of(self.effective_precision), ws, nb, h, w, w0, b0, out[at:at + nb], r[at:at + nb])
+                    continue
                 with torch.cuda.device(x.device):
                     check(l.balf_forward_stage_view(self._code_of(self.effective_precision), ws.data_ptr(), ws.numel(), nb, h, w, 4,
                                                     out[at:at + nb].data_ptr(), _lib.current_stream_ptr(x.device)),
                           "balf_forward_stage_view")
-        return out
+        return (out, r) if level == "rcab" else out
 
     def _forward(self, kind, dims, src, b, hp, wp, want_logits):
         """The body of ``forward`` / ``forward_u8`` on a checked input: ``dims`` are the kernel's own (see _launch), ``hp x wp``

@@ -682,3 +682,137 @@ def head_train_backward(dlogits: torch.Tensor, x2: torch.Tensor, w2: torch.Tenso
                                          saved.data_ptr(), b, hc, wc, *[t.data_ptr() for t in out], _ptr(dx2), ws.data_ptr(),
                                          ws.numel(), current_stream_ptr(dev)), "balf_head_train_backward")
     return HeadTrainBackward(*out, dx2)
+
+
+RCAB_PARAMS = ("ln_g", "ln_b", "wc1", "bc1", "wc2", "bc2", "ws0", "bs0", "ws2", "bs2")
+_RCAB_PARAM_SHAPES = {"ln_g": (256,), "ln_b": (256,), "wc1": (256, 256), "bc1": (256,), "wc2": (256, 256), "bc2": (256,),
+                      "ws0": (64, 256), "bs0": (64,), "ws2": (256, 64), "bs2": (256,)}
+_RCAB_BACKWARD_READS = ("ln_g", "wc1", "wc2", "ws0", "ws2")
+
+
+class RcabTrainForward(NamedTuple):
+    x2: torch.Tensor                          # [B,Hc,Wc,256] float32: the input of down4.conv2
+    saved: torch.Tensor                       # opaque uint8 block for rcab_train_backward
+
+
+class RcabTrainBackward(NamedTuple):
+    dln_g: torch.Tensor                       # the ten gradients, in RCAB_PARAMS order
+    dln_b: torch.Tensor
+    dwc1: torch.Tensor
+    dbc1: torch.Tensor
+    dwc2: torch.Tensor
+    dbc2: torch.Tensor
+    dws0: torch.Tensor
+    dbs0: torch.Tensor
+    dws2: torch.Tensor
+    dbs2: torch.Tensor
+    dy: Optional[torch.Tensor]                # [B,Hc,Wc,256]
+
+
+def _rcab_train_checks(y, named, aligned=()):
+    """As _head_train_checks: metadata first, then the devices.  ``aligned``: names whose storage must start on 16 bytes (the
+    LayerNorm kernels move four channels at a time).  -> (B, Hc, Wc)."""
+    if y.dim() != 4 or y.shape[3] != 256:
+        raise BalfHipError(f"y must be [B,Hc,Wc,256] (the input of stage 4's RCAB, NHWC), got {tuple(y.shape)}")
+    b, hc, wc, _ = y.shape
+    if not 1 <= b <= 65535 or hc < 1 or wc < 1 or not 2 <= b * hc * wc <= 1 << 24:
+        raise BalfHipError(f"rcab_train: 1 <= B <= 65535 and 2 <= B * Hc * Wc <= 2^24, got {tuple(y.shape)}")
+    for t, name, shape in named:
+        if t is None:
+            continue
+        if t.dtype != torch.float32 and name != "saved":
+            raise BalfHipError(f"{name} must be float32, got {t.dtype}")
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise BalfHipError(f"{name} must be {list(shape)}, got {list(t.shape)}")
+        if not t.is_contiguous():
+            raise BalfHipError(f"{name} must be contiguous")
+        if name in aligned and t.storage_offset() * t.element_size() % 16:
+            raise BalfHipError(f"{name} must start on a 16-byte boundary of its storage")
+    for t, name, _ in named:
+        if t is not None:
+            require_gpu_tensor(t, name)
+            if t.device != y.device:
+                raise BalfHipError(f"{name} is on {t.device}, y on {y.device}")
+    return b, hc, wc
+
+
+def rcab_train_forward(y: torch.Tensor, r: torch.Tensor, params, saved=None) -> RcabTrainForward:
+    """Stage 4's channel-attention block on ``y`` [B,Hc,Wc,256] with ``r`` = y + the long shortcut (``rcab_inputs`` /
+    ``MLP_MA_DECODER.encode(level="rcab")`` give both): LayerNorm, conv1, LeakyReLU, conv2, the squeeze-excite scale, ``x2 = t * s +
+    r`` (balf_rcab_train_forward in include/balf_hip.h).  ``params``: the ten tensors in ``RCAB_PARAMS`` order, float32 and
+    contiguous on y's GPU.  ``saved``: a uint8 block to reuse (at least balf_rcab_train_saved_bytes), else allocated."""
+    params = tuple(params)
+    if len(params) != len(RCAB_PARAMS):
+        raise BalfHipError(f"rcab_train_forward takes the ten parameters {RCAB_PARAMS}, got {len(params)}")
+    named = ((y, "y", None), (r, "r", tuple(y.shape))) + tuple((t, k, _RCAB_PARAM_SHAPES[k]) for t, k in zip(params, RCAB_PARAMS))
+    b, hc, wc = _rcab_train_checks(y, named + ((saved, "saved", None),), aligned=("y", "r", "ln_g", "ln_b"))
+    dev = y.device
+    l = lib()
+    need = l.balf_rcab_train_saved_bytes(b, hc, wc)
+    if saved is None:
+        saved = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif saved.dtype != torch.uint8 or saved.numel() < need or saved.data_ptr() % 16:
+        raise BalfHipError(f"saved must be a 16-byte aligned uint8 tensor of at least {need} bytes")
+    x2 = torch.empty_like(y)
+    ws = _workspace("rcab_train", dev, l.balf_rcab_train_workspace_bytes(b, hc, wc))
+    with torch.cuda.device(dev):
+        check(l.balf_rcab_train_forward(y.data_ptr(), r.data_ptr(), *[t.data_ptr() for t in params], b, hc, wc, x2.data_ptr(),
+                                        saved.data_ptr(), ws.data_ptr(), ws.numel(), current_stream_ptr(dev)),
+              "balf_rcab_train_forward")
+    return RcabTrainForward(x2, saved)
+
+
+def rcab_train_backward(dx2: torch.Tensor, y: torch.Tensor, ln_g: torch.Tensor, wc1: torch.Tensor, wc2: torch.Tensor,
+                        ws0: torch.Tensor, ws2: torch.Tensor, saved: torch.Tensor, want_dy=False) -> RcabTrainBackward:
+    """The backward of ``rcab_train_forward`` (balf_rcab_train_backward): ``dx2`` [B,Hc,Wc,256] (``head_train_backward`` writes
+    it) and the ``saved`` block of that forward -> the ten parameter gradients and, with ``want_dy``, the gradient at the block's
+    input (``want_dy`` may be a contiguous float32 tensor of y's shape to write into)."""
+    s = _RCAB_PARAM_SHAPES
+    dy = want_dy if isinstance(want_dy, torch.Tensor) else None
+    shape = tuple(y.shape)
+    named = ((y, "y", None), (dx2, "dx2", shape), (ln_g, "ln_g", s["ln_g"]), (wc1, "wc1", s["wc1"]), (wc2, "wc2", s["wc2"]),
+             (ws0, "ws0", s["ws0"]), (ws2, "ws2", s["ws2"]), (saved, "saved", None), (dy, "dy", shape))
+    b, hc, wc = _rcab_train_checks(y, named, aligned=("y", "ln_g"))
+    dev = y.device
+    l = lib()
+    if saved.dtype != torch.uint8 or saved.numel() < l.balf_rcab_train_saved_bytes(b, hc, wc) or saved.data_ptr() % 16:
+        raise BalfHipError("saved must be the uint8 block that rcab_train_forward returned for this shape")
+    if dy is None and want_dy:
+        dy = torch.empty_like(y)
+    out = [torch.empty(s[k], dtype=torch.float32, device=dev) for k in RCAB_PARAMS]
+    ws = _workspace("rcab_train", dev, l.balf_rcab_train_workspace_bytes(b, hc, wc))
+    with torch.cuda.device(dev):
+        check(l.balf_rcab_train_backward(dx2.data_ptr(), y.data_ptr(), ln_g.data_ptr(), wc1.data_ptr(), wc2.data_ptr(),
+                                         ws0.data_ptr(), ws2.data_ptr(), saved.data_ptr(), b, hc, wc,
+                                         *[t.data_ptr() for t in out], _ptr(dy), ws.data_ptr(), ws.numel(),
+                                         current_stream_ptr(dev)), "balf_rcab_train_backward")
+    return RcabTrainBackward(*out, dy)
+
+
+def rcab_inputs(precision: int, workspace: torch.Tensor, b: int, hp: int, wp: int, conv0_w: torch.Tensor, conv0_b: torch.Tensor,
+                y: torch.Tensor, r: torch.Tensor) -> None:
+    """After a forward of ``b`` padded ``hp x wp`` images whose workspace is ``workspace`` (balf_forward_rcab_inputs): write the
+    RCAB's input into ``y`` and y + the long shortcut into ``r``, both [b,hp/8,wp/8,256] float32 and contiguous on the
+    workspace's GPU; ``conv0_w`` [256,128], ``conv0_b`` [256] are ``down4.conv.0``.  ``precision``: _lib.PREC_FP32 / PREC_FP16,
+    the kernels that forward ran on."""
+    if hp <= 0 or wp <= 0 or hp % 64 or wp % 64 or b < 1:
+        raise BalfHipError(f"rcab_inputs: b >= 1 and hp, wp multiples of 64, got {(b, hp, wp)}")
+    shape = (b, hp // 8, wp // 8, 256)
+    for t, name, want in ((conv0_w, "conv0_w", (256, 128)), (conv0_b, "conv0_b", (256,)), (y, "y", shape), (r, "r", shape)):
+        if t.dtype != torch.float32:
+            raise BalfHipError(f"{name} must be float32, got {t.dtype}")
+        if tuple(t.shape) != want:
+            raise BalfHipError(f"{name} must be {list(want)}, got {list(t.shape)}")
+        if not t.is_contiguous():
+            raise BalfHipError(f"{name} must be contiguous")
+    if workspace.dtype != torch.uint8:
+        raise BalfHipError("workspace must be the uint8 workspace of the forward")
+    for t, name in ((workspace, "workspace"), (conv0_w, "conv0_w"), (conv0_b, "conv0_b"), (y, "y"), (r, "r")):
+        require_gpu_tensor(t, name)
+        if t.device != workspace.device:
+            raise BalfHipError(f"{name} is on {t.device}, the workspace on {workspace.device}")
+    dev = workspace.device
+    with torch.cuda.device(dev):
+        check(lib().balf_forward_rcab_inputs(precision, workspace.data_ptr(), workspace.numel(), b, hp, wp, conv0_w.data_ptr(),
+                                             conv0_b.data_ptr(), y.data_ptr(), r.data_ptr(), current_stream_ptr(dev)),
+              "balf_forward_rcab_inputs")

@@ -229,7 +229,8 @@ def _guarded_features(model, encode_chunk):
 
 def train_head(dataloader, model, head, optimizer, device, grid_size=8, chunk_batches=16, noise=None) -> float:
     """One epoch of the reference's training step (train_utils.py:104-124) for the trainable tail alone: ``model``'s encoder is
-    frozen and runs on the forward kernels (``model.encode``), ``head`` (``model.head_train.TrainableHead``) runs forward in
+    frozen and runs on the forward kernels (``model.encode``), ``head`` (``model.head_train.TrainableHead``, or
+    ``model.tail_train.TrainableTail``, whose ``encode_level`` attribute selects ``model.encode(x, level=...)``) runs forward in
     training mode and backward on the library, ``optimizer`` (torch's, over ``head.parameters()``) steps once per loader batch.
     ``dataloader`` yields the reference's 6-tuples ``(images_src, images_dst, heatmap_src, heatmap_dst, h_src_2_dst,
     h_dst_2_src)``; images ``[B,3,H,W]`` with H, W multiples of 64.  Per chunk of ``chunk_batches`` batches: every source and
@@ -247,8 +248,13 @@ def train_head(dataloader, model, head, optimizer, device, grid_size=8, chunk_ba
     chunk_batches = max(1, int(chunk_batches))
     values, batches = [], []
 
+    level = getattr(head, "encode_level", "x2")              # model.tail_train.TrainableTail: "rcab", features = (y, r)
+
+    def encode(x):
+        return model.encode(x) if level == "x2" else model.encode(x, level=level)
+
     def encode_chunk():
-        return [(model.encode(b[0].to(device)), model.encode(b[1].to(device))) for b in batches]
+        return [(encode(b[0].to(device)), encode(b[1].to(device))) for b in batches]
 
     def flush():
         features = _guarded_features(model, encode_chunk)

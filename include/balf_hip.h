@@ -606,6 +606,59 @@ int balf_head_train_backward(const float *dlogits_dev, const float *x2_dev, cons
                              float *dwd_dev, float *dbd_dev, float *dgamma_dev, float *dbeta_dev, float *dx2_dev,
                              void *workspace_dev, size_t workspace_bytes, void *stream);
 
+/* ---- stage 4's channel-attention block (RCAB) in training form, and its backward ---------------------------
+ * The block directly above x2: LayerNorm -> conv1 (Linear 256 -> 256) -> LeakyReLU(0.2) -> conv2 (Linear 256 -> 256) ->
+ * squeeze-excite scale, plus both shortcuts.  N = B * Hc * Wc pixels, i = the image of pixel p.  y_dev [N,256] is the block's
+ * input, r_dev [N,256] = y + x0 with x0 = relu(down4.conv.0(.)) the long shortcut (balf_forward_rcab_inputs writes both).  The
+ * ten parameters under down4.residual_channel_attention_block. are plain float32 device tensors in PyTorch layout: ln_g, ln_b
+ * [256] (norm), wc1 [256,256], bc1 [256] (conv1), wc2, bc2 (conv2), ws0 [64,256], bs0 [64] (calayer.excite.0), ws2 [256,64],
+ * bs2 [256] (calayer.excite.2).
+ *   forward    mean, var over the 256 channels of a pixel, the variance from the centred values; rstd = 1 / sqrt(var + 1e-5);
+ *              xhat = (y - mean) rstd;  n = fma(xhat, ln_g, ln_b);  h = n wc1^T + bc1;  a = h > 0 ? h : 0.2 h;  t = a wc2^T + bc2;
+ *              m_i = mean of t over the pixels of image i;  e_i = relu(m_i ws0^T + bs0);  s_i = sigmoid(e_i ws2^T + bs2)  (float64);
+ *              x2 = fma(t, fl32(s_i), r)  -- the formula of the inference forward.
+ *   backward   g = dx2_dev [N,256]:  ds_i = sum_p g t;  dq = ds s (1 - s);  dws2 = sum_i dq_i^T e_i;  dbs2 = sum_i dq_i;
+ *              de = (dq ws2) [e > 0];  dws0 = sum_i de_i^T m_i;  dbs0 = sum_i de_i;  dm = de ws0  (all float64, images in order);
+ *              dt = fma(g, fl32(s_i), fl32(dm_i / (Hc Wc)));  dwc2 = dt^T a;  dbc2 = sum_p dt;  da = dt wc2;
+ *              dh = da (a > 0 ? 1 : 0.2)  (0.2 at h == 0, as torch);  dwc1 = dh^T n;  dbc1 = sum_p dh;  dn = dh wc1;
+ *              dln_g = sum_p dn xhat;  dln_b = sum_p dn;  u = dn ln_g;
+ *              dy = g + rstd (u - mean_c u - xhat mean_c(u xhat))  (dy_dev NULL ok) -- the gradient at the block's input, its own
+ *              shortcut included.  The long shortcut's gradient is g itself and is not written.
+ * saved_dev: an opaque caller-owned block of balf_rcab_train_saved_bytes bytes that the forward writes and the backward of the
+ * same (B, Hc, Wc) reads: n, a, t [N,256], (mean, rstd) per pixel, m, e, s per image.  The backward recomputes xhat from y and
+ * the saved (mean, rstd) with the forward's operations (ln_g may be 0).
+ * Arithmetic: the six 256 x 256 products run on v_mfma_f32_16x16x4_f32 (the GEMM of the head, train_gemm.h), dwc1 / dwc2 over
+ * S = ceil(N / rows) slices of the pixels with a float64 slab sum, as dW2 of the head.  A LayerNorm row is one wave, four
+ * channels per lane, every channel sum (v0 + v1) + (v2 + v3) and then the xor butterfly.  Every sum over pixels (m, ds, dbc1,
+ * dbc2, dln_g, dln_b) is made of float64 per-workgroup partials added in one fixed order; m and ds per image, over row blocks of
+ * THAT image (max(64, ceil(Hc Wc / 1024)) rows each), so that no partial mixes two images.  No floating-point atomics; every
+ * order is a function of (B, Hc, Wc) alone: two calls on the same input give bit-identical outputs.  dy, when not requested, is
+ * neither computed nor written and the other outputs do not change.  Stream-ordered, nothing synchronised or read back,
+ * capturable; every word of the workspace and of saved that is read was written before.
+ * Launches: forward 6, backward 16.
+ * Limits: 1 <= B <= 65535, Hc, Wc >= 1, N >= 2 (BALF_ERR_ARG), N <= 2^24 (BALF_ERR_SHAPE); the required pointers must not be
+ * NULL; y_dev, r_dev, x2_dev, ln_g_dev, ln_b_dev, saved_dev and workspace_dev must be 16-byte aligned (dx2_dev and dy_dev need 4)
+ * (BALF_ERR_ARG); a workspace smaller than balf_rcab_train_workspace_bytes gives BALF_ERR_WORKSPACE.  Both size queries return 0
+ * outside these limits. */
+size_t balf_rcab_train_workspace_bytes(int B, int Hc, int Wc);
+size_t balf_rcab_train_saved_bytes(int B, int Hc, int Wc);
+int balf_rcab_train_forward(const float *y_dev, const float *r_dev, const float *ln_g_dev, const float *ln_b_dev,
+                            const float *wc1_dev, const float *bc1_dev, const float *wc2_dev, const float *bc2_dev,
+                            const float *ws0_dev, const float *bs0_dev, const float *ws2_dev, const float *bs2_dev, int B, int Hc,
+                            int Wc, float *x2_dev, void *saved_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+int balf_rcab_train_backward(const float *dx2_dev, const float *y_dev, const float *ln_g_dev, const float *wc1_dev,
+                             const float *wc2_dev, const float *ws0_dev, const float *ws2_dev, const void *saved_dev, int B, int Hc,
+                             int Wc, float *dln_g_dev, float *dln_b_dev, float *dwc1_dev, float *dbc1_dev, float *dwc2_dev,
+                             float *dbc2_dev, float *dws0_dev, float *dbs0_dev, float *dws2_dev, float *dbs2_dev, float *dy_dev,
+                             void *workspace_dev, size_t workspace_bytes, void *stream);
+/* After a forward whose last micro-batch of B images is resident in workspace_dev (the rules and error codes of
+ * balf_forward_stage_view): r_dev [B,Hp/8,Wp/8,256] = the forward's own y + x0, copied; x0 = relu(x3 W^T + b) computed again from
+ * the resident stage-3 output (view 3, de-fragmented on the split-f16 path) with the training GEMM and conv0_w_dev [256,128],
+ * conv0_b_dev [256] = down4.conv.0; y_dev = r - x0.  y therefore carries one more rounding of r and the difference of the two
+ * evaluations of x0.  The forward's kernels and buffers are only read; the two outputs serve as scratch, nothing is allocated. */
+int balf_forward_rcab_inputs(int precision, const void *workspace_dev, size_t workspace_bytes, int B, int Hp, int Wp,
+                             const float *conv0_w_dev, const float *conv0_b_dev, float *y_dev, float *r_dev, void *stream);
+
 /* ---- measurement aid (not part of the data path) ---------------------------------------------
  * Between balf_profile_begin() and balf_profile_end() every kernel launch of the library is bracketed
  * by a hipEvent pair on its launch stream.  balf_profile_end() waits for those events and returns,
