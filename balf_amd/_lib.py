@@ -100,6 +100,11 @@ PROTOTYPES = {
     "balf_rcab_train_forward": (_i, [_fp] * 12 + [_i, _i, _i, _fp, _vp, _vp, _sz, _vp]),
     "balf_rcab_train_backward": (_i, [_fp] * 7 + [_vp, _i, _i, _i] + [_fp] * 11 + [_vp, _sz, _vp]),
     "balf_forward_rcab_inputs": (_i, [_i, _vp, _sz, _i, _i, _i, _fp, _fp, _fp, _fp, _vp]),
+    "balf_gmlp_train_workspace_bytes": (_sz, [_i, _i, _i]),
+    "balf_gmlp_train_saved_bytes": (_sz, [_i, _i, _i]),
+    "balf_gmlp_train_forward": (_i, [_fp, C.POINTER(_vp), _i, _i, _i, _fp, _vp, _vp, _sz, _vp]),
+    "balf_gmlp_train_backward": (_i, [_fp, _fp, C.POINTER(_vp), _vp, _i, _i, _i, C.POINTER(_vp), _fp, _vp, _sz, _vp]),
+    "balf_forward_gmlp_input": (_i, [_i, _vp, _sz, _i, _i, _i, _fp, _fp, _fp, _fp, _vp]),
     "balf_profile_num_slots": (_i, []),
     "balf_profile_slot_name": (C.c_char_p, [_i]),
     "balf_profile_begin": (_i, []),

@@ -1,0 +1,589 @@
+// balf_gmlp_train_forward / balf_gmlp_train_backward (include/balf_hip.h): stage 4's ResidualSplitHeadMultiAxisGmlpLayer in
+// training form,  x0 -> LayerNorm -> dense1 (256 -> 512) -> GELU -> halves (u, v) -> the grid branch on u, the block branch on v
+// -> dense2 (512 -> 256) + x0 = y,  and its backward from dy to the 26 parameter gradients and dx0.
+// N = B * Hc * Wc pixels.  A branch on z [N,256]:  LayerNorm -> dense1 (256 -> 512) -> GELU -> halves (a, c) -> LayerNorm of c ->
+// the 64 x 64 product along the TOKEN axis -> gate a * (mix + 1) -> dense2 (256 -> 256) + z.
+//
+// Kernels:
+//   * gemm_kernel (train_gemm.h) for every product along the channels; GELU is its epilogue EPI_BIAS_N_GELU, which also keeps the
+//     pre-activation, the shortcuts are EPI_BIAS_N_ADD.  The weight gradients go through the slab split and the float64 slab sum.
+//   * LayerNorm: ln_fwd_kernel / ln_bwd_kernel of train_ln.h for the layer's own norm; ln_fwd_s_kernel / ln_bwd_s_kernel here are the
+//     same row-per-wave arithmetic on a 256-channel half of a [N,512] row (a row stride and a column offset), the backward
+//     multiplied by the GELU derivative of the product that made its input, so that dH = dG * gelu'(H) costs no pass of its own.
+//   * the token mix.  A group's 64 tokens are 64 pixels that no single stride addresses: pixel(token) = base(group) +
+//     (token >> 3) * sy + (token & 7) * sx, with (sy, sx) = (Hc / 8 * Wc, Wc / 8) under the grid map and (Wc, 1) under the block
+//     map.  mix_fwd_kernel / mix_bwd_kernel take a workgroup per group, Wt in LDS, and gather the rows through that map: wave w
+//     owns channels 64 w .. 64 w + 63 of all 64 tokens, a lane loads four consecutive channels of a token's row straight into the
+//     B operands of four MFMA tiles (tile j, column li <-> channel 64 w + 4 li + j), so every activation is read once, by one
+//     lane, as a 16-byte load, and nothing is transposed through memory.  k, the token summed over, ascends.
+//   * column sums in float64 per workgroup of rows (col_sum_kernel, col_sum_s_kernel), added by partial_sum_kernel.
+// dWt and dbt: each wave of mix_bwd_kernel sums dmix cn^T over its 64 channels in an MFMA chain per group and adds the groups of
+// its workgroup in float64 registers; the 4 * PW wave partials are added by partial_sum_kernel in one fixed order.
+// No floating-point atomics; every order is a function of (B, Hc, Wc) alone.
+#include "train_ln.h"
+
+namespace balf {
+namespace {
+
+constexpr int kC = 256, kC2 = 512;          // channels; the width of the two dense1 outputs and of the concatenation
+constexpr int kTok = 64;                    // tokens of a group: the 8 x 8 grid, the 8 x 8 block
+constexpr int kParams = 26;
+constexpr int kBranchParams = 10;           // norm.{w,b} dense1.{w,b} gating norm.{w,b} gating dense.{w,b} dense2.{w,b}
+constexpr int kMaxN = 1 << 24;
+constexpr int kMixPitch = 80;               // floats per row of Wt in LDS: the four k of an MFMA step fall on disjoint banks
+constexpr int kMixPart = kTok * kTok + kTok;    // float64 per wave partial: dWt, then dbt
+constexpr int kMaxMixWgs = 256;             // workgroups of mix_bwd_kernel: one per CU, or one per group when there are fewer
+
+struct Branch {                             // saved, per branch
+    float *nb, *statb, *hb, *gb, *statg, *cn, *mixp1, *gated;
+};
+
+struct Layout {
+    int B, Hc, Wc, N, S, rows, col_rows, PC, groups, gpw, PW;
+    // saved
+    float *n0, *stat0, *h0, *g0, *cat;
+    Branch br[2];
+    // workspace
+    double *col_part;                       // [2][PC][512]
+    double *mix_part;                       // [4 PW][kMixPart]
+    float *dcat, *dh0, *dhb;                // [N,512] each
+    float *t0, *t1;                         // [N,256]: dgated, then dnb, then dn0; dcn
+    float *slab;                            // [S][512 * 256]
+};
+
+Layout make_layout(int B, int Hc, int Wc, char *saved, char *work, size_t *saved_bytes, size_t *work_bytes) {
+    Layout l{};
+    l.B = B; l.Hc = Hc; l.Wc = Wc;
+    const int N = l.N = B * Hc * Wc;
+    l.rows = rows_per_slice(N);
+    l.S = balf_ceil_div(N, l.rows);
+    l.col_rows = l.rows / 16 > 64 ? l.rows / 16 : 64;       // as rcab_train.hip: 64 rows per workgroup, or what keeps PC at 1024
+    l.PC = balf_ceil_div(N, l.col_rows);
+    l.groups = N / kTok;
+    l.gpw = balf_ceil_div(l.groups, kMaxMixWgs);
+    l.PW = balf_ceil_div(l.groups, l.gpw);
+    const size_t a1 = (size_t)N * kC * sizeof(float), a2 = 2 * a1, st = (size_t)N * 2 * sizeof(float);
+    WorkspaceCursor sv{saved, 0};
+    l.n0 = sv.take<float>(a1);
+    l.stat0 = sv.take<float>(st);
+    l.h0 = sv.take<float>(a2);
+    l.g0 = sv.take<float>(a2);
+    l.cat = sv.take<float>(a2);
+    for (Branch &b : l.br) {
+        b.nb = sv.take<float>(a1);
+        b.statb = sv.take<float>(st);
+        b.hb = sv.take<float>(a2);
+        b.gb = sv.take<float>(a2);
+        b.statg = sv.take<float>(st);
+        b.cn = sv.take<float>(a1);
+        b.mixp1 = sv.take<float>(a1);
+        b.gated = sv.take<float>(a1);
+    }
+    if (saved_bytes) *saved_bytes = sv.used;
+    WorkspaceCursor ws{work, 0};
+    l.col_part = ws.take<double>((size_t)2 * l.PC * kC2 * sizeof(double));
+    l.mix_part = ws.take<double>((size_t)4 * l.PW * kMixPart * sizeof(double));
+    l.dcat = ws.take<float>(a2);
+    l.dh0 = ws.take<float>(a2);
+    l.dhb = ws.take<float>(a2);
+    l.t0 = ws.take<float>(a1);
+    l.t1 = ws.take<float>(a1);
+    l.slab = ws.take<float>((size_t)l.S * kC2 * kC * sizeof(float));
+    if (work_bytes) *work_bytes = ws.used;
+    return l;
+}
+
+// ---- LayerNorm on a 256-channel half of a wider row ----------------------------------------------------------------------------
+// ln_fwd_kernel with a row stride: x[p * xs + c]
+__global__ __launch_bounds__(256) void ln_fwd_s_kernel(const float *x, size_t xs, const float *ln_g, const float *ln_b, int N,
+                                                       float *n_out, float *stat) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const gf4 gg = ld4(ln_g + 4 * lane), bb = ld4(ln_b + 4 * lane);
+#pragma unroll
+    for (int i = 0; i < kLnFwdPix / 4; ++i) {
+        const int p = blockIdx.x * kLnFwdPix + 4 * i + wave;   // (uniform in the wave)
+        if (p >= N) break;
+        const gf4 v = ld4(x + (size_t)p * xs + 4 * lane);
+        const float mean = chan_sum(v) * (1.0f / kC);
+        const gf4 d = v - mean;
+        const float var = chan_sum(d * d) * (1.0f / kC);
+        const float rstd = 1.0f / sqrtf(var + kLnEps);
+        const gf4 xh = d * rstd;
+        gf4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = fmaf(xh[j], gg[j], bb[j]);
+        st4(n_out + (size_t)p * kC + 4 * lane, o);
+        if (lane == 0) { stat[2 * (size_t)p] = mean; stat[2 * (size_t)p + 1] = rstd; }
+    }
+}
+
+struct LnBwdSArgs {
+    int N, rows;
+    const float *dn, *stat, *ln_g;          // dn [N,256]
+    const float *x, *g, *h;                 // the LayerNorm's input, the shortcut's gradient (ADD_G), the pre-activation behind x
+    size_t xs, gs, hs, os;                  // their row strides, and out's
+    float *out;
+    double *part_g, *part_b;                // [PC][256] each
+};
+
+// ln_bwd_kernel on strided rows, its result times the GELU derivative:  out = (g + rstd * (u - mean_c u - xhat * mean_c(u * xhat)))
+// * gelu'(h), u = dn * ln_g, and the float64 partials of dln_g = sum dn * xhat, dln_b = sum dn
+template <bool ADD_G>
+__global__ __launch_bounds__(256) void ln_bwd_s_kernel(LnBwdSArgs a) {
+    __shared__ double s_part[2][4][kC];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int r0 = blockIdx.x * a.rows, r1 = min(a.N, r0 + a.rows);
+    const gf4 gg = ld4(a.ln_g + 4 * lane);
+    double sg[4] = {0.0, 0.0, 0.0, 0.0}, sb[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int p = r0 + wave; p < r1; p += 4) {
+        const gf4 dn = ld4(a.dn + (size_t)p * kC + 4 * lane), v = ld4(a.x + (size_t)p * a.xs + 4 * lane);
+        const gf4 hv = ld4(a.h + (size_t)p * a.hs + 4 * lane);
+        const float mean = a.stat[2 * (size_t)p], rstd = a.stat[2 * (size_t)p + 1];
+        const gf4 d = v - mean;
+        const gf4 xh = d * rstd;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            sg[j] += (double)dn[j] * (double)xh[j];
+            sb[j] += (double)dn[j];
+        }
+        const gf4 u = dn * gg;
+        const float mu = chan_sum(u) * (1.0f / kC), mux = chan_sum(u * xh) * (1.0f / kC);
+        gf4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = rstd * ((u[j] - mu) - xh[j] * mux);
+        if constexpr (ADD_G) o = ld4(a.g + (size_t)p * a.gs + 4 * lane) + o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] *= gelu_grad(hv[j]);
+        st4(a.out + (size_t)p * a.os + 4 * lane, o);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        s_part[0][wave][4 * lane + j] = sg[j];
+        s_part[1][wave][4 * lane + j] = sb[j];
+    }
+    __syncthreads();
+    const int c = threadIdx.x;
+    a.part_g[(size_t)blockIdx.x * kC + c] = ((s_part[0][0][c] + s_part[0][1][c]) + s_part[0][2][c]) + s_part[0][3][c];
+    a.part_b[(size_t)blockIdx.x * kC + c] = ((s_part[1][0][c] + s_part[1][1][c]) + s_part[1][2][c]) + s_part[1][3][c];
+}
+
+// col_sum_kernel on rows of stride xs and gridDim.y * 256 columns: part[block][column]
+__global__ __launch_bounds__(256) void col_sum_s_kernel(const float *x, size_t xs, int N, int rows, double *part) {
+    const int r0 = blockIdx.x * rows, r1 = min(N, r0 + rows), c = blockIdx.y * 256 + threadIdx.x;
+    double s[4] = {0.0, 0.0, 0.0, 0.0};                      // row r goes to chain (r - r0) % 4: four loads in flight
+    int r = r0;
+    for (; r + 4 <= r1; r += 4) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) s[i] += (double)x[(size_t)(r + i) * xs + c];
+    }
+    for (int i = 0; r < r1; ++r, ++i) s[i] += (double)x[(size_t)r * xs + c];
+    part[(size_t)blockIdx.x * (gridDim.y * 256) + c] = (s[0] + s[1]) + (s[2] + s[3]);
+}
+
+// ---- the token mix -------------------------------------------------------------------------------------------------------------
+struct MixArgs {
+    int groups, gpw;                        // groups in all; per workgroup of the backward
+    int per_img, fw, HW, by, bx, sy, sx;    // base(group) = image * HW + iy * by + ix * bx, (iy, ix) = the group's place in its image
+    const float *wt, *bt;                   // [64,64], [64]
+    const float *cn, *gb;                   // LayerNorm(c) [N,256]; gelu(hb) [N,512], a = its lower half
+    float *mixp1, *gated;                   // forward: mix + 1, a * (mix + 1)  [N,256]
+    const float *dgated, *hb, *mixp1_in;    // backward
+    float *dhb, *dcn;                       // dhb [N,512], its lower half written here; dcn [N,256]
+    double *part;                           // [4 * PW][kMixPart]
+};
+
+__device__ __forceinline__ size_t group_base(const MixArgs &a, int g) {
+    const int img = g / a.per_img, rem = g - img * a.per_img, iy = rem / a.fw, ix = rem - iy * a.fw;
+    return (size_t)img * a.HW + (size_t)iy * a.by + (size_t)ix * a.bx;
+}
+__device__ __forceinline__ size_t token_pixel(const MixArgs &a, size_t base, int t) {
+    return base + (size_t)((t >> 3) * a.sy + (t & 7) * a.sx);
+}
+
+typedef float (*MixTile)[kMixPitch];
+
+// TRANSPOSE: sW[q][p] = Wt[p][q] (forward: the MFMA's A operand is (m = p, k = q)); else sW[p][q] (backward: (m = q, k = p))
+template <bool TRANSPOSE>
+__device__ __forceinline__ void load_wt(const float *wt, MixTile sW) {
+    for (int e = threadIdx.x; e < kTok * kTok; e += 256) {
+        const int p = e >> 6, q = e & 63;
+        if (TRANSPOSE) sW[q][p] = wt[e];
+        else sW[p][q] = wt[e];
+    }
+}
+
+__device__ __forceinline__ void zero_acc(gf4 (&acc)[4][4]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = gf4{0.0f, 0.0f, 0.0f, 0.0f};
+}
+
+// a workgroup per group: mix[p][ch] = sum_q Wt[p][q] cn[q][ch] + bt[p], q ascending; mixp1 = mix + 1; gated = a * mixp1
+__global__ __launch_bounds__(256) void mix_fwd_kernel(MixArgs a) {
+    __shared__ float sW[kTok][kMixPitch];
+    __shared__ float sB[kTok];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4, li = lane & 15;
+    load_wt<true>(a.wt, sW);
+    if (threadIdx.x < kTok) sB[threadIdx.x] = a.bt[threadIdx.x];
+    __syncthreads();
+    const size_t base = group_base(a, blockIdx.x);
+    const int ch = 64 * wave + 4 * li;
+    gf4 acc[4][4];
+    zero_acc(acc);
+#pragma unroll 4
+    for (int ks = 0; ks < kTok / 4; ++ks) {
+        const int k = 4 * ks + q;
+        const gf4 b = ld4(a.cn + token_pixel(a, base, k) * kC + ch);
+        float w[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) w[i] = sW[k][16 * i + li];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[i], b[j], acc[i][j], 0, 0, 0);
+    }
+    // tile (i, j), register r: token 16 i + 4 q + r, channel ch + j
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int m = 16 * i + 4 * q + r;
+            const size_t pix = token_pixel(a, base, m);
+            const float bias = sB[m];
+            const gf4 av = ld4(a.gb + pix * kC2 + ch);
+            gf4 mp, gt;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                mp[j] = (acc[i][j][r] + bias) + 1.0f;
+                gt[j] = av[j] * mp[j];
+            }
+            st4(a.mixp1 + pix * kC + ch, mp);
+            st4(a.gated + pix * kC + ch, gt);
+        }
+}
+
+// a workgroup per gpw consecutive groups.  Per group: dmix = dgated * a;  dhb(lower half) = dgated * mixp1 * gelu'(hb);
+// dcn[q][ch] = sum_p Wt[p][q] dmix[p][ch], p ascending;  then, over the wave's own 64 channels, dWt[p][q] += sum_ch dmix[p][ch]
+// cn[q][ch] (lane quarter k of step s takes channel 16 k + s of the 64: four 16-byte loads cover the sixteen steps) and dbt[p] +=
+// sum_ch dmix[p][ch].  The groups of the workgroup are added in float64 registers, in group order.
+__global__ __launch_bounds__(256) void mix_bwd_kernel(MixArgs a) {
+    __shared__ float sW[kTok][kMixPitch];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4, li = lane & 15;
+    load_wt<false>(a.wt, sW);
+    __syncthreads();
+    const int ch = 64 * wave + 4 * li;
+    double wacc[4][4][4], bsum[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        bsum[i] = 0.0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) wacc[i][j][r] = 0.0;
+    }
+    const int g0 = blockIdx.x * a.gpw, g1 = min(a.groups, g0 + a.gpw);
+    for (int g = g0; g < g1; ++g) {
+        const size_t base = group_base(a, g);
+        gf4 acc[4][4];
+        zero_acc(acc);
+#pragma unroll 4
+        for (int ks = 0; ks < kTok / 4; ++ks) {
+            const int k = 4 * ks + q;
+            const size_t pix = token_pixel(a, base, k);
+            const gf4 dg = ld4(a.dgated + pix * kC + ch), av = ld4(a.gb + pix * kC2 + ch);
+            const gf4 mp = ld4(a.mixp1_in + pix * kC + ch), hv = ld4(a.hb + pix * kC2 + ch);
+            const gf4 dm = dg * av;
+            gf4 dh;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) dh[j] = (dg[j] * mp[j]) * gelu_grad(hv[j]);
+            st4(a.dhb + pix * kC2 + ch, dh);
+            float w[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) w[i] = sW[k][16 * i + li];
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[i], dm[j], acc[i][j], 0, 0, 0);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const size_t pix = token_pixel(a, base, 16 * i + 4 * q + r);
+                st4(a.dcn + pix * kC + ch, gf4{acc[i][0][r], acc[i][1][r], acc[i][2][r], acc[i][3][r]});
+            }
+        // dWt over channels 64 wave + 16 q + s: the A operand (m = p = 16 i + li) is dmix, the B operand (n = q' = 16 j + li) is cn
+        zero_acc(acc);
+        size_t pa[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) pa[i] = token_pixel(a, base, 16 * i + li);
+        const int c0 = 64 * wave + 16 * q;
+#pragma unroll
+        for (int s4 = 0; s4 < 4; ++s4) {
+            gf4 am[4], bc[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                am[i] = ld4(a.dgated + pa[i] * kC + c0 + 4 * s4) * ld4(a.gb + pa[i] * kC2 + c0 + 4 * s4);
+                bc[i] = ld4(a.cn + pa[i] * kC + c0 + 4 * s4);
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    bsum[i] += (double)am[i][e];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(am[i][e], bc[j][e], acc[i][j], 0, 0, 0);
+                }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) wacc[i][j][r] += (double)acc[i][j][r];
+    }
+    double *out = a.part + ((size_t)blockIdx.x * 4 + wave) * kMixPart;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) out[(16 * i + 4 * q + r) * kTok + 16 * j + li] = wacc[i][j][r];
+        double v = bsum[i];                 // token 16 i + li over this lane's sixteen channels: add the four quarters
+        v += __shfl_xor(v, 16);
+        v += __shfl_xor(v, 32);
+        if (q == 0) out[kTok * kTok + 16 * i + li] = v;
+    }
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------------------
+int check_sizes(int B, int Hc, int Wc) {
+    if (B < 1 || B > kMaxPairs || Hc < 1 || Wc < 1) return BALF_ERR_ARG;
+    if (Hc % 8 || Wc % 8) return BALF_ERR_SHAPE;            // the 8 x 8 grid and the 8 x 8 blocks
+    if ((long)B * (long)Hc * (long)Wc > (long)kMaxN) return BALF_ERR_SHAPE;
+    return BALF_OK;
+}
+
+bool misaligned(const void *p, unsigned mask) { return ((uintptr_t)p & mask) != 0; }
+
+MixArgs mix_args(const Layout &l, bool grid) {
+    MixArgs m{};
+    const int fh = l.Hc / 8, fw = l.Wc / 8;
+    m.groups = l.groups; m.gpw = l.gpw;
+    m.per_img = fh * fw; m.fw = fw; m.HW = l.Hc * l.Wc;
+    if (grid) { m.by = l.Wc; m.bx = 1; m.sy = fh * l.Wc; m.sx = fw; }     // group = a place inside the region, token = the region
+    else { m.by = 8 * l.Wc; m.bx = 8; m.sy = l.Wc; m.sx = 1; }            // group = a block, token = a place inside the block
+    return m;
+}
+
+// C[pixel][n] = epilogue(sum_k A[pixel * lda + k] * W(k, n)), n < Nn, k < K: TRANSPOSED = false reads W[n][k] (x W^T), true reads
+// W[k][n] (x W)
+template <int EPI, bool TRANSPOSED>
+void pixel_gemm(const float *A, size_t lda, int K, const float *W, int Nn, int N, float *C, size_t ldc, const float *bias,
+                const float *mask, hipStream_t st) {
+    GemmArgs g{};
+    g.A = A; g.a_sm = lda; g.a_sk = 1;
+    g.B = W; g.b_sn = TRANSPOSED ? 1 : K; g.b_sk = TRANSPOSED ? Nn : 1;
+    g.M = N; g.Nn = Nn; g.K = K; g.k_rows = K;
+    g.C = C; g.c_sm = ldc; g.bias = bias; g.mask = mask;
+    launch_gemm<true, !TRANSPOSED, false, EPI>(g, st);
+}
+
+// out[o][k] = fl32(sum_pixel D[pixel * ldd + o] * X[pixel * ldx + k]), o < M, k < Nn, in S slices of the pixels, the slabs added in
+// float64
+void weight_grad(const float *D, size_t ldd, int M, const float *X, size_t ldx, int Nn, const Layout &l, float *out, hipStream_t st) {
+    GemmArgs g{};
+    g.A = D; g.a_sm = 1; g.a_sk = ldd;
+    g.B = X; g.b_sn = 1; g.b_sk = ldx;
+    g.M = M; g.Nn = Nn; g.K = l.N; g.k_rows = l.rows;
+    g.C = l.slab; g.c_sm = Nn; g.c_sz = (size_t)M * Nn;
+    launch_gemm<false, false, false, EPI_STORE>(g, st);
+    slab_sum_kernel<<<M * Nn / 256, 256, 0, st>>>(l.slab, l.S, M * Nn, out);
+}
+
+// out[c] = fl32(sum over the PC float64 partials of column c), c < cols
+void finish_cols(const double *part, int cols, const Layout &l, float *out, hipStream_t st) {
+    partial_sum_kernel<<<cols / 4, 256, 0, st>>>(part, cols, l.PC, 1, (size_t)cols, out, nullptr);
+}
+
+int check_call(const float *const *params, const void *const *others, int n_others, const void *const *aligned, int n_aligned) {
+    if (!params) return BALF_ERR_ARG;
+    for (int i = 0; i < kParams; ++i)
+        if (!params[i] || misaligned(params[i], 15)) return BALF_ERR_ARG;
+    for (int i = 0; i < n_others; ++i)
+        if (!others[i]) return BALF_ERR_ARG;
+    for (int i = 0; i < n_aligned; ++i)
+        if (misaligned(aligned[i], 15)) return BALF_ERR_ARG;
+    return BALF_OK;
+}
+
+}  // namespace
+}  // namespace balf
+
+using namespace balf;
+
+extern "C" size_t balf_gmlp_train_workspace_bytes(int B, int Hc, int Wc) {
+    if (check_sizes(B, Hc, Wc) != BALF_OK) return 0;
+    size_t bytes = 0;
+    make_layout(B, Hc, Wc, nullptr, nullptr, nullptr, &bytes);
+    return bytes;
+}
+
+extern "C" size_t balf_gmlp_train_saved_bytes(int B, int Hc, int Wc) {
+    if (check_sizes(B, Hc, Wc) != BALF_OK) return 0;
+    size_t bytes = 0;
+    make_layout(B, Hc, Wc, nullptr, nullptr, &bytes, nullptr);
+    return bytes;
+}
+
+extern "C" int balf_gmlp_train_forward(const float *x0_dev, const float *const *params, int B, int Hc, int Wc, float *y_dev,
+                                       void *saved_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
+    const void *ptrs[] = {x0_dev, y_dev, saved_dev, workspace_dev};
+    int rc = check_call(params, ptrs, 4, ptrs, 4);
+    if (rc != BALF_OK) return rc;
+    rc = check_sizes(B, Hc, Wc);
+    if (rc != BALF_OK) return rc;
+    if (workspace_bytes < balf_gmlp_train_workspace_bytes(B, Hc, Wc)) return BALF_ERR_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const Layout l = make_layout(B, Hc, Wc, static_cast<char *>(saved_dev), static_cast<char *>(workspace_dev), nullptr, nullptr);
+    const int N = l.N, ln_blocks = balf_ceil_div(N, kLnFwdPix);
+    const float *const *P = params;
+
+    ln_fwd_kernel<<<ln_blocks, 256, 0, st>>>(x0_dev, P[0], P[1], N, l.n0, l.stat0);
+    BALF_LAUNCH_CHECK();
+    pixel_gemm<EPI_BIAS_N_GELU, false>(l.n0, kC, kC, P[2], kC2, N, l.g0, kC2, P[3], l.h0, st);      // (u, v) = gelu(n0 W1^T + b1)
+    BALF_LAUNCH_CHECK();
+    for (int k = 0; k < 2; ++k) {
+        const Branch &b = l.br[k];
+        const float *const *Q = P + 4 + kBranchParams * k;
+        const float *z = l.g0 + kC * k;                                                              // u or v, row stride 512
+        ln_fwd_s_kernel<<<ln_blocks, 256, 0, st>>>(z, kC2, Q[0], Q[1], N, b.nb, b.statb);
+        BALF_LAUNCH_CHECK();
+        pixel_gemm<EPI_BIAS_N_GELU, false>(b.nb, kC, kC, Q[2], kC2, N, b.gb, kC2, Q[3], b.hb, st);   // (a, c)
+        BALF_LAUNCH_CHECK();
+        ln_fwd_s_kernel<<<ln_blocks, 256, 0, st>>>(b.gb + kC, kC2, Q[4], Q[5], N, b.cn, b.statg);
+        BALF_LAUNCH_CHECK();
+        MixArgs m = mix_args(l, k == 0);
+        m.wt = Q[6]; m.bt = Q[7]; m.cn = b.cn; m.gb = b.gb; m.mixp1 = b.mixp1; m.gated = b.gated;
+        mix_fwd_kernel<<<l.groups, 256, 0, st>>>(m);
+        BALF_LAUNCH_CHECK();
+        pixel_gemm<EPI_BIAS_N_ADD, false>(b.gated, kC, kC, Q[8], kC, N, l.cat + kC * k, kC2, Q[9], z, st);   // z' = z + gated Wb2^T + bb2
+        BALF_LAUNCH_CHECK();
+    }
+    pixel_gemm<EPI_BIAS_N_ADD, false>(l.cat, kC2, kC2, P[24], kC, N, y_dev, kC, P[25], x0_dev, st);  // y = cat W2^T + b2 + x0
+    BALF_LAUNCH_CHECK();
+    return BALF_OK;
+}
+
+extern "C" int balf_gmlp_train_backward(const float *dy_dev, const float *x0_dev, const float *const *params, const void *saved_dev,
+                                        int B, int Hc, int Wc, float *const *grads, float *dx0_dev, void *workspace_dev,
+                                        size_t workspace_bytes, void *stream) {
+    const void *ptrs[] = {dy_dev, x0_dev, saved_dev, workspace_dev, dx0_dev};
+    int rc = check_call(params, ptrs, 4, ptrs, 5);
+    if (rc != BALF_OK) return rc;
+    if (!grads) return BALF_ERR_ARG;
+    for (int i = 0; i < kParams; ++i)
+        if (!grads[i]) return BALF_ERR_ARG;
+    rc = check_sizes(B, Hc, Wc);
+    if (rc != BALF_OK) return rc;
+    if (workspace_bytes < balf_gmlp_train_workspace_bytes(B, Hc, Wc)) return BALF_ERR_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const Layout l = make_layout(B, Hc, Wc, static_cast<char *>(const_cast<void *>(saved_dev)), static_cast<char *>(workspace_dev),
+                                 nullptr, nullptr);
+    const int N = l.N;
+    const float *const *P = params;
+    float *const *G = grads;
+    double *part0 = l.col_part, *part1 = l.col_part + (size_t)l.PC * kC2;
+
+    // y = cat W2^T + b2 + x0:  db2 = sum dy,  dW2 = dy^T cat,  dcat = dy W2
+    col_sum_kernel<<<l.PC, kC, 0, st>>>(dy_dev, N, l.col_rows, part0);
+    BALF_LAUNCH_CHECK();
+    finish_cols(part0, kC, l, G[25], st);
+    BALF_LAUNCH_CHECK();
+    weight_grad(dy_dev, kC, kC, l.cat, kC2, kC2, l, G[24], st);
+    BALF_LAUNCH_CHECK();
+    pixel_gemm<EPI_STORE, true>(dy_dev, kC, kC, P[24], kC2, N, l.dcat, kC2, nullptr, nullptr, st);
+    BALF_LAUNCH_CHECK();
+    for (int k = 0; k < 2; ++k) {
+        const Branch &b = l.br[k];
+        const float *const *Q = P + 4 + kBranchParams * k;
+        float *const *D = G + 4 + kBranchParams * k;
+        const float *dzo = l.dcat + kC * k;                                                          // the gradient at z', row stride 512
+        // z' = z + gated Wb2^T + bb2
+        col_sum_s_kernel<<<dim3(l.PC, 1), 256, 0, st>>>(dzo, kC2, N, l.col_rows, part0);
+        BALF_LAUNCH_CHECK();
+        finish_cols(part0, kC, l, D[9], st);
+        BALF_LAUNCH_CHECK();
+        weight_grad(dzo, kC2, kC, b.gated, kC, kC, l, D[8], st);
+        BALF_LAUNCH_CHECK();
+        float *dgated = l.t0, *dcn = l.t1;
+        pixel_gemm<EPI_STORE, true>(dzo, kC2, kC, Q[8], kC, N, dgated, kC, nullptr, nullptr, st);
+        BALF_LAUNCH_CHECK();
+        // the gate and the token mix: dhb (a's half), dcn, dWt, dbt
+        MixArgs m = mix_args(l, k == 0);
+        m.wt = Q[6]; m.cn = b.cn; m.gb = b.gb; m.dgated = dgated; m.hb = b.hb; m.mixp1_in = b.mixp1; m.dhb = l.dhb; m.dcn = dcn;
+        m.part = l.mix_part;
+        mix_bwd_kernel<<<l.PW, 256, 0, st>>>(m);
+        BALF_LAUNCH_CHECK();
+        partial_sum_kernel<<<kTok * kTok / 4, 256, 0, st>>>(l.mix_part, kTok * kTok, 4 * l.PW, 1, (size_t)kMixPart, D[6], nullptr);
+        BALF_LAUNCH_CHECK();
+        partial_sum_kernel<<<kTok / 4, 256, 0, st>>>(l.mix_part + kTok * kTok, kTok, 4 * l.PW, 1, (size_t)kMixPart, D[7], nullptr);
+        BALF_LAUNCH_CHECK();
+        // the gating LayerNorm on c: dhb (c's half) = LN'(dcn) * gelu'(hb)
+        LnBwdSArgs s{};
+        s.N = N; s.rows = l.col_rows; s.dn = dcn; s.stat = b.statg; s.ln_g = Q[4];
+        s.x = b.gb + kC; s.xs = kC2; s.h = b.hb + kC; s.hs = kC2; s.out = l.dhb + kC; s.os = kC2;
+        s.part_g = part0; s.part_b = part1;
+        ln_bwd_s_kernel<false><<<l.PC, 256, 0, st>>>(s);
+        BALF_LAUNCH_CHECK();
+        finish_cols(part0, kC, l, D[4], st);
+        BALF_LAUNCH_CHECK();
+        finish_cols(part1, kC, l, D[5], st);
+        BALF_LAUNCH_CHECK();
+        // hb = nb Wb1^T + bb1
+        col_sum_s_kernel<<<dim3(l.PC, 2), 256, 0, st>>>(l.dhb, kC2, N, l.col_rows, part0);
+        BALF_LAUNCH_CHECK();
+        finish_cols(part0, kC2, l, D[3], st);
+        BALF_LAUNCH_CHECK();
+        weight_grad(l.dhb, kC2, kC2, b.nb, kC, kC, l, D[2], st);
+        BALF_LAUNCH_CHECK();
+        float *dnb = l.t0;                                                                           // dgated is spent
+        pixel_gemm<EPI_STORE, true>(l.dhb, kC2, kC2, Q[2], kC, N, dnb, kC, nullptr, nullptr, st);
+        BALF_LAUNCH_CHECK();
+        // the branch's LayerNorm on z and its shortcut: dh0 (this half) = (dzo + LN'(dnb)) * gelu'(h0)
+        s = LnBwdSArgs{};
+        s.N = N; s.rows = l.col_rows; s.dn = dnb; s.stat = b.statb; s.ln_g = Q[0];
+        s.x = l.g0 + kC * k; s.xs = kC2; s.g = dzo; s.gs = kC2; s.h = l.h0 + kC * k; s.hs = kC2; s.out = l.dh0 + kC * k; s.os = kC2;
+        s.part_g = part0; s.part_b = part1;
+        ln_bwd_s_kernel<true><<<l.PC, 256, 0, st>>>(s);
+        BALF_LAUNCH_CHECK();
+        finish_cols(part0, kC, l, D[0], st);
+        BALF_LAUNCH_CHECK();
+        finish_cols(part1, kC, l, D[1], st);
+        BALF_LAUNCH_CHECK();
+    }
+    // h0 = n0 W1^T + b1
+    col_sum_s_kernel<<<dim3(l.PC, 2), 256, 0, st>>>(l.dh0, kC2, N, l.col_rows, part0);
+    BALF_LAUNCH_CHECK();
+    finish_cols(part0, kC2, l, G[3], st);
+    BALF_LAUNCH_CHECK();
+    weight_grad(l.dh0, kC2, kC2, l.n0, kC, kC, l, G[2], st);
+    BALF_LAUNCH_CHECK();
+    float *dn0 = l.t0;
+    pixel_gemm<EPI_STORE, true>(l.dh0, kC2, kC2, P[2], kC, N, dn0, kC, nullptr, nullptr, st);
+    BALF_LAUNCH_CHECK();
+    // the layer's LayerNorm and its shortcut: dx0 = dy + LN'(dn0)
+    LnBwdArgs n{};
+    n.N = N; n.rows = l.col_rows; n.dn = dn0; n.y = x0_dev; n.stat = l.stat0; n.ln_g = P[0]; n.g = dy_dev; n.dy = dx0_dev;
+    n.part_g = part0; n.part_b = part1;
+    n.vec_g = true; n.vec_dy = true;
+    if (dx0_dev) ln_bwd_kernel<true><<<l.PC, 256, 0, st>>>(n);
+    else ln_bwd_kernel<false><<<l.PC, 256, 0, st>>>(n);
+    BALF_LAUNCH_CHECK();
+    finish_cols(part0, kC, l, G[0], st);
+    BALF_LAUNCH_CHECK();
+    finish_cols(part1, kC, l, G[1], st);
+    BALF_LAUNCH_CHECK();
+    return BALF_OK;
+}

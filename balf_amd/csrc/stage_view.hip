@@ -45,6 +45,29 @@ __global__ void rcab_y_kernel(const float *r, float *y, size_t n) {
     if (i < n) y[i] = r[i] - y[i];
 }
 
+// x0[pixel][o] = relu(sum_k x3[pixel][k] * W[o][k] + b[o]) from the resident stage-3 output with the training GEMM; on the split-f16
+// path x3 is de-fragmented into scratch first (pixels * 128 floats)
+int stage4_input(int precision, const char *ws, const Plan &pl, int B, int Hp, int Wp, const float *conv0_w, const float *conv0_b,
+                 float *x0, float *scratch, hipStream_t st) {
+    const int C3 = kC[2], C4 = kC[3];
+    const size_t pix = (size_t)B * (Hp / 8) * (Wp / 8);
+    const float *x3 = reinterpret_cast<const float *>(ws + pl.off_X[2]);
+    if (precision == BALF_PREC_FP16) {
+        hipLaunchKernelGGL(view_frag_kernel, dim3((unsigned)((pix * C3 + 255) / 256)), dim3(256), 0, st, ws + pl.off_X[2], (long)pix, C3,
+                           kFmt32[3] ? 1 : 0, scratch);
+        BALF_LAUNCH_CHECK();
+        x3 = scratch;
+    }
+    GemmArgs g{};
+    g.A = x3; g.a_sm = C3; g.a_sk = 1;
+    g.B = conv0_w; g.b_sn = C3; g.b_sk = 1;
+    g.M = (int)pix; g.Nn = C4; g.K = C3; g.k_rows = C3;
+    g.C = x0; g.c_sm = C4; g.bias = conv0_b;
+    launch_gemm<true, true, false, EPI_BIAS_N_RELU>(g, st);
+    BALF_LAUNCH_CHECK();
+    return BALF_OK;
+}
+
 }  // namespace
 }  // namespace balf
 
@@ -99,25 +122,27 @@ extern "C" int balf_forward_rcab_inputs(int precision, const void *workspace_dev
     if (B > pl.mb) return BALF_ERR_ARG;                          // only the last micro-batch of a forward is resident
     const char *ws = static_cast<const char *>(workspace_dev);
     hipStream_t st = (hipStream_t)stream;
-    const int C3 = kC[2], C4 = kC[3];
-    const size_t pix = (size_t)B * (Hp / 8) * (Wp / 8), n = pix * C4;
-    const float *x3 = reinterpret_cast<const float *>(ws + pl.off_X[2]);
-    if (precision == BALF_PREC_FP16) {
-        hipLaunchKernelGGL(view_frag_kernel, dim3((unsigned)((pix * C3 + 255) / 256)), dim3(256), 0, st, ws + pl.off_X[2], (long)pix, C3,
-                           kFmt32[3] ? 1 : 0, r_dev);
-        BALF_LAUNCH_CHECK();
-        x3 = r_dev;
-    }
-    // x0[pixel][o] = relu(sum_k x3[pixel][k] * W[o][k] + b[o])
-    GemmArgs g{};
-    g.A = x3; g.a_sm = C3; g.a_sk = 1;
-    g.B = conv0_w_dev; g.b_sn = C3; g.b_sk = 1;
-    g.M = (int)pix; g.Nn = C4; g.K = C3; g.k_rows = C3;
-    g.C = y_dev; g.c_sm = C4; g.bias = conv0_b_dev;
-    launch_gemm<true, true, false, EPI_BIAS_N_RELU>(g, st);
-    BALF_LAUNCH_CHECK();
+    const size_t n = (size_t)B * (Hp / 8) * (Wp / 8) * kC[3];
+    const int rc = stage4_input(precision, ws, pl, B, Hp, Wp, conv0_w_dev, conv0_b_dev, y_dev, r_dev, st);
+    if (rc != BALF_OK) return rc;
     if (hipMemcpyAsync(r_dev, ws + pl.off_R, n * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return BALF_ERR_LAUNCH;
     hipLaunchKernelGGL(rcab_y_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, r_dev, y_dev, n);
     BALF_LAUNCH_CHECK();
     return BALF_OK;
+}
+
+// The input of stage 4's gMLP layer for training (balf_gmlp_train_forward): x0, the first half of balf_forward_rcab_inputs.
+extern "C" int balf_forward_gmlp_input(int precision, const void *workspace_dev, size_t workspace_bytes, int B, int Hp, int Wp,
+                                       const float *conv0_w_dev, const float *conv0_b_dev, float *x0_dev, float *scratch_dev,
+                                       void *stream) {
+    using namespace balf;
+    if (!workspace_dev || !conv0_w_dev || !conv0_b_dev || !x0_dev || B <= 0) return BALF_ERR_ARG;
+    if (precision != BALF_PREC_FP32 && precision != BALF_PREC_FP16) return BALF_ERR_ARG;
+    if (precision == BALF_PREC_FP16 && !scratch_dev) return BALF_ERR_ARG;
+    if (Hp <= 0 || Wp <= 0 || Hp % 64 || Wp % 64) return BALF_ERR_SHAPE;
+    const Plan pl = make_plan(B, Hp, Wp);
+    if (workspace_bytes < pl.total) return BALF_ERR_WORKSPACE;
+    if (B > pl.mb) return BALF_ERR_ARG;                          // only the last micro-batch of a forward is resident
+    return stage4_input(precision, static_cast<const char *>(workspace_dev), pl, B, Hp, Wp, conv0_w_dev, conv0_b_dev, x0_dev, scratch_dev,
+                        (hipStream_t)stream);
 }

@@ -1,4 +1,5 @@
-// The shared pieces of the training kernels (head_train.hip, rcab_train.hip, and the x0 recomputation of stage_view.hip):
+// The shared pieces of the training kernels (head_train.hip, rcab_train.hip, gmlp_train.hip, and the x0 recomputation of
+// stage_view.hip):
 //   * gemm_kernel: ONE LDS-tiled GEMM on v_mfma_f32_16x16x4_f32 (exact fp32 fma chains, k ascending).  A workgroup of four waves
 //     owns a 64 x 64 tile of C[m][n] = sum_k A(m,k) * B(k,n), a wave a 32 x 32 quarter (2 x 2 MFMA tiles); K goes through LDS in
 //     steps of 16 with the next step's operands fetched into registers before the MFMAs of this one.  The operands are addressed
@@ -28,8 +29,19 @@ int rows_per_slice(int N) {
 
 // ---- the GEMM -----------------------------------------------------------------------------------------------------------------
 // EPI_BIAS_N: + bias[n];  EPI_BIAS_N_LRELU: + bias[n], then v > 0 ? v : 0.2 v;  EPI_LRELU_MASK: mask > 0 ? v : 0.2 v (the LeakyReLU's
-// derivative from its OUTPUT: the output has the sign of the input, and 0.2 at 0 as torch)
-enum { EPI_STORE = 0, EPI_BIAS_N_RELU = 1, EPI_BIAS_M = 2, EPI_RELU_MASK = 3, EPI_BIAS_N = 4, EPI_BIAS_N_LRELU = 5, EPI_LRELU_MASK = 6 };
+// derivative from its OUTPUT: the output has the sign of the input, and 0.2 at 0 as torch);  EPI_BIAS_N_GELU: h = v + bias[n] is
+// STORED at mask's place (the pre-activation, which the backward takes the derivative from) and C gets gelu(h), the exact erf
+// form;  EPI_BIAS_N_ADD: (v + bias[n]) + mask, a shortcut laid out as C
+enum { EPI_STORE = 0, EPI_BIAS_N_RELU = 1, EPI_BIAS_M = 2, EPI_RELU_MASK = 3, EPI_BIAS_N = 4, EPI_BIAS_N_LRELU = 5, EPI_LRELU_MASK = 6,
+       EPI_BIAS_N_GELU = 7, EPI_BIAS_N_ADD = 8 };
+
+// Phi(h), the normal distribution function, from erfc: no cancellation in the lower tail
+__device__ __forceinline__ float normal_cdf(float h) { return 0.5f * erfcf(-0.70710678118654752f * h); }
+// gelu(h) = h Phi(h) (nn.GELU(), approximate = 'none') and its derivative Phi(h) + h phi(h)
+__device__ __forceinline__ float gelu_exact(float h) { return h * normal_cdf(h); }
+__device__ __forceinline__ float gelu_grad(float h) {
+    return fmaf(h, 0.39894228040143268f * expf(-0.5f * h * h), normal_cdf(h));
+}
 
 struct GemmArgs {
     const float *A, *B;
@@ -37,7 +49,7 @@ struct GemmArgs {
     int M, Nn, K, k_rows;                   // slice z sums k in [z * k_rows, min(K, (z + 1) * k_rows))
     float *C;
     size_t c_sm, c_sz;                      // C[z * c_sz + m * c_sm + n]
-    const float *bias, *mask;               // the epilogue's: bias[n] or bias[m]; mask as C (EPI_RELU_MASK)
+    const float *bias, *mask;               // the epilogue's: bias[n] or bias[m]; mask as C (EPI_RELU_MASK; written by EPI_BIAS_N_GELU)
 };
 
 // A_K / B_K: the operand is contiguous along k (else along m / n) -- decides which way the 256 threads walk its 64 x 16 tile
@@ -113,6 +125,8 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs g) {
                 if (EPI == EPI_BIAS_N) v = v + g.bias[n];
                 if (EPI == EPI_BIAS_N_LRELU) { v = v + g.bias[n]; v = v > 0.0f ? v : 0.2f * v; }
                 if (EPI == EPI_LRELU_MASK) v = g.mask[at] > 0.0f ? v : 0.2f * v;
+                if (EPI == EPI_BIAS_N_GELU) { v = v + g.bias[n]; const_cast<float *>(g.mask)[at] = v; v = gelu_exact(v); }
+                if (EPI == EPI_BIAS_N_ADD) v = (v + g.bias[n]) + g.mask[at];
                 g.C[(size_t)blockIdx.z * g.c_sz + at] = v;
             }
 }

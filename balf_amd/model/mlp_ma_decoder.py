@@ -250,7 +250,10 @@ class MLP_MA_DECODER(nn.Module):
         return self._forward("f32", (b, h, w), x.contiguous().float(), b, h, w, want_logits)
 
     def encode(self, x: torch.Tensor, chunk=None, level: str = "x2"):
-        """``level="rcab"``: one block earlier -- ``(y, r)``, the input of stage 4's channel-attention block and y + the long
+        """``level="gmlp"``: two blocks earlier -- ``x0``, the input of stage 4's multi-axis gated-MLP layer, [B,H/8,W/8,256]
+        float32 NHWC, what ``model.mixer_train.TrainableMixerTail`` trains on (balf_forward_gmlp_input).
+
+        ``level="rcab"``: one block earlier -- ``(y, r)``, the input of stage 4's channel-attention block and y + the long
         shortcut, each [B,H/8,W/8,256] float32 NHWC, what ``model.tail_train.TrainableTail`` trains on (balf_forward_rcab_inputs
         with the module's own ``down4.conv.0``); chunked and guarded exactly as the default level, which is:
 
@@ -272,8 +275,8 @@ class MLP_MA_DECODER(nn.Module):
             raise ValueError(f"H and W must be multiples of 64 (pad with mod_padding_symmetric), got {h}x{w}")
         if b < 1:
             raise ValueError("encode: an empty batch")
-        if level not in ("x2", "rcab"):
-            raise ValueError(f"encode: level must be 'x2' or 'rcab', got {level!r}")
+        if level not in ("x2", "rcab", "gmlp"):
+            raise ValueError(f"encode: level must be 'x2', 'rcab' or 'gmlp', got {level!r}")
         x = x.contiguous().float()
         l = lib()
         mb = l.balf_forward_micro_batch(b, h, w)
@@ -281,6 +284,7 @@ class MLP_MA_DECODER(nn.Module):
         out = torch.empty((b, h // 8, w // 8, 256), dtype=torch.float32, device=x.device)
         if level == "rcab":
             r = torch.empty_like(out)
+        if level != "x2":
             conv0 = self.down4.conv[0]
             w0, b0 = conv0.weight.detach().float().contiguous(), conv0.bias.detach().float().contiguous()
         with torch.no_grad():
@@ -290,6 +294,9 @@ class MLP_MA_DECODER(nn.Module):
                 ws = ops._workspace("forward", x.device, l.balf_forward_workspace_bytes(nb, h, w))
                 if level == "rcab":
                     ops.rcab_inputs(self._code_of(self.effective_precision), ws, nb, h, w, w0, b0, out[at:at + nb], r[at:at + nb])
+                    continue
+                if level == "gmlp":
+                    ops.gmlp_input(self._code_of(self.effective_precision), ws, nb, h, w, w0, b0, out[at:at + nb])
                     continue
                 with torch.cuda.device(x.device):
                     check(l.balf_forward_stage_view(self._code_of(self.effective_precision), ws.data_ptr(), ws.numel(), nb, h, w, 4,

@@ -18,7 +18,8 @@ from .head_train import TrainableHead
 
 class _RcabTrain(torch.autograd.Function):
     """Forward keeps the kernel's ``saved`` block; backward is one balf_rcab_train_backward call (dy only if ``y`` requires a
-    gradient).  ``r`` = y + the long shortcut is a constant of the frozen encoder here: no gradient is returned for it."""
+    gradient).  ``r`` = y + the long shortcut is a constant of the frozen encoder for ``TrainableTail``; when it does require a
+    gradient (``model.mixer_train.TrainableMixerTail`` with an input that requires one) that gradient is dx2 itself."""
 
     @staticmethod
     def forward(ctx, y, r, *params):
@@ -32,7 +33,7 @@ class _RcabTrain(torch.autograd.Function):
     def backward(ctx, dx2):
         y, ln_g, wc1, wc2, ws0, ws2, saved = ctx.saved_tensors
         g = ops.rcab_train_backward(dx2.contiguous(), y, ln_g, wc1, wc2, ws0, ws2, saved, want_dy=ctx.needs_input_grad[0])
-        return (g.dy, None) + tuple(g[:10])
+        return (g.dy, dx2 if ctx.needs_input_grad[1] else None) + tuple(g[:10])
 
 
 class _Holder(nn.Module):
@@ -92,9 +93,9 @@ class TrainableTail(nn.Module):
         only for ``y``).  ``eval()`` mode: the same arithmetic without a graph, and the head in eval mode."""
         y, r = features
         params = self.rcab_parameters()
-        wanted = y.requires_grad or any(p.requires_grad for p in params)
+        wanted = y.requires_grad or r.requires_grad or any(p.requires_grad for p in params)
         if self.training and torch.is_grad_enabled() and wanted:
-            x2 = _RcabTrain.apply(y, r.detach(), *params)
+            x2 = _RcabTrain.apply(y, r, *params)
         else:
             x2 = ops.rcab_train_forward(y.detach(), r.detach(), tuple(p.detach() for p in params)).x2
         return self.head(x2, want_prob=want_prob)

@@ -816,3 +816,138 @@ def rcab_inputs(precision: int, workspace: torch.Tensor, b: int, hp: int, wp: in
         check(lib().balf_forward_rcab_inputs(precision, workspace.data_ptr(), workspace.numel(), b, hp, wp, conv0_w.data_ptr(),
                                              conv0_b.data_ptr(), y.data_ptr(), r.data_ptr(), current_stream_ptr(dev)),
               "balf_forward_rcab_inputs")
+
+
+_GMLP_BRANCH = ("norm.weight", "norm.bias", "dense1.weight", "dense1.bias", "{u}.norm.weight", "{u}.norm.bias", "{u}.dense.weight",
+                "{u}.dense.bias", "dense2.weight", "dense2.bias")
+_GMLP_BRANCH_SHAPES = ((256,), (256,), (512, 256), (512,), (256,), (256,), (64, 64), (64,), (256, 256), (256,))
+# the 26 parameters of down4.residual_split_head_multi_axis_gmlp_layer under their state-dict names, in the order of
+# include/balf_hip.h
+GMLP_PARAMS = (("norm.weight", "norm.bias", "dense1.weight", "dense1.bias")
+               + tuple(f"{layer}.{n.format(u=unit)}" for layer, unit in (("grid_gmlp_layer", "grid_gating_unit"),
+                                                                         ("block_gmlp_layer", "block_gating_unit"))
+                       for n in _GMLP_BRANCH)
+               + ("dense2.weight", "dense2.bias"))
+_GMLP_PARAM_SHAPES = dict(zip(GMLP_PARAMS, ((256,), (256,), (512, 256), (512,)) + 2 * _GMLP_BRANCH_SHAPES + ((256, 512), (256,))))
+
+
+class GmlpTrainForward(NamedTuple):
+    y: torch.Tensor                           # [B,Hc,Wc,256] float32: the input of stage 4's RCAB
+    saved: torch.Tensor                       # opaque uint8 block for gmlp_train_backward
+
+
+class GmlpTrainBackward(NamedTuple):
+    grads: Tuple[torch.Tensor, ...]           # the 26 gradients, in GMLP_PARAMS order
+    dx0: Optional[torch.Tensor]               # [B,Hc,Wc,256]
+
+
+def _gmlp_train_checks(x0, params, others):
+    """As _rcab_train_checks: metadata first, then the devices.  ``others``: (tensor or None, name, shape) triples.  Every tensor
+    but ``saved`` is float32, contiguous and starts on a 16-byte boundary of its storage.  -> (B, Hc, Wc)."""
+    if x0.dim() != 4 or x0.shape[3] != 256:
+        raise BalfHipError(f"x0 must be [B,Hc,Wc,256] (the input of stage 4's gMLP layer, NHWC), got {tuple(x0.shape)}")
+    b, hc, wc, _ = x0.shape
+    if not 1 <= b <= 65535 or hc < 1 or wc < 1 or hc % 8 or wc % 8 or b * hc * wc > 1 << 24:
+        raise BalfHipError(f"gmlp_train: 1 <= B <= 65535, Hc and Wc multiples of 8 and B * Hc * Wc <= 2^24, got {tuple(x0.shape)}")
+    params = tuple(params)
+    if len(params) != len(GMLP_PARAMS):
+        raise BalfHipError(f"gmlp_train takes the {len(GMLP_PARAMS)} parameters of ops.GMLP_PARAMS, got {len(params)}")
+    named = ((x0, "x0", None),) + tuple((t, k, _GMLP_PARAM_SHAPES[k]) for t, k in zip(params, GMLP_PARAMS)) + tuple(others)
+    for t, name, shape in named:
+        if t is None:
+            continue
+        if name == "saved":
+            if t.dtype != torch.uint8 or not t.is_contiguous():
+                raise BalfHipError("saved must be a contiguous uint8 tensor")
+            continue
+        if t.dtype != torch.float32:
+            raise BalfHipError(f"{name} must be float32, got {t.dtype}")
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise BalfHipError(f"{name} must be {list(shape)}, got {list(t.shape)}")
+        if not t.is_contiguous():
+            raise BalfHipError(f"{name} must be contiguous")
+        if t.storage_offset() * t.element_size() % 16:
+            raise BalfHipError(f"{name} must start on a 16-byte boundary of its storage")
+    for t, name, _ in named:
+        if t is not None:
+            require_gpu_tensor(t, name)
+            if t.device != x0.device:
+                raise BalfHipError(f"{name} is on {t.device}, x0 on {x0.device}")
+    return b, hc, wc, params
+
+
+def _pointer_array(tensors):
+    return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def gmlp_train_forward(x0: torch.Tensor, params, saved=None) -> GmlpTrainForward:
+    """Stage 4's multi-axis gated-MLP layer on ``x0`` [B,Hc,Wc,256] (``MLP_MA_DECODER.encode(level="gmlp")`` gives it):
+    balf_gmlp_train_forward in include/balf_hip.h.  ``params``: the 26 tensors in ``GMLP_PARAMS`` order, float32 and contiguous on
+    x0's GPU.  ``saved``: a uint8 block to reuse (at least balf_gmlp_train_saved_bytes), else allocated."""
+    b, hc, wc, params = _gmlp_train_checks(x0, params, ((saved, "saved", None),))
+    dev = x0.device
+    l = lib()
+    need = l.balf_gmlp_train_saved_bytes(b, hc, wc)
+    if saved is None:
+        saved = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif saved.numel() < need or saved.data_ptr() % 16:
+        raise BalfHipError(f"saved must be a 16-byte aligned uint8 tensor of at least {need} bytes")
+    y = torch.empty_like(x0)
+    ws = _workspace("gmlp_train", dev, l.balf_gmlp_train_workspace_bytes(b, hc, wc))
+    with torch.cuda.device(dev):
+        check(l.balf_gmlp_train_forward(x0.data_ptr(), _pointer_array(params), b, hc, wc, y.data_ptr(), saved.data_ptr(),
+                                        ws.data_ptr(), ws.numel(), current_stream_ptr(dev)), "balf_gmlp_train_forward")
+    return GmlpTrainForward(y, saved)
+
+
+def gmlp_train_backward(dy: torch.Tensor, x0: torch.Tensor, params, saved: torch.Tensor, want_dx0=False) -> GmlpTrainBackward:
+    """The backward of ``gmlp_train_forward`` (balf_gmlp_train_backward): ``dy`` [B,Hc,Wc,256] (``rcab_train_backward`` writes it)
+    and the ``saved`` block of that forward -> the 26 parameter gradients and, with ``want_dx0``, the gradient at the layer's input
+    through the layer (``want_dx0`` may be a contiguous float32 tensor of x0's shape to write into)."""
+    dx0 = want_dx0 if isinstance(want_dx0, torch.Tensor) else None
+    shape = tuple(x0.shape)
+    b, hc, wc, params = _gmlp_train_checks(x0, params, ((dy, "dy", shape), (saved, "saved", None), (dx0, "dx0", shape)))
+    dev = x0.device
+    l = lib()
+    if saved is None or saved.numel() < l.balf_gmlp_train_saved_bytes(b, hc, wc) or saved.data_ptr() % 16:
+        raise BalfHipError("saved must be the uint8 block that gmlp_train_forward returned for this shape")
+    if dx0 is None and want_dx0:
+        dx0 = torch.empty_like(x0)
+    out = tuple(torch.empty(_GMLP_PARAM_SHAPES[k], dtype=torch.float32, device=dev) for k in GMLP_PARAMS)
+    ws = _workspace("gmlp_train", dev, l.balf_gmlp_train_workspace_bytes(b, hc, wc))
+    with torch.cuda.device(dev):
+        check(l.balf_gmlp_train_backward(dy.data_ptr(), x0.data_ptr(), _pointer_array(params), saved.data_ptr(), b, hc, wc,
+                                         _pointer_array(out), _ptr(dx0), ws.data_ptr(), ws.numel(), current_stream_ptr(dev)),
+              "balf_gmlp_train_backward")
+    return GmlpTrainBackward(out, dx0)
+
+
+def gmlp_input(precision: int, workspace: torch.Tensor, b: int, hp: int, wp: int, conv0_w: torch.Tensor, conv0_b: torch.Tensor,
+               x0: torch.Tensor) -> None:
+    """After a forward of ``b`` padded ``hp x wp`` images whose workspace is ``workspace`` (balf_forward_gmlp_input): write the
+    input of stage 4's gMLP layer into ``x0`` [b,hp/8,wp/8,256], float32 and contiguous on the workspace's GPU; ``conv0_w``
+    [256,128], ``conv0_b`` [256] are ``down4.conv.0``.  ``precision``: _lib.PREC_FP32 / PREC_FP16, the kernels that forward ran on."""
+    if hp <= 0 or wp <= 0 or hp % 64 or wp % 64 or b < 1:
+        raise BalfHipError(f"gmlp_input: b >= 1 and hp, wp multiples of 64, got {(b, hp, wp)}")
+    shape = (b, hp // 8, wp // 8, 256)
+    for t, name, want in ((conv0_w, "conv0_w", (256, 128)), (conv0_b, "conv0_b", (256,)), (x0, "x0", shape)):
+        if t.dtype != torch.float32:
+            raise BalfHipError(f"{name} must be float32, got {t.dtype}")
+        if tuple(t.shape) != want:
+            raise BalfHipError(f"{name} must be {list(want)}, got {list(t.shape)}")
+        if not t.is_contiguous():
+            raise BalfHipError(f"{name} must be contiguous")
+    if workspace.dtype != torch.uint8:
+        raise BalfHipError("workspace must be the uint8 workspace of the forward")
+    for t, name in ((workspace, "workspace"), (conv0_w, "conv0_w"), (conv0_b, "conv0_b"), (x0, "x0")):
+        require_gpu_tensor(t, name)
+        if t.device != workspace.device:
+            raise BalfHipError(f"{name} is on {t.device}, the workspace on {workspace.device}")
+    dev = workspace.device
+    scratch = None
+    if precision == _lib.PREC_FP16:
+        scratch = _workspace("gmlp_input", dev, x0.numel() // 2 * 4)
+    with torch.cuda.device(dev):
+        check(lib().balf_forward_gmlp_input(precision, workspace.data_ptr(), workspace.numel(), b, hp, wp, conv0_w.data_ptr(),
+                                            conv0_b.data_ptr(), x0.data_ptr(), _ptr(scratch), current_stream_ptr(dev)),
+              "balf_forward_gmlp_input")

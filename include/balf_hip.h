@@ -659,6 +659,64 @@ int balf_rcab_train_backward(const float *dx2_dev, const float *y_dev, const flo
 int balf_forward_rcab_inputs(int precision, const void *workspace_dev, size_t workspace_bytes, int B, int Hp, int Wp,
                              const float *conv0_w_dev, const float *conv0_b_dev, float *y_dev, float *r_dev, void *stream);
 
+/* ---- stage 4's multi-axis gated-MLP layer in training form, and its backward ------------------------------
+ * The layer directly above the RCAB: down4.residual_split_head_multi_axis_gmlp_layer.  N = B * Hc * Wc pixels; x0_dev [N,256]
+ * float32 NHWC is its input (relu(down4.conv.0(.)), balf_forward_gmlp_input writes it), y_dev [N,256] its output, the y of
+ * balf_rcab_train_forward.
+ *   forward    n0 = LN(x0);  h0 = n0 W1^T + b1 [N,512];  (u, v) = the halves of gelu(h0), gelu(h) = h Phi(h), the exact erf form;
+ *              branch(z, map):  nb = LN_b(z);  hb = nb Wb1^T + bb1 [N,512];  (a, c) = the halves of gelu(hb);  cn = LN_g(c);
+ *                               mix[p][ch] = sum_q Wt[p][q] cn[q][ch] + bt[p] over the 64 tokens of one group, per channel;
+ *                               z' = z + (a * (mix + 1)) Wb2^T + bb2;
+ *              u' = branch(u, grid);  v' = branch(v, block);  y = cat(u', v') W2^T + b2 + x0.
+ *              Grid map: token = which of the 8 x 8 image regions of (Hc / 8) x (Wc / 8) pixels, group = (image, position inside
+ *              the region).  Block map: token = position inside a contiguous 8 x 8 block, group = (image, block).  Tokens count
+ *              row-major, 8 * row + column.  Every LN is over the 256 channels of a pixel, eps = 1e-5, as the RCAB's.
+ *   backward   g = dy_dev [N,256]:  db2 = sum g;  dW2 = g^T cat;  dcat = g W2;  per branch, dz' = its half of dcat:
+ *              dbb2 = sum dz';  dWb2 = dz'^T (a (mix + 1));  dgated = dz' Wb2;  da = dgated (mix + 1);  dmix = dgated a;
+ *              dbt[p] = sum over groups and channels of dmix;  dWt[p][q] = sum over groups and channels of dmix[p] cn[q];
+ *              dcn[q] = sum_p Wt[p][q] dmix[p];  dc = LN_g'(dcn) (with dLN_g's gain and bias);  dhb = (da, dc) gelu'(hb), gelu'(h) =
+ *              Phi(h) + h phi(h) from the saved pre-activation;  dbb1 = sum dhb;  dWb1 = dhb^T nb;  dnb = dhb Wb1;
+ *              dz = dz' + LN_b'(dnb);  dh0 = (du, dv) gelu'(h0);  db1 = sum dh0;  dW1 = dh0^T n0;  dn0 = dh0 W1;
+ *              dx0 = g + LN'(dn0)  (dx0_dev NULL ok) -- the gradient at the layer's input through the layer, its own shortcut
+ *              included.  x0 also feeds the RCAB's long shortcut; that addend (the dx2 of balf_rcab_train_backward) is the caller's.
+ * params / grads: HOST arrays of 26 device pointers, float32 tensors in PyTorch layout, in this order (names under
+ * down4.residual_split_head_multi_axis_gmlp_layer.):
+ *    0 norm.weight [256]            1 norm.bias [256]            2 dense1.weight [512,256]     3 dense1.bias [512]
+ *    for L = grid_gmlp_layer (U = grid_gating_unit) at 4 .. 13, then L = block_gmlp_layer (U = block_gating_unit) at 14 .. 23:
+ *    +0 L.norm.weight [256]         +1 L.norm.bias [256]         +2 L.dense1.weight [512,256]  +3 L.dense1.bias [512]
+ *    +4 L.U.norm.weight [256]       +5 L.U.norm.bias [256]       +6 L.U.dense.weight [64,64]   +7 L.U.dense.bias [64]
+ *    +8 L.dense2.weight [256,256]   +9 L.dense2.bias [256]
+ *   24 dense2.weight [256,512]     25 dense2.bias [256]
+ * saved_dev: an opaque caller-owned block of balf_gmlp_train_saved_bytes bytes that the forward writes and the backward of the
+ * same (B, Hc, Wc) reads: n0, h0, gelu(h0), cat, the (mean, rstd) of every LN, and per branch nb, hb, gelu(hb), cn, mix + 1 and
+ * a (mix + 1).  Every xhat is recomputed from the LN's input and the saved (mean, rstd) with the forward's operations.
+ * Arithmetic: every product along the channels runs on v_mfma_f32_16x16x4_f32 through the GEMM of the head (train_gemm.h), the
+ * weight gradients over S = ceil(N / rows) slices of the pixels with a float64 slab sum.  The token mix and dcn are 64 x 64 MFMA
+ * products per group, gathered through the map, the summed token ascending.  dWt / dbt: an MFMA chain over 64 channels per wave
+ * and group, the groups of a workgroup (ceil(N / 64 / 256) each) added in float64, then the wave partials in one fixed order.
+ * Every sum over pixels is made of float64 per-workgroup partials added in one fixed order.  No floating-point atomics; every
+ * order is a function of (B, Hc, Wc) alone: two calls on the same input give bit-identical outputs.  dx0, when not requested, is
+ * neither computed nor written and the other outputs do not change.  Stream-ordered, nothing synchronised or read back,
+ * capturable; every word of the workspace and of saved that is read was written before.
+ * Launches: forward 13, backward 51.
+ * Limits: 1 <= B <= 65535, Hc, Wc >= 1 (BALF_ERR_ARG); Hc and Wc multiples of 8, N <= 2^24 (BALF_ERR_SHAPE); the required
+ * pointers, the two arrays and their 26 entries must not be NULL; x0_dev, y_dev, dy_dev, dx0_dev, the parameters, saved_dev and
+ * workspace_dev must be 16-byte aligned (BALF_ERR_ARG); a workspace smaller than balf_gmlp_train_workspace_bytes gives
+ * BALF_ERR_WORKSPACE.  Both size queries return 0 outside these limits. */
+size_t balf_gmlp_train_workspace_bytes(int B, int Hc, int Wc);
+size_t balf_gmlp_train_saved_bytes(int B, int Hc, int Wc);
+int balf_gmlp_train_forward(const float *x0_dev, const float *const *params, int B, int Hc, int Wc, float *y_dev, void *saved_dev,
+                            void *workspace_dev, size_t workspace_bytes, void *stream);
+int balf_gmlp_train_backward(const float *dy_dev, const float *x0_dev, const float *const *params, const void *saved_dev, int B,
+                             int Hc, int Wc, float *const *grads, float *dx0_dev, void *workspace_dev, size_t workspace_bytes,
+                             void *stream);
+/* After a forward whose last micro-batch of B images is resident in workspace_dev (the rules and error codes of
+ * balf_forward_stage_view): x0_dev [B,Hp/8,Wp/8,256] = relu(x3 W^T + b), computed from the resident stage-3 output with the
+ * training GEMM exactly as balf_forward_rcab_inputs computes it (the same bits).  scratch_dev: B * Hp/8 * Wp/8 * 128 floats for the
+ * de-fragmented stage-3 view of the split-f16 path (NULL ok with BALF_PREC_FP32). */
+int balf_forward_gmlp_input(int precision, const void *workspace_dev, size_t workspace_bytes, int B, int Hp, int Wp,
+                            const float *conv0_w_dev, const float *conv0_b_dev, float *x0_dev, float *scratch_dev, void *stream);
+
 /* ---- measurement aid (not part of the data path) ---------------------------------------------
  * Between balf_profile_begin() and balf_profile_end() every kernel launch of the library is bracketed
  * by a hipEvent pair on its launch stream.  balf_profile_end() waits for those events and returns,
