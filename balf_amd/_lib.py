@@ -105,6 +105,9 @@ PROTOTYPES = {
     "balf_gmlp_train_forward": (_i, [_fp, C.POINTER(_vp), _i, _i, _i, _fp, _vp, _vp, _sz, _vp]),
     "balf_gmlp_train_backward": (_i, [_fp, _fp, C.POINTER(_vp), _vp, _i, _i, _i, C.POINTER(_vp), _fp, _vp, _sz, _vp]),
     "balf_forward_gmlp_input": (_i, [_i, _vp, _sz, _i, _i, _i, _fp, _fp, _fp, _fp, _vp]),
+    "balf_linrelu_train_workspace_bytes": (_sz, [_i, _i]),
+    "balf_linrelu_train_forward": (_i, [_fp, _fp, _fp, _i, _i, _fp, _vp]),
+    "balf_linrelu_train_backward": (_i, [_fp, _fp, _fp, _fp, _i, _i, _fp, _fp, _fp, _vp, _sz, _vp]),
     "balf_profile_num_slots": (_i, []),
     "balf_profile_slot_name": (C.c_char_p, [_i]),
     "balf_profile_begin": (_i, []),

@@ -250,7 +250,11 @@ class MLP_MA_DECODER(nn.Module):
         return self._forward("f32", (b, h, w), x.contiguous().float(), b, h, w, want_logits)
 
     def encode(self, x: torch.Tensor, chunk=None, level: str = "x2"):
-        """``level="gmlp"``: two blocks earlier -- ``x0``, the input of stage 4's multi-axis gated-MLP layer, [B,H/8,W/8,256]
+        """``level="stage3"``: the whole of stage 4 earlier -- ``x3``, the stage-3 output and input of ``down4.conv.0``,
+        [B,H/8,W/8,128] float32 NHWC, what ``model.stage4_train.TrainableStage4`` trains on (balf_forward_stage_view, stage 3:
+        a copy on the fp32 path, de-fragmented on the split-f16 path -- the x3 that levels "rcab" and "gmlp" compute x0 from).
+
+        ``level="gmlp"``: two blocks earlier -- ``x0``, the input of stage 4's multi-axis gated-MLP layer, [B,H/8,W/8,256]
         float32 NHWC, what ``model.mixer_train.TrainableMixerTail`` trains on (balf_forward_gmlp_input).
 
         ``level="rcab"``: one block earlier -- ``(y, r)``, the input of stage 4's channel-attention block and y + the long
@@ -275,16 +279,17 @@ class MLP_MA_DECODER(nn.Module):
             raise ValueError(f"H and W must be multiples of 64 (pad with mod_padding_symmetric), got {h}x{w}")
         if b < 1:
             raise ValueError("encode: an empty batch")
-        if level not in ("x2", "rcab", "gmlp"):
-            raise ValueError(f"encode: level must be 'x2', 'rcab' or 'gmlp', got {level!r}")
+        if level not in ("x2", "rcab", "gmlp", "stage3"):
+            raise ValueError(f"encode: level must be 'x2', 'rcab', 'gmlp' or 'stage3', got {level!r}")
         x = x.contiguous().float()
         l = lib()
         mb = l.balf_forward_micro_batch(b, h, w)
         chunk = mb if chunk is None else max(1, min(int(chunk), mb))
-        out = torch.empty((b, h // 8, w // 8, 256), dtype=torch.float32, device=x.device)
+        stage = 3 if level == "stage3" else 4
+        out = torch.empty((b, h // 8, w // 8, 128 if stage == 3 else 256), dtype=torch.float32, device=x.device)
         if level == "rcab":
             r = torch.empty_like(out)
-        if level != "x2":
+        if level in ("rcab", "gmlp"):
             conv0 = self.down4.conv[0]
             w0, b0 = conv0.weight.detach().float().contiguous(), conv0.bias.detach().float().contiguous()
         with torch.no_grad():
@@ -299,7 +304,7 @@ class MLP_MA_DECODER(nn.Module):
                     ops.gmlp_input(self._code_of(self.effective_precision), ws, nb, h, w, w0, b0, out[at:at + nb])
                     continue
                 with torch.cuda.device(x.device):
-                    check(l.balf_forward_stage_view(self._code_of(self.effective_precision), ws.data_ptr(), ws.numel(), nb, h, w, 4,
+                    check(l.balf_forward_stage_view(self._code_of(self.effective_precision), ws.data_ptr(), ws.numel(), nb, h, w, stage,
                                                     out[at:at + nb].data_ptr(), _lib.current_stream_ptr(x.device)),
                           "balf_forward_stage_view")
         return (out, r) if level == "rcab" else out

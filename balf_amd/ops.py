@@ -951,3 +951,81 @@ def gmlp_input(precision: int, workspace: torch.Tensor, b: int, hp: int, wp: int
         check(lib().balf_forward_gmlp_input(precision, workspace.data_ptr(), workspace.numel(), b, hp, wp, conv0_w.data_ptr(),
                                             conv0_b.data_ptr(), x0.data_ptr(), _ptr(scratch), current_stream_ptr(dev)),
               "balf_forward_gmlp_input")
+
+
+LINRELU_PARAMS = ("weight", "bias")       # of the Linear c_in -> 2 c_in in front of a ReLU (down4.conv.0 at c_in = 128)
+_LINRELU_WIDTHS = (32, 64, 128)
+
+
+class LinreluTrainForward(NamedTuple):
+    y: torch.Tensor                           # [..., 2 c_in] float32: relu(x w^T + b)
+
+
+class LinreluTrainBackward(NamedTuple):
+    dweight: torch.Tensor                     # [2 c_in, c_in]
+    dbias: torch.Tensor                       # [2 c_in]
+    dx: Optional[torch.Tensor]                # as x
+
+
+def _linrelu_train_checks(x, weight, others):
+    """As _gmlp_train_checks: metadata first, then the devices.  ``others``: (tensor or None, name, shape) triples.  Every tensor
+    is float32, contiguous and starts on a 16-byte boundary of its storage.  -> (N, c_in)."""
+    if x.dim() < 2 or x.shape[-1] not in _LINRELU_WIDTHS:
+        raise BalfHipError(f"x must be [..., c_in] with c_in one of {_LINRELU_WIDTHS} (pixels by channels, NHWC), got {tuple(x.shape)}")
+    c_in = x.shape[-1]
+    n = x.numel() // c_in
+    if not 1 <= n <= 1 << 24:
+        raise BalfHipError(f"linrelu_train: 1 <= N <= 2^24 pixels, got {tuple(x.shape)}")
+    named = ((x, "x", None), (weight, "weight", (2 * c_in, c_in))) + tuple(others)
+    for t, name, shape in named:
+        if t is None:
+            continue
+        if t.dtype != torch.float32:
+            raise BalfHipError(f"{name} must be float32, got {t.dtype}")
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise BalfHipError(f"{name} must be {list(shape)}, got {list(t.shape)}")
+        if not t.is_contiguous():
+            raise BalfHipError(f"{name} must be contiguous")
+        if t.storage_offset() * t.element_size() % 16:
+            raise BalfHipError(f"{name} must start on a 16-byte boundary of its storage")
+    for t, name, _ in named:
+        if t is not None:
+            require_gpu_tensor(t, name)
+            if t.device != x.device:
+                raise BalfHipError(f"{name} is on {t.device}, x on {x.device}")
+    return n, c_in
+
+
+def linrelu_train_forward(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor) -> LinreluTrainForward:
+    """``relu(x weight^T + bias)`` per pixel (balf_linrelu_train_forward in include/balf_hip.h): ``x`` [..., c_in] with c_in of 32, 64
+    or 128, ``weight`` [2 c_in, c_in], ``bias`` [2 c_in], float32 and contiguous on one GPU.  At c_in = 128 with ``down4.conv.0`` and
+    ``x`` = ``MLP_MA_DECODER.encode(level="stage3")`` it gives the bits of ``encode(level="gmlp")``."""
+    c = x.shape[-1] if x.dim() >= 2 else 0
+    n, c_in = _linrelu_train_checks(x, weight, ((bias, "bias", (2 * c,)),))
+    dev = x.device
+    y = torch.empty(tuple(x.shape[:-1]) + (2 * c_in,), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().balf_linrelu_train_forward(x.data_ptr(), weight.data_ptr(), bias.data_ptr(), n, c_in, y.data_ptr(),
+                                               current_stream_ptr(dev)), "balf_linrelu_train_forward")
+    return LinreluTrainForward(y)
+
+
+def linrelu_train_backward(g: torch.Tensor, y: torch.Tensor, x: torch.Tensor, weight: torch.Tensor, want_dx=False) -> LinreluTrainBackward:
+    """The backward of ``linrelu_train_forward`` (balf_linrelu_train_backward): ``g`` the total gradient at ``y``, ``y`` that
+    forward's output (the ReLU's derivative is taken from it) -> the gradients of ``weight`` and ``bias`` and, with ``want_dx``, of
+    ``x`` (``want_dx`` may be a contiguous float32 tensor of x's shape to write into)."""
+    dx = want_dx if isinstance(want_dx, torch.Tensor) else None
+    wide = tuple(x.shape[:-1]) + (2 * x.shape[-1],) if x.dim() >= 2 else None
+    n, c_in = _linrelu_train_checks(x, weight, ((g, "g", wide), (y, "y", wide), (dx, "dx", tuple(x.shape))))
+    dev = x.device
+    l = lib()
+    if dx is None and want_dx:
+        dx = torch.empty_like(x)
+    dw = torch.empty((2 * c_in, c_in), dtype=torch.float32, device=dev)
+    db = torch.empty((2 * c_in,), dtype=torch.float32, device=dev)
+    ws = _workspace("linrelu_train", dev, l.balf_linrelu_train_workspace_bytes(n, c_in))
+    with torch.cuda.device(dev):
+        check(l.balf_linrelu_train_backward(g.data_ptr(), y.data_ptr(), x.data_ptr(), weight.data_ptr(), n, c_in, dw.data_ptr(),
+                                            db.data_ptr(), _ptr(dx), ws.data_ptr(), ws.numel(), current_stream_ptr(dev)),
+              "balf_linrelu_train_backward")
+    return LinreluTrainBackward(dw, db, dx)

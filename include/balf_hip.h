@@ -717,6 +717,31 @@ int balf_gmlp_train_backward(const float *dy_dev, const float *x0_dev, const flo
 int balf_forward_gmlp_input(int precision, const void *workspace_dev, size_t workspace_bytes, int B, int Hp, int Wp,
                             const float *conv0_w_dev, const float *conv0_b_dev, float *x0_dev, float *scratch_dev, void *stream);
 
+/* ---- the first layer of a Down stage in training form, and its backward --------------------------------------
+ * A per-pixel Linear c_in -> c_out = 2 c_in followed by a ReLU: down4.conv.0 at c_in = 128 (its output is the x0 of
+ * balf_forward_gmlp_input), the same layer of stages 3 and 2 at c_in = 64 and 32.  N pixels; x_dev [N,c_in], w_dev [c_out,c_in]
+ * (PyTorch layout), b_dev [c_out], y_dev [N,c_out], g_dev [N,c_out] the TOTAL gradient at y, all float32.
+ *   forward    y = relu(x w^T + b): the GEMM of the head (train_gemm.h) on v_mfma_f32_16x16x4_f32, k ascending, launched exactly as
+ *              balf_forward_gmlp_input launches it -- at c_in = 128 the same bits as its x0 from the same x.
+ *   backward   gm = y > 0 ? g : 0, the derivative from the OUTPUT as torch's threshold_backward: a select, so whatever g holds
+ *              under a dead unit (huge, non-finite) gives 0, and the derivative at exactly 0 is 0;
+ *              db[o] = sum_p gm[p,o];  dw[o,k] = sum_p gm[p,o] x[p,k];  dx = gm w  (dx_dev NULL ok: then it is neither computed
+ *              nor written and no other output changes).
+ * db: float64 per-workgroup column partials, made in the pass that makes gm, added by one wave in a fixed order.  dw: S =
+ * ceil(N / rows) slices of the pixels, each an MFMA chain, the slabs added in float64 in slice order.  No floating-point atomics;
+ * every order is a function of (N, c_in) alone: two calls on the same input give bit-identical outputs.  Stream-ordered, nothing
+ * synchronised, allocated or read back, capturable; every word of the workspace that is read was written by the same call.
+ * Launches: forward 1, backward 4 (5 with dx).
+ * Limits: every required pointer non-NULL, every pointer 16-byte aligned, c_in one of 32, 64, 128 (BALF_ERR_ARG); 1 <= N <= 2^24
+ * (BALF_ERR_SHAPE); a workspace smaller than balf_linrelu_train_workspace_bytes gives BALF_ERR_WORKSPACE.  The size query returns
+ * 0 outside these limits. */
+size_t balf_linrelu_train_workspace_bytes(int N, int c_in);
+int balf_linrelu_train_forward(const float *x_dev, const float *w_dev, const float *b_dev, int N, int c_in, float *y_dev,
+                               void *stream);
+int balf_linrelu_train_backward(const float *g_dev, const float *y_dev, const float *x_dev, const float *w_dev, int N, int c_in,
+                                float *dw_dev, float *db_dev, float *dx_dev, void *workspace_dev, size_t workspace_bytes,
+                                void *stream);
+
 /* ---- measurement aid (not part of the data path) ---------------------------------------------
  * Between balf_profile_begin() and balf_profile_end() every kernel launch of the library is bracketed
  * by a hipEvent pair on its launch stream.  balf_profile_end() waits for those events and returns,
