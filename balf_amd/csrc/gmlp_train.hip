@@ -29,7 +29,6 @@ constexpr int kC = 256, kC2 = 512;          // channels; the width of the two de
 constexpr int kTok = 64;                    // tokens of a group: the 8 x 8 grid, the 8 x 8 block
 constexpr int kParams = 26;
 constexpr int kBranchParams = 10;           // norm.{w,b} dense1.{w,b} gating norm.{w,b} gating dense.{w,b} dense2.{w,b}
-constexpr int kMaxN = 1 << 24;
 constexpr int kMixPitch = 80;               // floats per row of Wt in LDS: the four k of an MFMA step fall on disjoint banks
 constexpr int kMixPart = kTok * kTok + kTok;    // float64 per wave partial: dWt, then dbt
 constexpr int kMaxMixWgs = 256;             // workgroups of mix_bwd_kernel: one per CU, or one per group when there are fewer
@@ -39,7 +38,8 @@ struct Branch {                             // saved, per branch
 };
 
 struct Layout {
-    int B, Hc, Wc, N, S, rows, col_rows, PC, groups, gpw, PW;
+    int B, Hc, Wc, groups, gpw, PW;
+    PixelSlices px;
     // saved
     float *n0, *stat0, *h0, *g0, *cat;
     Branch br[2];
@@ -54,11 +54,8 @@ struct Layout {
 Layout make_layout(int B, int Hc, int Wc, char *saved, char *work, size_t *saved_bytes, size_t *work_bytes) {
     Layout l{};
     l.B = B; l.Hc = Hc; l.Wc = Wc;
-    const int N = l.N = B * Hc * Wc;
-    l.rows = rows_per_slice(N);
-    l.S = balf_ceil_div(N, l.rows);
-    l.col_rows = l.rows / 16 > 64 ? l.rows / 16 : 64;       // as rcab_train.hip: 64 rows per workgroup, or what keeps PC at 1024
-    l.PC = balf_ceil_div(N, l.col_rows);
+    const int N = B * Hc * Wc;
+    l.px = pixel_slices(N);
     l.groups = N / kTok;
     l.gpw = balf_ceil_div(l.groups, kMaxMixWgs);
     l.PW = balf_ceil_div(l.groups, l.gpw);
@@ -81,14 +78,14 @@ Layout make_layout(int B, int Hc, int Wc, char *saved, char *work, size_t *saved
     }
     if (saved_bytes) *saved_bytes = sv.used;
     WorkspaceCursor ws{work, 0};
-    l.col_part = ws.take<double>((size_t)2 * l.PC * kC2 * sizeof(double));
+    l.col_part = ws.take<double>((size_t)2 * l.px.PC * kC2 * sizeof(double));
     l.mix_part = ws.take<double>((size_t)4 * l.PW * kMixPart * sizeof(double));
     l.dcat = ws.take<float>(a2);
     l.dh0 = ws.take<float>(a2);
     l.dhb = ws.take<float>(a2);
     l.t0 = ws.take<float>(a1);
     l.t1 = ws.take<float>(a1);
-    l.slab = ws.take<float>((size_t)l.S * kC2 * kC * sizeof(float));
+    l.slab = ws.take<float>((size_t)l.px.S * kC2 * kC * sizeof(float));
     if (work_bytes) *work_bytes = ws.used;
     return l;
 }
@@ -361,11 +358,9 @@ __global__ __launch_bounds__(256) void mix_bwd_kernel(MixArgs a) {
 int check_sizes(int B, int Hc, int Wc) {
     if (B < 1 || B > kMaxPairs || Hc < 1 || Wc < 1) return BALF_ERR_ARG;
     if (Hc % 8 || Wc % 8) return BALF_ERR_SHAPE;            // the 8 x 8 grid and the 8 x 8 blocks
-    if ((long)B * (long)Hc * (long)Wc > (long)kMaxN) return BALF_ERR_SHAPE;
+    if ((long)B * (long)Hc * (long)Wc > (long)kTrainMaxN) return BALF_ERR_SHAPE;
     return BALF_OK;
 }
-
-bool misaligned(const void *p, unsigned mask) { return ((uintptr_t)p & mask) != 0; }
 
 MixArgs mix_args(const Layout &l, bool grid) {
     MixArgs m{};
@@ -375,36 +370,6 @@ MixArgs mix_args(const Layout &l, bool grid) {
     if (grid) { m.by = l.Wc; m.bx = 1; m.sy = fh * l.Wc; m.sx = fw; }     // group = a place inside the region, token = the region
     else { m.by = 8 * l.Wc; m.bx = 8; m.sy = l.Wc; m.sx = 1; }            // group = a block, token = a place inside the block
     return m;
-}
-
-// C[pixel][n] = epilogue(sum_k A[pixel * lda + k] * W(k, n)), n < Nn, k < K: TRANSPOSED = false reads W[n][k] (x W^T), true reads
-// W[k][n] (x W)
-template <int EPI, bool TRANSPOSED>
-void pixel_gemm(const float *A, size_t lda, int K, const float *W, int Nn, int N, float *C, size_t ldc, const float *bias,
-                const float *mask, hipStream_t st) {
-    GemmArgs g{};
-    g.A = A; g.a_sm = lda; g.a_sk = 1;
-    g.B = W; g.b_sn = TRANSPOSED ? 1 : K; g.b_sk = TRANSPOSED ? Nn : 1;
-    g.M = N; g.Nn = Nn; g.K = K; g.k_rows = K;
-    g.C = C; g.c_sm = ldc; g.bias = bias; g.mask = mask;
-    launch_gemm<true, !TRANSPOSED, false, EPI>(g, st);
-}
-
-// out[o][k] = fl32(sum_pixel D[pixel * ldd + o] * X[pixel * ldx + k]), o < M, k < Nn, in S slices of the pixels, the slabs added in
-// float64
-void weight_grad(const float *D, size_t ldd, int M, const float *X, size_t ldx, int Nn, const Layout &l, float *out, hipStream_t st) {
-    GemmArgs g{};
-    g.A = D; g.a_sm = 1; g.a_sk = ldd;
-    g.B = X; g.b_sn = 1; g.b_sk = ldx;
-    g.M = M; g.Nn = Nn; g.K = l.N; g.k_rows = l.rows;
-    g.C = l.slab; g.c_sm = Nn; g.c_sz = (size_t)M * Nn;
-    launch_gemm<false, false, false, EPI_STORE>(g, st);
-    slab_sum_kernel<<<M * Nn / 256, 256, 0, st>>>(l.slab, l.S, M * Nn, out);
-}
-
-// out[c] = fl32(sum over the PC float64 partials of column c), c < cols
-void finish_cols(const double *part, int cols, const Layout &l, float *out, hipStream_t st) {
-    partial_sum_kernel<<<cols / 4, 256, 0, st>>>(part, cols, l.PC, 1, (size_t)cols, out, nullptr);
 }
 
 int check_call(const float *const *params, const void *const *others, int n_others, const void *const *aligned, int n_aligned) {
@@ -447,7 +412,7 @@ extern "C" int balf_gmlp_train_forward(const float *x0_dev, const float *const *
     if (workspace_bytes < balf_gmlp_train_workspace_bytes(B, Hc, Wc)) return BALF_ERR_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const Layout l = make_layout(B, Hc, Wc, static_cast<char *>(saved_dev), static_cast<char *>(workspace_dev), nullptr, nullptr);
-    const int N = l.N, ln_blocks = balf_ceil_div(N, kLnFwdPix);
+    const int N = l.px.N, ln_blocks = balf_ceil_div(N, kLnFwdPix);
     const float *const *P = params;
 
     ln_fwd_kernel<<<ln_blocks, 256, 0, st>>>(x0_dev, P[0], P[1], N, l.n0, l.stat0);
@@ -491,17 +456,17 @@ extern "C" int balf_gmlp_train_backward(const float *dy_dev, const float *x0_dev
     hipStream_t st = static_cast<hipStream_t>(stream);
     const Layout l = make_layout(B, Hc, Wc, static_cast<char *>(const_cast<void *>(saved_dev)), static_cast<char *>(workspace_dev),
                                  nullptr, nullptr);
-    const int N = l.N;
+    const int N = l.px.N;
     const float *const *P = params;
     float *const *G = grads;
-    double *part0 = l.col_part, *part1 = l.col_part + (size_t)l.PC * kC2;
+    double *part0 = l.col_part, *part1 = l.col_part + (size_t)l.px.PC * kC2;
 
     // y = cat W2^T + b2 + x0:  db2 = sum dy,  dW2 = dy^T cat,  dcat = dy W2
-    col_sum_kernel<<<l.PC, kC, 0, st>>>(dy_dev, N, l.col_rows, part0);
+    col_sum_kernel<<<l.px.PC, kC, 0, st>>>(dy_dev, N, l.px.col_rows, part0);
     BALF_LAUNCH_CHECK();
-    finish_cols(part0, kC, l, G[25], st);
+    finish_cols(part0, kC, l.px.PC, G[25], st);
     BALF_LAUNCH_CHECK();
-    weight_grad(dy_dev, kC, kC, l.cat, kC2, kC2, l, G[24], st);
+    weight_grad(dy_dev, kC, kC, l.cat, kC2, kC2, l.px, l.slab, G[24], st);
     BALF_LAUNCH_CHECK();
     pixel_gemm<EPI_STORE, true>(dy_dev, kC, kC, P[24], kC2, N, l.dcat, kC2, nullptr, nullptr, st);
     BALF_LAUNCH_CHECK();
@@ -511,11 +476,11 @@ extern "C" int balf_gmlp_train_backward(const float *dy_dev, const float *x0_dev
         float *const *D = G + 4 + kBranchParams * k;
         const float *dzo = l.dcat + kC * k;                                                          // the gradient at z', row stride 512
         // z' = z + gated Wb2^T + bb2
-        col_sum_s_kernel<<<dim3(l.PC, 1), 256, 0, st>>>(dzo, kC2, N, l.col_rows, part0);
+        col_sum_s_kernel<<<dim3(l.px.PC, 1), 256, 0, st>>>(dzo, kC2, N, l.px.col_rows, part0);
         BALF_LAUNCH_CHECK();
-        finish_cols(part0, kC, l, D[9], st);
+        finish_cols(part0, kC, l.px.PC, D[9], st);
         BALF_LAUNCH_CHECK();
-        weight_grad(dzo, kC2, kC, b.gated, kC, kC, l, D[8], st);
+        weight_grad(dzo, kC2, kC, b.gated, kC, kC, l.px, l.slab, D[8], st);
         BALF_LAUNCH_CHECK();
         float *dgated = l.t0, *dcn = l.t1;
         pixel_gemm<EPI_STORE, true>(dzo, kC2, kC, Q[8], kC, N, dgated, kC, nullptr, nullptr, st);
@@ -532,58 +497,58 @@ extern "C" int balf_gmlp_train_backward(const float *dy_dev, const float *x0_dev
         BALF_LAUNCH_CHECK();
         // the gating LayerNorm on c: dhb (c's half) = LN'(dcn) * gelu'(hb)
         LnBwdSArgs s{};
-        s.N = N; s.rows = l.col_rows; s.dn = dcn; s.stat = b.statg; s.ln_g = Q[4];
+        s.N = N; s.rows = l.px.col_rows; s.dn = dcn; s.stat = b.statg; s.ln_g = Q[4];
         s.x = b.gb + kC; s.xs = kC2; s.h = b.hb + kC; s.hs = kC2; s.out = l.dhb + kC; s.os = kC2;
         s.part_g = part0; s.part_b = part1;
-        ln_bwd_s_kernel<false><<<l.PC, 256, 0, st>>>(s);
+        ln_bwd_s_kernel<false><<<l.px.PC, 256, 0, st>>>(s);
         BALF_LAUNCH_CHECK();
-        finish_cols(part0, kC, l, D[4], st);
+        finish_cols(part0, kC, l.px.PC, D[4], st);
         BALF_LAUNCH_CHECK();
-        finish_cols(part1, kC, l, D[5], st);
+        finish_cols(part1, kC, l.px.PC, D[5], st);
         BALF_LAUNCH_CHECK();
         // hb = nb Wb1^T + bb1
-        col_sum_s_kernel<<<dim3(l.PC, 2), 256, 0, st>>>(l.dhb, kC2, N, l.col_rows, part0);
+        col_sum_s_kernel<<<dim3(l.px.PC, 2), 256, 0, st>>>(l.dhb, kC2, N, l.px.col_rows, part0);
         BALF_LAUNCH_CHECK();
-        finish_cols(part0, kC2, l, D[3], st);
+        finish_cols(part0, kC2, l.px.PC, D[3], st);
         BALF_LAUNCH_CHECK();
-        weight_grad(l.dhb, kC2, kC2, b.nb, kC, kC, l, D[2], st);
+        weight_grad(l.dhb, kC2, kC2, b.nb, kC, kC, l.px, l.slab, D[2], st);
         BALF_LAUNCH_CHECK();
         float *dnb = l.t0;                                                                           // dgated is spent
         pixel_gemm<EPI_STORE, true>(l.dhb, kC2, kC2, Q[2], kC, N, dnb, kC, nullptr, nullptr, st);
         BALF_LAUNCH_CHECK();
         // the branch's LayerNorm on z and its shortcut: dh0 (this half) = (dzo + LN'(dnb)) * gelu'(h0)
         s = LnBwdSArgs{};
-        s.N = N; s.rows = l.col_rows; s.dn = dnb; s.stat = b.statb; s.ln_g = Q[0];
+        s.N = N; s.rows = l.px.col_rows; s.dn = dnb; s.stat = b.statb; s.ln_g = Q[0];
         s.x = l.g0 + kC * k; s.xs = kC2; s.g = dzo; s.gs = kC2; s.h = l.h0 + kC * k; s.hs = kC2; s.out = l.dh0 + kC * k; s.os = kC2;
         s.part_g = part0; s.part_b = part1;
-        ln_bwd_s_kernel<true><<<l.PC, 256, 0, st>>>(s);
+        ln_bwd_s_kernel<true><<<l.px.PC, 256, 0, st>>>(s);
         BALF_LAUNCH_CHECK();
-        finish_cols(part0, kC, l, D[0], st);
+        finish_cols(part0, kC, l.px.PC, D[0], st);
         BALF_LAUNCH_CHECK();
-        finish_cols(part1, kC, l, D[1], st);
+        finish_cols(part1, kC, l.px.PC, D[1], st);
         BALF_LAUNCH_CHECK();
     }
     // h0 = n0 W1^T + b1
-    col_sum_s_kernel<<<dim3(l.PC, 2), 256, 0, st>>>(l.dh0, kC2, N, l.col_rows, part0);
+    col_sum_s_kernel<<<dim3(l.px.PC, 2), 256, 0, st>>>(l.dh0, kC2, N, l.px.col_rows, part0);
     BALF_LAUNCH_CHECK();
-    finish_cols(part0, kC2, l, G[3], st);
+    finish_cols(part0, kC2, l.px.PC, G[3], st);
     BALF_LAUNCH_CHECK();
-    weight_grad(l.dh0, kC2, kC2, l.n0, kC, kC, l, G[2], st);
+    weight_grad(l.dh0, kC2, kC2, l.n0, kC, kC, l.px, l.slab, G[2], st);
     BALF_LAUNCH_CHECK();
     float *dn0 = l.t0;
     pixel_gemm<EPI_STORE, true>(l.dh0, kC2, kC2, P[2], kC, N, dn0, kC, nullptr, nullptr, st);
     BALF_LAUNCH_CHECK();
     // the layer's LayerNorm and its shortcut: dx0 = dy + LN'(dn0)
     LnBwdArgs n{};
-    n.N = N; n.rows = l.col_rows; n.dn = dn0; n.y = x0_dev; n.stat = l.stat0; n.ln_g = P[0]; n.g = dy_dev; n.dy = dx0_dev;
+    n.N = N; n.rows = l.px.col_rows; n.dn = dn0; n.y = x0_dev; n.stat = l.stat0; n.ln_g = P[0]; n.g = dy_dev; n.dy = dx0_dev;
     n.part_g = part0; n.part_b = part1;
     n.vec_g = true; n.vec_dy = true;
-    if (dx0_dev) ln_bwd_kernel<true><<<l.PC, 256, 0, st>>>(n);
-    else ln_bwd_kernel<false><<<l.PC, 256, 0, st>>>(n);
+    if (dx0_dev) ln_bwd_kernel<true><<<l.px.PC, 256, 0, st>>>(n);
+    else ln_bwd_kernel<false><<<l.px.PC, 256, 0, st>>>(n);
     BALF_LAUNCH_CHECK();
-    finish_cols(part0, kC, l, G[0], st);
+    finish_cols(part0, kC, l.px.PC, G[0], st);
     BALF_LAUNCH_CHECK();
-    finish_cols(part1, kC, l, G[1], st);
+    finish_cols(part1, kC, l.px.PC, G[1], st);
     BALF_LAUNCH_CHECK();
     return BALF_OK;
 }

@@ -25,12 +25,12 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 
 constexpr int kC = 256;                     // channels of x2, of down4.conv2 and of the head's input
 constexpr int kZ = 65;                      // head channels
-constexpr int kMaxN = 1 << 24;              // pixels: up to 2^32 elements in a [N,256] matrix, indexed in size_t
 constexpr int kRowThreads = 256;
 constexpr int kRowChunk = 4 * kRowThreads;  // pixels per workgroup of the row kernels
 
 struct Layout {
-    int N, P, S, rows, col_rows, PC;        // P row-kernel partials per channel, S slices, PC column-sum partials
+    int P;                                  // row-kernel partials per channel
+    PixelSlices px;
     // saved
     float *a, *zT;
     double *stat;                           // [2][65]: mean, 1 / sqrt(var + eps)
@@ -43,12 +43,8 @@ struct Layout {
 
 Layout make_layout(int N, char *saved, char *work, size_t *saved_bytes, size_t *work_bytes) {
     Layout l{};
-    l.N = N;
     l.P = balf_ceil_div(N, kRowChunk);
-    l.rows = rows_per_slice(N);
-    l.S = balf_ceil_div(N, l.rows);
-    l.col_rows = l.rows / 16 > 64 ? l.rows / 16 : 64;       // 64 rows per workgroup, or what keeps PC at 1024
-    l.PC = balf_ceil_div(N, l.col_rows);
+    l.px = pixel_slices(N);
     WorkspaceCursor sv{saved, 0};
     l.a = sv.take<float>((size_t)N * kC * sizeof(float));
     l.zT = sv.take<float>((size_t)N * kZ * sizeof(float));
@@ -57,11 +53,11 @@ Layout make_layout(int N, char *saved, char *work, size_t *saved_bytes, size_t *
     WorkspaceCursor ws{work, 0};
     l.part = ws.take<double>((size_t)2 * kZ * l.P * sizeof(double));
     l.dbn = ws.take<double>(2 * kZ * sizeof(double));
-    l.b2_part = ws.take<double>((size_t)l.PC * kC * sizeof(double));
+    l.b2_part = ws.take<double>((size_t)l.px.PC * kC * sizeof(double));
     l.dzT = ws.take<float>((size_t)N * kZ * sizeof(float));
     l.dh = ws.take<float>((size_t)N * kC * sizeof(float));
-    l.slab_wd = ws.take<float>((size_t)l.S * kZ * kC * sizeof(float));
-    l.slab_w2 = ws.take<float>((size_t)l.S * kC * kC * sizeof(float));
+    l.slab_wd = ws.take<float>((size_t)l.px.S * kZ * kC * sizeof(float));
+    l.slab_w2 = ws.take<float>((size_t)l.px.S * kC * kC * sizeof(float));
     if (work_bytes) *work_bytes = ws.used;
     return l;
 }
@@ -203,12 +199,10 @@ __global__ __launch_bounds__(256) void normalize_kernel(NormArgs a) {
 int check_sizes(int B, int Hc, int Wc) {
     if (B < 1 || B > kMaxPairs || Hc < 1 || Wc < 1) return BALF_ERR_ARG;
     const long n = (long)B * (long)Hc * (long)Wc;
-    if (n > (long)kMaxN) return BALF_ERR_SHAPE;
+    if (n > (long)kTrainMaxN) return BALF_ERR_SHAPE;
     if (n < 2) return BALF_ERR_ARG;         // one value per channel has no variance
     return BALF_OK;
 }
-
-bool misaligned8(const void *p) { return ((uintptr_t)p & 7u) != 0; }
 
 }  // namespace
 }  // namespace balf
@@ -216,14 +210,14 @@ bool misaligned8(const void *p) { return ((uintptr_t)p & 7u) != 0; }
 using namespace balf;
 
 extern "C" size_t balf_head_train_workspace_bytes(long N) {
-    if (N < 2 || N > (long)kMaxN) return 0;
+    if (N < 2 || N > (long)kTrainMaxN) return 0;
     size_t bytes = 0;
     make_layout((int)N, nullptr, nullptr, nullptr, &bytes);
     return bytes;
 }
 
 extern "C" size_t balf_head_train_saved_bytes(long N) {
-    if (N < 2 || N > (long)kMaxN) return 0;
+    if (N < 2 || N > (long)kTrainMaxN) return 0;
     size_t bytes = 0;
     make_layout((int)N, nullptr, nullptr, &bytes, nullptr);
     return bytes;
@@ -237,7 +231,7 @@ extern "C" int balf_head_train_forward(const float *x2_dev, const float *w2_dev,
     if (!x2_dev || !w2_dev || !b2_dev || !wd_dev || !bd_dev || !gamma_dev || !beta_dev || !logits_dev || !saved_dev || !workspace_dev)
         return BALF_ERR_ARG;
     if (use_stats && !stats_in_dev) return BALF_ERR_ARG;
-    if (misaligned8(saved_dev) || misaligned8(workspace_dev)) return BALF_ERR_ARG;      // float64 statistics and partial sums
+    if (misaligned(saved_dev, 7) || misaligned(workspace_dev, 7)) return BALF_ERR_ARG;      // float64 statistics and partial sums
     if (!(eps >= 0.0)) return BALF_ERR_ARG;
     const int rc = check_sizes(B, Hc, Wc);
     if (rc != BALF_OK) return rc;
@@ -247,15 +241,10 @@ extern "C" int balf_head_train_forward(const float *x2_dev, const float *w2_dev,
     const Layout l = make_layout(N, static_cast<char *>(saved_dev), static_cast<char *>(workspace_dev), nullptr, nullptr);
 
     // a[pixel][out] = relu(sum_k x2[pixel][k] * W2[out][k] + b2[out])
-    GemmArgs g{};
-    g.A = x2_dev; g.a_sm = kC; g.a_sk = 1;
-    g.B = w2_dev; g.b_sn = kC; g.b_sk = 1;
-    g.M = N; g.Nn = kC; g.K = kC; g.k_rows = kC;
-    g.C = l.a; g.c_sm = kC; g.bias = b2_dev;
-    launch_gemm<true, true, false, EPI_BIAS_N_RELU>(g, st);
+    pixel_gemm<EPI_BIAS_N_RELU, false>(x2_dev, kC, kC, w2_dev, kC, N, l.a, kC, b2_dev, nullptr, st);
     BALF_LAUNCH_CHECK();
     // zT[c][pixel] = sum_k Wd[c][k] * a[pixel][k] + bd[c]
-    g = GemmArgs{};
+    GemmArgs g{};
     g.A = wd_dev; g.a_sm = kC; g.a_sk = 1;
     g.B = l.a; g.b_sn = kC; g.b_sk = 1;
     g.M = kZ; g.Nn = N; g.K = kC; g.k_rows = kC;
@@ -294,7 +283,7 @@ extern "C" int balf_head_train_backward(const float *dlogits_dev, const float *x
     if (!dlogits_dev || !x2_dev || !w2_dev || !wd_dev || !gamma_dev || !saved_dev || !dw2_dev || !db2_dev || !dwd_dev || !dbd_dev ||
         !dgamma_dev || !dbeta_dev || !workspace_dev)
         return BALF_ERR_ARG;
-    if (misaligned8(saved_dev) || misaligned8(workspace_dev)) return BALF_ERR_ARG;
+    if (misaligned(saved_dev, 7) || misaligned(workspace_dev, 7)) return BALF_ERR_ARG;
     const int rc = check_sizes(B, Hc, Wc);
     if (rc != BALF_OK) return rc;
     const int N = B * Hc * Wc;
@@ -321,11 +310,11 @@ extern "C" int balf_head_train_backward(const float *dlogits_dev, const float *x
     GemmArgs g{};
     g.A = l.dzT; g.a_sm = (size_t)N; g.a_sk = 1;
     g.B = l.a; g.b_sn = 1; g.b_sk = kC;
-    g.M = kZ; g.Nn = kC; g.K = N; g.k_rows = l.rows;
+    g.M = kZ; g.Nn = kC; g.K = N; g.k_rows = l.px.rows;
     g.C = l.slab_wd; g.c_sm = kC; g.c_sz = (size_t)kZ * kC;
     launch_gemm<true, false, false, EPI_STORE>(g, st);
     BALF_LAUNCH_CHECK();
-    slab_sum_kernel<<<balf_ceil_div(kZ * kC, 256), 256, 0, st>>>(l.slab_wd, l.S, kZ * kC, dwd_dev);
+    slab_sum_kernel<<<balf_ceil_div(kZ * kC, 256), 256, 0, st>>>(l.slab_wd, l.px.S, kZ * kC, dwd_dev);
     BALF_LAUNCH_CHECK();
 
     // dh[pixel][k] = [a > 0] * sum_c dzT[c][pixel] * Wd[c][k]
@@ -336,30 +325,17 @@ extern "C" int balf_head_train_backward(const float *dlogits_dev, const float *x
     g.C = l.dh; g.c_sm = kC; g.mask = l.a;
     launch_gemm<false, false, false, EPI_RELU_MASK>(g, st);
     BALF_LAUNCH_CHECK();
-    col_sum_kernel<<<l.PC, kC, 0, st>>>(l.dh, N, l.col_rows, l.b2_part);
+    col_sum_kernel<<<l.px.PC, kC, 0, st>>>(l.dh, N, l.px.col_rows, l.b2_part);
     BALF_LAUNCH_CHECK();
-    partial_sum_kernel<<<kC / 4, 256, 0, st>>>(l.b2_part, kC, l.PC, 1, (size_t)kC, db2_dev, nullptr);
+    finish_cols(l.b2_part, kC, l.px.PC, db2_dev, st);
     BALF_LAUNCH_CHECK();
 
     // dW2[o][k] = sum_pixel dh[pixel][o] * x2[pixel][k], in S slices of the pixels
-    g = GemmArgs{};
-    g.A = l.dh; g.a_sm = 1; g.a_sk = kC;
-    g.B = x2_dev; g.b_sn = 1; g.b_sk = kC;
-    g.M = kC; g.Nn = kC; g.K = N; g.k_rows = l.rows;
-    g.C = l.slab_w2; g.c_sm = kC; g.c_sz = (size_t)kC * kC;
-    launch_gemm<false, false, false, EPI_STORE>(g, st);
+    weight_grad(l.dh, kC, kC, x2_dev, kC, kC, l.px, l.slab_w2, dw2_dev, st);
     BALF_LAUNCH_CHECK();
-    slab_sum_kernel<<<kC * kC / 256, 256, 0, st>>>(l.slab_w2, l.S, kC * kC, dw2_dev);
-    BALF_LAUNCH_CHECK();
-
     if (dx2_dev) {
         // dx2[pixel][k] = sum_o dh[pixel][o] * W2[o][k]
-        g = GemmArgs{};
-        g.A = l.dh; g.a_sm = kC; g.a_sk = 1;
-        g.B = w2_dev; g.b_sn = 1; g.b_sk = kC;
-        g.M = N; g.Nn = kC; g.K = kC; g.k_rows = kC;
-        g.C = dx2_dev; g.c_sm = kC;
-        launch_gemm<true, false, false, EPI_STORE>(g, st);
+        pixel_gemm<EPI_STORE, true>(l.dh, kC, kC, w2_dev, kC, N, dx2_dev, kC, nullptr, nullptr, st);
         BALF_LAUNCH_CHECK();
     }
     return BALF_OK;

@@ -15,25 +15,21 @@
 namespace balf {
 namespace {
 
-constexpr int kMaxN = 1 << 24;              // pixels: up to 2^32 elements in a [N,256] matrix, indexed in size_t
-
 struct Layout {
-    int N, c_in, c_out, S, rows, col_rows, P;   // S slices of rows pixels; P workgroups of col_rows rows in the mask kernel
+    int c_in, c_out;
+    PixelSlices px;                         // px.PC workgroups of px.col_rows rows in the mask kernel
     float *gm, *slab;
     double *part;
 };
 
 Layout make_layout(int N, int c_in, char *work, size_t *work_bytes) {
     Layout l{};
-    l.N = N; l.c_in = c_in; l.c_out = 2 * c_in;
-    l.rows = rows_per_slice(N);
-    l.S = balf_ceil_div(N, l.rows);
-    l.col_rows = l.rows / 16 > 64 ? l.rows / 16 : 64;       // 64 rows per workgroup, or what keeps P at 1024
-    l.P = balf_ceil_div(N, l.col_rows);
+    l.c_in = c_in; l.c_out = 2 * c_in;
+    l.px = pixel_slices(N);
     WorkspaceCursor ws{work, 0};
     l.gm = ws.take<float>((size_t)N * l.c_out * sizeof(float));
-    l.part = ws.take<double>((size_t)l.P * l.c_out * sizeof(double));
-    l.slab = ws.take<float>((size_t)l.S * l.c_out * l.c_in * sizeof(float));
+    l.part = ws.take<double>((size_t)l.px.PC * l.c_out * sizeof(double));
+    l.slab = ws.take<float>((size_t)l.px.S * l.c_out * l.c_in * sizeof(float));
     if (work_bytes) *work_bytes = ws.used;
     return l;
 }
@@ -75,7 +71,6 @@ __global__ __launch_bounds__(256) void relu_mask_colsum_kernel(const float *g, c
 }
 
 bool width_ok(int c_in) { return c_in == 32 || c_in == 64 || c_in == 128; }
-bool misaligned(const void *p) { return ((uintptr_t)p & 15) != 0; }
 
 }  // namespace
 }  // namespace balf
@@ -83,7 +78,7 @@ bool misaligned(const void *p) { return ((uintptr_t)p & 15) != 0; }
 using namespace balf;
 
 extern "C" size_t balf_linrelu_train_workspace_bytes(int N, int c_in) {
-    if (!width_ok(c_in) || N < 1 || N > kMaxN) return 0;
+    if (!width_ok(c_in) || N < 1 || N > kTrainMaxN) return 0;
     size_t bytes = 0;
     make_layout(N, c_in, nullptr, &bytes);
     return bytes;
@@ -92,15 +87,10 @@ extern "C" size_t balf_linrelu_train_workspace_bytes(int N, int c_in) {
 extern "C" int balf_linrelu_train_forward(const float *x_dev, const float *w_dev, const float *b_dev, int N, int c_in, float *y_dev,
                                           void *stream) {
     if (!x_dev || !w_dev || !b_dev || !y_dev || !width_ok(c_in)) return BALF_ERR_ARG;
-    if (misaligned(x_dev) || misaligned(w_dev) || misaligned(b_dev) || misaligned(y_dev)) return BALF_ERR_ARG;
-    if (N < 1 || N > kMaxN) return BALF_ERR_SHAPE;
-    const int c_out = 2 * c_in;
-    GemmArgs g{};
-    g.A = x_dev; g.a_sm = c_in; g.a_sk = 1;
-    g.B = w_dev; g.b_sn = c_in; g.b_sk = 1;
-    g.M = N; g.Nn = c_out; g.K = c_in; g.k_rows = c_in;
-    g.C = y_dev; g.c_sm = c_out; g.bias = b_dev;
-    launch_gemm<true, true, false, EPI_BIAS_N_RELU>(g, static_cast<hipStream_t>(stream));
+    if (misaligned(x_dev, 15) || misaligned(w_dev, 15) || misaligned(b_dev, 15) || misaligned(y_dev, 15)) return BALF_ERR_ARG;
+    if (N < 1 || N > kTrainMaxN) return BALF_ERR_SHAPE;
+    pixel_gemm<EPI_BIAS_N_RELU, false>(x_dev, c_in, c_in, w_dev, 2 * c_in, N, y_dev, 2 * c_in, b_dev, nullptr,
+                                       static_cast<hipStream_t>(stream));
     BALF_LAUNCH_CHECK();
     return BALF_OK;
 }
@@ -109,40 +99,28 @@ extern "C" int balf_linrelu_train_backward(const float *g_dev, const float *y_de
                                            float *dw_dev, float *db_dev, float *dx_dev, void *workspace_dev, size_t workspace_bytes,
                                            void *stream) {
     if (!g_dev || !y_dev || !x_dev || !w_dev || !dw_dev || !db_dev || !workspace_dev || !width_ok(c_in)) return BALF_ERR_ARG;
-    if (misaligned(g_dev) || misaligned(y_dev) || misaligned(x_dev) || misaligned(w_dev) || misaligned(dw_dev) || misaligned(db_dev) ||
-        misaligned(dx_dev) || misaligned(workspace_dev))
+    if (misaligned(g_dev, 15) || misaligned(y_dev, 15) || misaligned(x_dev, 15) || misaligned(w_dev, 15) || misaligned(dw_dev, 15) ||
+        misaligned(db_dev, 15) || misaligned(dx_dev, 15) || misaligned(workspace_dev, 15))
         return BALF_ERR_ARG;
-    if (N < 1 || N > kMaxN) return BALF_ERR_SHAPE;
+    if (N < 1 || N > kTrainMaxN) return BALF_ERR_SHAPE;
     if (workspace_bytes < balf_linrelu_train_workspace_bytes(N, c_in)) return BALF_ERR_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const Layout l = make_layout(N, c_in, static_cast<char *>(workspace_dev), nullptr);
     const int c_out = l.c_out;
 
     // gm = y > 0 ? g : 0 and db = sum gm
-    if (c_out == 64) relu_mask_colsum_kernel<64><<<l.P, 256, 0, st>>>(g_dev, y_dev, N, l.col_rows, l.gm, l.part);
-    else if (c_out == 128) relu_mask_colsum_kernel<128><<<l.P, 256, 0, st>>>(g_dev, y_dev, N, l.col_rows, l.gm, l.part);
-    else relu_mask_colsum_kernel<256><<<l.P, 256, 0, st>>>(g_dev, y_dev, N, l.col_rows, l.gm, l.part);
+    if (c_out == 64) relu_mask_colsum_kernel<64><<<l.px.PC, 256, 0, st>>>(g_dev, y_dev, N, l.px.col_rows, l.gm, l.part);
+    else if (c_out == 128) relu_mask_colsum_kernel<128><<<l.px.PC, 256, 0, st>>>(g_dev, y_dev, N, l.px.col_rows, l.gm, l.part);
+    else relu_mask_colsum_kernel<256><<<l.px.PC, 256, 0, st>>>(g_dev, y_dev, N, l.px.col_rows, l.gm, l.part);
     BALF_LAUNCH_CHECK();
-    partial_sum_kernel<<<c_out / 4, 256, 0, st>>>(l.part, c_out, l.P, 1, (size_t)c_out, db_dev, nullptr);
+    finish_cols(l.part, c_out, l.px.PC, db_dev, st);
     BALF_LAUNCH_CHECK();
     // dw[o][k] = fl32(sum_pixel gm[pixel][o] * x[pixel][k]) in S slices of the pixels, the slabs added in float64
-    GemmArgs a{};
-    a.A = l.gm; a.a_sm = 1; a.a_sk = c_out;
-    a.B = x_dev; a.b_sn = 1; a.b_sk = c_in;
-    a.M = c_out; a.Nn = c_in; a.K = N; a.k_rows = l.rows;
-    a.C = l.slab; a.c_sm = c_in; a.c_sz = (size_t)c_out * c_in;
-    launch_gemm<false, false, false, EPI_STORE>(a, st);
-    BALF_LAUNCH_CHECK();
-    slab_sum_kernel<<<c_out * c_in / 256, 256, 0, st>>>(l.slab, l.S, c_out * c_in, dw_dev);
+    weight_grad(l.gm, c_out, c_out, x_dev, c_in, c_in, l.px, l.slab, dw_dev, st);
     BALF_LAUNCH_CHECK();
     // dx[pixel][k] = sum_o gm[pixel][o] * w[o][k]
     if (dx_dev) {
-        GemmArgs d{};
-        d.A = l.gm; d.a_sm = c_out; d.a_sk = 1;
-        d.B = w_dev; d.b_sn = 1; d.b_sk = c_in;
-        d.M = N; d.Nn = c_in; d.K = c_out; d.k_rows = c_out;
-        d.C = dx_dev; d.c_sm = c_in;
-        launch_gemm<true, false, false, EPI_STORE>(d, st);
+        pixel_gemm<EPI_STORE, true>(l.gm, c_out, c_out, w_dev, c_in, N, dx_dev, c_in, nullptr, nullptr, st);
         BALF_LAUNCH_CHECK();
     }
     return BALF_OK;

@@ -3,7 +3,7 @@
 // x2 = t * s_image + r,  and its backward from dx2 to the ten parameter gradients and dy.  N = B * Hc * Wc pixels.
 //
 // Four kinds of kernels:
-//   * gemm_kernel (train_gemm.h, shared with head_train.hip) for the six 256 x 256 products; dwc1 / dwc2 through the slab split
+//   * gemm_kernel (train_gemm.h, with its launch helpers) for the six 256 x 256 products; dwc1 / dwc2 through the slab split
 //     and the float64 slab sum.
 //   * LayerNorm row kernels (train_ln.h, shared with gmlp_train.hip): a pixel's 256 channels on one wave.
 //   * column kernels, a channel per thread over a block of pixel rows, float64 partial sums per workgroup: over the rows of ONE
@@ -20,11 +20,11 @@ namespace {
 
 constexpr int kC = 256;                     // channels
 constexpr int kH = 64;                      // squeeze-excite hidden units
-constexpr int kMaxN = 1 << 24;              // pixels: up to 2^32 elements in a [N,256] matrix, indexed in size_t
 constexpr int kMaxImgParts = 1024;          // row blocks per image of img_sum_kernel
 
 struct Layout {
-    int B, hw, N, S, rows, col_rows, PC;    // S slices of rows pixels; PC blocks of col_rows rows over all pixels
+    int B, hw;
+    PixelSlices px;                         // of all N = B * hw pixels
     int img_rows, PI;                       // PI blocks of img_rows rows per image
     // saved
     float *n, *a, *t, *stat, *sf;           // stat [N][2]: mean, rstd; sf [B][256]
@@ -40,11 +40,8 @@ struct Layout {
 Layout make_layout(int B, int hw, char *saved, char *work, size_t *saved_bytes, size_t *work_bytes) {
     Layout l{};
     l.B = B; l.hw = hw;
-    const int N = l.N = B * hw;
-    l.rows = rows_per_slice(N);
-    l.S = balf_ceil_div(N, l.rows);
-    l.col_rows = l.rows / 16 > 64 ? l.rows / 16 : 64;       // 64 rows per workgroup, or what keeps PC at 1024
-    l.PC = balf_ceil_div(N, l.col_rows);
+    const int N = B * hw;
+    l.px = pixel_slices(N);
     const int per = balf_ceil_div(hw, kMaxImgParts);
     l.img_rows = per > 64 ? per : 64;
     l.PI = balf_ceil_div(hw, l.img_rows);
@@ -61,13 +58,13 @@ Layout make_layout(int B, int hw, char *saved, char *work, size_t *saved_bytes, 
     if (saved_bytes) *saved_bytes = sv.used;
     WorkspaceCursor ws{work, 0};
     l.img_part = ws.take<double>((size_t)B * l.PI * kC * sizeof(double));
-    l.col_part = ws.take<double>((size_t)2 * l.PC * kC * sizeof(double));
+    l.col_part = ws.take<double>((size_t)2 * l.px.PC * kC * sizeof(double));
     l.dq = ws.take<double>((size_t)B * kC * sizeof(double));
     l.de = ws.take<double>((size_t)B * kH * sizeof(double));
     l.dmh = ws.take<float>((size_t)B * kC * sizeof(float));
     l.dt = ws.take<float>(act);
     l.dh = ws.take<float>(act);
-    l.slab = ws.take<float>((size_t)l.S * kC * kC * sizeof(float));
+    l.slab = ws.take<float>((size_t)l.px.S * kC * kC * sizeof(float));
     if (work_bytes) *work_bytes = ws.used;
     return l;
 }
@@ -229,33 +226,9 @@ __global__ __launch_bounds__(kC) void dt_kernel(const float *g, const float *sf,
 int check_sizes(int B, int Hc, int Wc) {
     if (B < 1 || B > kMaxPairs || Hc < 1 || Wc < 1) return BALF_ERR_ARG;
     const long n = (long)B * (long)Hc * (long)Wc;
-    if (n > (long)kMaxN) return BALF_ERR_SHAPE;
+    if (n > (long)kTrainMaxN) return BALF_ERR_SHAPE;
     if (n < 2) return BALF_ERR_ARG;         // the limits of the head, whose input this block produces
     return BALF_OK;
-}
-
-bool misaligned(const void *p, unsigned mask) { return ((uintptr_t)p & mask) != 0; }
-
-// C[pixel][n] = epilogue(sum_k A[pixel][k] * W(k, n)): TRANSPOSED = false reads W[n][k] (x W^T), true reads W[k][n] (x W)
-template <int EPI, bool TRANSPOSED>
-void pixel_gemm(const float *A, const float *W, int N, float *C, const float *bias, const float *mask, hipStream_t st) {
-    GemmArgs g{};
-    g.A = A; g.a_sm = kC; g.a_sk = 1;
-    g.B = W; g.b_sn = TRANSPOSED ? 1 : kC; g.b_sk = TRANSPOSED ? kC : 1;
-    g.M = N; g.Nn = kC; g.K = kC; g.k_rows = kC;
-    g.C = C; g.c_sm = kC; g.bias = bias; g.mask = mask;
-    launch_gemm<true, !TRANSPOSED, false, EPI>(g, st);
-}
-
-// out[o][k] = fl32(sum_pixel D[pixel][o] * X[pixel][k]) in S slices of the pixels, the slabs added in float64
-void weight_grad(const float *D, const float *X, const Layout &l, float *out, hipStream_t st) {
-    GemmArgs g{};
-    g.A = D; g.a_sm = 1; g.a_sk = kC;
-    g.B = X; g.b_sn = 1; g.b_sk = kC;
-    g.M = kC; g.Nn = kC; g.K = l.N; g.k_rows = l.rows;
-    g.C = l.slab; g.c_sm = kC; g.c_sz = (size_t)kC * kC;
-    launch_gemm<false, false, false, EPI_STORE>(g, st);
-    slab_sum_kernel<<<kC * kC / 256, 256, 0, st>>>(l.slab, l.S, kC * kC, out);
 }
 
 }  // namespace
@@ -298,9 +271,9 @@ extern "C" int balf_rcab_train_forward(const float *y_dev, const float *r_dev, c
 
     ln_fwd_kernel<<<balf_ceil_div(N, kLnFwdPix), 256, 0, st>>>(y_dev, ln_g_dev, ln_b_dev, N, l.n, l.stat);
     BALF_LAUNCH_CHECK();
-    pixel_gemm<EPI_BIAS_N_LRELU, false>(l.n, wc1_dev, N, l.a, bc1_dev, nullptr, st);       // a = lrelu(n wc1^T + bc1)
+    pixel_gemm<EPI_BIAS_N_LRELU, false>(l.n, kC, kC, wc1_dev, kC, N, l.a, kC, bc1_dev, nullptr, st);   // a = lrelu(n wc1^T + bc1)
     BALF_LAUNCH_CHECK();
-    pixel_gemm<EPI_BIAS_N, false>(l.a, wc2_dev, N, l.t, bc2_dev, nullptr, st);             // t = a wc2^T + bc2
+    pixel_gemm<EPI_BIAS_N, false>(l.a, kC, kC, wc2_dev, kC, N, l.t, kC, bc2_dev, nullptr, st);         // t = a wc2^T + bc2
     BALF_LAUNCH_CHECK();
     img_sum_kernel<false><<<dim3(l.PI, B), kC, 0, st>>>(l.t, nullptr, hw, l.img_rows, l.img_part);
     BALF_LAUNCH_CHECK();
@@ -332,7 +305,7 @@ extern "C" int balf_rcab_train_backward(const float *dx2_dev, const float *y_dev
     const int hw = Hc * Wc, N = B * hw;
     const Layout l = make_layout(B, hw, static_cast<char *>(const_cast<void *>(saved_dev)), static_cast<char *>(workspace_dev), nullptr,
                                  nullptr);
-    double *part0 = l.col_part, *part1 = l.col_part + (size_t)l.PC * kC;
+    double *part0 = l.col_part, *part1 = l.col_part + (size_t)l.px.PC * kC;
 
     // the squeeze-excite: ds_i = sum_p g t, then dq, de, dm per image and the four SE gradients over the images
     img_sum_kernel<true><<<dim3(l.PI, B), kC, 0, st>>>(dx2_dev, l.t, hw, l.img_rows, l.img_part);
@@ -350,35 +323,35 @@ extern "C" int balf_rcab_train_backward(const float *dx2_dev, const float *y_dev
     BALF_LAUNCH_CHECK();
 
     // dt = g s_i + dm_i / hw, dbc2 = sum dt, dwc2 = dt^T a
-    dt_kernel<<<l.PC, kC, 0, st>>>(dx2_dev, l.sf, l.dmh, N, hw, l.col_rows, l.dt, part0);
+    dt_kernel<<<l.px.PC, kC, 0, st>>>(dx2_dev, l.sf, l.dmh, N, hw, l.px.col_rows, l.dt, part0);
     BALF_LAUNCH_CHECK();
-    partial_sum_kernel<<<kC / 4, 256, 0, st>>>(part0, kC, l.PC, 1, (size_t)kC, dbc2_dev, nullptr);
+    finish_cols(part0, kC, l.px.PC, dbc2_dev, st);
     BALF_LAUNCH_CHECK();
-    weight_grad(l.dt, l.a, l, dwc2_dev, st);
+    weight_grad(l.dt, kC, kC, l.a, kC, kC, l.px, l.slab, dwc2_dev, st);
     BALF_LAUNCH_CHECK();
     // dh = (dt wc2) * (a > 0 ? 1 : 0.2), dbc1 = sum dh, dwc1 = dh^T n
-    pixel_gemm<EPI_LRELU_MASK, true>(l.dt, wc2_dev, N, l.dh, nullptr, l.a, st);
+    pixel_gemm<EPI_LRELU_MASK, true>(l.dt, kC, kC, wc2_dev, kC, N, l.dh, kC, nullptr, l.a, st);
     BALF_LAUNCH_CHECK();
-    col_sum_kernel<<<l.PC, kC, 0, st>>>(l.dh, N, l.col_rows, part0);
+    col_sum_kernel<<<l.px.PC, kC, 0, st>>>(l.dh, N, l.px.col_rows, part0);
     BALF_LAUNCH_CHECK();
-    partial_sum_kernel<<<kC / 4, 256, 0, st>>>(part0, kC, l.PC, 1, (size_t)kC, dbc1_dev, nullptr);
+    finish_cols(part0, kC, l.px.PC, dbc1_dev, st);
     BALF_LAUNCH_CHECK();
-    weight_grad(l.dh, l.n, l, dwc1_dev, st);
+    weight_grad(l.dh, kC, kC, l.n, kC, kC, l.px, l.slab, dwc1_dev, st);
     BALF_LAUNCH_CHECK();
     // dn = dh wc1 (over dt, which nobody reads any more), then the LayerNorm: dln_g, dln_b and, if asked for, dy
     float *dn = l.dt;
-    pixel_gemm<EPI_STORE, true>(l.dh, wc1_dev, N, dn, nullptr, nullptr, st);
+    pixel_gemm<EPI_STORE, true>(l.dh, kC, kC, wc1_dev, kC, N, dn, kC, nullptr, nullptr, st);
     BALF_LAUNCH_CHECK();
     LnBwdArgs b{};
-    b.N = N; b.rows = l.col_rows; b.dn = dn; b.y = y_dev; b.stat = l.stat; b.ln_g = ln_g_dev; b.g = dx2_dev; b.dy = dy_dev;
+    b.N = N; b.rows = l.px.col_rows; b.dn = dn; b.y = y_dev; b.stat = l.stat; b.ln_g = ln_g_dev; b.g = dx2_dev; b.dy = dy_dev;
     b.part_g = part0; b.part_b = part1;
     b.vec_g = !misaligned(dx2_dev, 15); b.vec_dy = !misaligned(dy_dev, 15);
-    if (dy_dev) ln_bwd_kernel<true><<<l.PC, 256, 0, st>>>(b);
-    else ln_bwd_kernel<false><<<l.PC, 256, 0, st>>>(b);
+    if (dy_dev) ln_bwd_kernel<true><<<l.px.PC, 256, 0, st>>>(b);
+    else ln_bwd_kernel<false><<<l.px.PC, 256, 0, st>>>(b);
     BALF_LAUNCH_CHECK();
-    partial_sum_kernel<<<kC / 4, 256, 0, st>>>(part0, kC, l.PC, 1, (size_t)kC, dln_g_dev, nullptr);
+    finish_cols(part0, kC, l.px.PC, dln_g_dev, st);
     BALF_LAUNCH_CHECK();
-    partial_sum_kernel<<<kC / 4, 256, 0, st>>>(part1, kC, l.PC, 1, (size_t)kC, dln_b_dev, nullptr);
+    finish_cols(part1, kC, l.px.PC, dln_b_dev, st);
     BALF_LAUNCH_CHECK();
     return BALF_OK;
 }

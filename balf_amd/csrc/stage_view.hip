@@ -58,12 +58,7 @@ int stage4_input(int precision, const char *ws, const Plan &pl, int B, int Hp, i
         BALF_LAUNCH_CHECK();
         x3 = scratch;
     }
-    GemmArgs g{};
-    g.A = x3; g.a_sm = C3; g.a_sk = 1;
-    g.B = conv0_w; g.b_sn = C3; g.b_sk = 1;
-    g.M = (int)pix; g.Nn = C4; g.K = C3; g.k_rows = C3;
-    g.C = x0; g.c_sm = C4; g.bias = conv0_b;
-    launch_gemm<true, true, false, EPI_BIAS_N_RELU>(g, st);
+    pixel_gemm<EPI_BIAS_N_RELU, false>(x3, C3, C3, conv0_w, C4, (int)pix, x0, C4, conv0_b, nullptr, st);
     BALF_LAUNCH_CHECK();
     return BALF_OK;
 }

@@ -1,5 +1,5 @@
-// The shared pieces of the training kernels (head_train.hip, rcab_train.hip, gmlp_train.hip, and the x0 recomputation of
-// stage_view.hip):
+// The shared pieces of the training kernels (head_train.hip, rcab_train.hip, gmlp_train.hip, linrelu_train.hip, and the x0
+// recomputation of stage_view.hip):
 //   * gemm_kernel: ONE LDS-tiled GEMM on v_mfma_f32_16x16x4_f32 (exact fp32 fma chains, k ascending).  A workgroup of four waves
 //     owns a 64 x 64 tile of C[m][n] = sum_k A(m,k) * B(k,n), a wave a 32 x 32 quarter (2 x 2 MFMA tiles); K goes through LDS in
 //     steps of 16 with the next step's operands fetched into registers before the MFMAs of this one.  The operands are addressed
@@ -8,6 +8,8 @@
 //     (rows_per_slice(N)), slice s writes slab s of the workspace, and slab_sum_kernel adds the S slabs in float64 in slice order.
 //   * the float64 sums over pixels: col_sum_kernel (per-workgroup partials of the columns of a [N,256] matrix) and
 //     partial_sum_kernel (a wave per output adds the partials in one fixed order: lanes strided, then the butterfly).
+//   * the host side of both: PixelSlices, the slice geometry of N pixels that every unit's Layout holds, and the launch helpers
+//     pixel_gemm / weight_grad / finish_cols, which fill a GemmArgs for the products along the channels of pixel-major matrices.
 // An epilogue is a template value: a new one adds an instantiation and leaves the code of the others as it was.
 #pragma once
 #include "block_ops.h"
@@ -20,11 +22,30 @@ typedef float gf4 __attribute__((ext_vector_type(4)));
 constexpr int kTrainC = 256;                // the channel count of every [N,256] matrix here
 constexpr int kTile = 64, kTK = 16, kPitch = kTile + 4;
 constexpr int kMaxSlices = 64;              // slabs of a weight gradient
+constexpr int kTrainMaxN = 1 << 24;         // pixels: up to 2^32 elements in a [N,256] matrix, indexed in size_t
+
+bool misaligned(const void *p, unsigned mask) { return ((uintptr_t)p & mask) != 0; }
 
 // rows (pixels) per K slice of dW2 / dWd: 256, or the multiple of 256 that keeps the slices at kMaxSlices
 int rows_per_slice(int N) {
     const int chunks = balf_ceil_div(N, 256);
     return 256 * balf_ceil_div(chunks, kMaxSlices);
+}
+
+// How the N pixels are cut: S slices of rows pixels for the K range of a weight gradient, PC workgroups of col_rows rows for the
+// float64 column sums (64 rows per workgroup, or what keeps PC at 1024)
+struct PixelSlices {
+    int N, rows, S, col_rows, PC;
+};
+
+PixelSlices pixel_slices(int N) {
+    PixelSlices p{};
+    p.N = N;
+    p.rows = rows_per_slice(N);
+    p.S = balf_ceil_div(N, p.rows);
+    p.col_rows = p.rows / 16 > 64 ? p.rows / 16 : 64;
+    p.PC = balf_ceil_div(N, p.col_rows);
+    return p;
 }
 
 // ---- the GEMM -----------------------------------------------------------------------------------------------------------------
@@ -178,6 +199,40 @@ __global__ __launch_bounds__(kTrainC) void col_sum_kernel(const float *x, int N,
     }
     for (int i = 0; r < r1; ++r, ++i) s[i] += (double)x[(size_t)r * kTrainC + threadIdx.x];
     part[(size_t)blockIdx.x * kTrainC + threadIdx.x] = (s[0] + s[1]) + (s[2] + s[3]);
+}
+
+// ---- the launches along the channels -----------------------------------------------------------------------------------------
+// C[pixel][n] = epilogue(sum_k A[pixel * lda + k] * W(k, n)), n < Nn, k < K: TRANSPOSED = false reads W[n][k] (x W^T), true reads
+// W[k][n] (x W)
+template <int EPI, bool TRANSPOSED>
+void pixel_gemm(const float *A, size_t lda, int K, const float *W, int Nn, int N, float *C, size_t ldc, const float *bias,
+                const float *mask, hipStream_t st) {
+    GemmArgs g{};
+    g.A = A; g.a_sm = lda; g.a_sk = 1;
+    g.B = W; g.b_sn = TRANSPOSED ? 1 : K; g.b_sk = TRANSPOSED ? Nn : 1;
+    g.M = N; g.Nn = Nn; g.K = K; g.k_rows = K;
+    g.C = C; g.c_sm = ldc; g.bias = bias; g.mask = mask;
+    launch_gemm<true, !TRANSPOSED, false, EPI>(g, st);
+}
+
+// out[o][k] = fl32(sum_pixel D[pixel * ldd + o] * X[pixel * ldx + k]), o < M, k < Nn, in p.S slices of the pixels through slab
+// [p.S][M * Nn], the slabs added in float64.  Two launches: the caller's launch check after it covers both, hipGetLastError
+// keeps an error until it is read.  (A template only so that a unit that never calls it instantiates no GEMM for it.)
+template <typename = void>
+void weight_grad(const float *D, size_t ldd, int M, const float *X, size_t ldx, int Nn, const PixelSlices &p, float *slab, float *out,
+                 hipStream_t st) {
+    GemmArgs g{};
+    g.A = D; g.a_sm = 1; g.a_sk = ldd;
+    g.B = X; g.b_sn = 1; g.b_sk = ldx;
+    g.M = M; g.Nn = Nn; g.K = p.N; g.k_rows = p.rows;
+    g.C = slab; g.c_sm = Nn; g.c_sz = (size_t)M * Nn;
+    launch_gemm<false, false, false, EPI_STORE>(g, st);
+    slab_sum_kernel<<<M * Nn / 256, 256, 0, st>>>(slab, p.S, M * Nn, out);
+}
+
+// out[c] = fl32(sum over the P float64 partials part[p][c] of column c), c < cols
+void finish_cols(const double *part, int cols, int P, float *out, hipStream_t st) {
+    partial_sum_kernel<<<cols / 4, 256, 0, st>>>(part, cols, P, 1, (size_t)cols, out, nullptr);
 }
 
 }  // namespace

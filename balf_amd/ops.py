@@ -523,6 +523,70 @@ def synth_pairs(packed: torch.Tensor, offsets: torch.Tensor, sizes: torch.Tensor
     return tuple(out)
 
 
+def _check_devices(named, anchor, dev) -> None:
+    """Every tensor of ``named`` ((tensor or None, name, ...) tuples) is on a GPU, and on ``dev``, the device of ``anchor``."""
+    for t, name, *_ in named:
+        if t is not None:
+            require_gpu_tensor(t, name)
+            if t.device != dev:
+                raise BalfHipError(f"{name} is on {t.device}, {anchor} on {dev}")
+
+
+def _check_metadata(named, aligned=(), strict_saved=False) -> None:
+    """``named``: (tensor or None, name, shape or None) triples.  Every tensor is float32, of its shape and contiguous; those
+    named in ``aligned`` (True: all) start on a 16-byte boundary of their storage.  ``saved`` is the opaque uint8 block of a
+    training unit: contiguous (``strict_saved``: and uint8, in one message); _saved_block checks the rest."""
+    for t, name, shape in named:
+        if t is None:
+            continue
+        if name == "saved":
+            if strict_saved and (t.dtype != torch.uint8 or not t.is_contiguous()):
+                raise BalfHipError("saved must be a contiguous uint8 tensor")
+            if not t.is_contiguous():
+                raise BalfHipError("saved must be contiguous")
+            continue
+        if t.dtype != torch.float32:
+            raise BalfHipError(f"{name} must be float32, got {t.dtype}")
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise BalfHipError(f"{name} must be {list(shape)}, got {list(t.shape)}")
+        if not t.is_contiguous():
+            raise BalfHipError(f"{name} must be contiguous")
+        if (aligned is True or name in aligned) and t.storage_offset() * t.element_size() % 16:
+            raise BalfHipError(f"{name} must start on a 16-byte boundary of its storage")
+
+
+def _check_tensors(named, anchor, aligned=(), strict_saved=False) -> None:
+    """The checks of a training unit's tensors, the anchor (whose device the others must share) first in ``named``: all of
+    _check_metadata, then the devices, so that a wrong call is refused before any device is touched."""
+    _check_metadata(named, aligned, strict_saved)
+    _check_devices(named, anchor, named[0][0].device)
+
+
+def _saved_block(saved, need: int, dev, align16: bool, made_by: Optional[str] = None) -> torch.Tensor:
+    """The ``saved`` block of a training unit.  Forward (``made_by`` None): allocated when None, else a uint8 tensor of at least
+    ``need`` bytes (``align16``: that starts on 16 bytes).  Backward: the same demands on the block that forward ``made_by``
+    returned."""
+    if saved is None and made_by is None:
+        return torch.empty(need, dtype=torch.uint8, device=dev)
+    if saved is None or saved.dtype != torch.uint8 or saved.numel() < need or (align16 and saved.data_ptr() % 16):
+        if made_by is not None:
+            raise BalfHipError(f"saved must be the uint8 block that {made_by} returned for this shape")
+        raise BalfHipError(f"saved must be a {'16-byte aligned ' if align16 else ''}uint8 tensor of at least {need} bytes")
+    return saved
+
+
+def _stage4_input_checks(what: str, workspace, b: int, hp: int, wp: int, conv0_w, conv0_b, outs) -> None:
+    """The checks of rcab_inputs and gmlp_input: ``outs`` are (tensor, name) pairs of [b,hp/8,wp/8,256] outputs."""
+    if hp <= 0 or wp <= 0 or hp % 64 or wp % 64 or b < 1:
+        raise BalfHipError(f"{what}: b >= 1 and hp, wp multiples of 64, got {(b, hp, wp)}")
+    shape = (b, hp // 8, wp // 8, 256)
+    named = ((conv0_w, "conv0_w", (256, 128)), (conv0_b, "conv0_b", (256,))) + tuple((t, k, shape) for t, k in outs)
+    _check_metadata(named)
+    if workspace.dtype != torch.uint8:
+        raise BalfHipError("workspace must be the uint8 workspace of the forward")
+    _check_devices(((workspace, "workspace"),) + named, "the workspace", workspace.device)
+
+
 class DetectorLoss(NamedTuple):
     loss: torch.Tensor                        # [] float32
     per_image: Optional[torch.Tensor]         # [B] float32
@@ -553,11 +617,8 @@ def detector_loss(logits: torch.Tensor, keypoint_map: torch.Tensor, valid_mask=N
         if not t.is_contiguous():
             raise BalfHipError(f"{name} must be contiguous")
     dev = logits.device
-    for t, name in ((logits, "logits"), (keypoint_map, "keypoint_map"), (valid_mask, "valid_mask"), (noise, "noise")):
-        if t is not None:
-            require_gpu_tensor(t, name)
-            if t.device != dev:
-                raise BalfHipError(f"{name} is on {t.device}, logits on {dev}")
+    _check_devices(((logits, "logits"), (keypoint_map, "keypoint_map"), (valid_mask, "valid_mask"), (noise, "noise")), "logits",
+                   dev)
     loss = torch.empty((), dtype=torch.float32, device=dev)
     per_image = torch.empty((b,), dtype=torch.float32, device=dev) if want_per_image else None
     labels = torch.empty((b, hc, wc), dtype=torch.int32, device=dev) if want_labels else None
@@ -595,27 +656,13 @@ _HEAD_PARAM_SHAPES = {"w2": (256, 256), "b2": (256,), "wd": (65, 256), "bd": (65
 
 
 def _head_train_checks(x2, named):
-    """Shapes, dtypes and contiguity from the tensors' metadata, then the devices: a wrong call is refused before any device is
-    touched.  ``named``: (tensor or None, name, shape) triples, x2 first.  -> (B, Hc, Wc)."""
+    """``named``: (tensor or None, name, shape) triples, x2 first (_check_tensors).  -> (B, Hc, Wc)."""
     if x2.dim() != 4 or x2.shape[3] != 256:
         raise BalfHipError(f"x2 must be [B,Hc,Wc,256] (the stage-4 activation, NHWC), got {tuple(x2.shape)}")
     b, hc, wc, _ = x2.shape
     if not 1 <= b <= 65535 or hc < 1 or wc < 1 or not 2 <= b * hc * wc <= 1 << 24:
         raise BalfHipError(f"head_train: 1 <= B <= 65535 and 2 <= B * Hc * Wc <= 2^24, got {tuple(x2.shape)}")
-    for t, name, shape in named:
-        if t is None:
-            continue
-        if t.dtype != torch.float32 and name != "saved":
-            raise BalfHipError(f"{name} must be float32, got {t.dtype}")
-        if shape is not None and tuple(t.shape) != tuple(shape):
-            raise BalfHipError(f"{name} must be {list(shape)}, got {list(t.shape)}")
-        if not t.is_contiguous():
-            raise BalfHipError(f"{name} must be contiguous")
-    for t, name, _ in named:
-        if t is not None:
-            require_gpu_tensor(t, name)
-            if t.device != x2.device:
-                raise BalfHipError(f"{name} is on {t.device}, x2 on {x2.device}")
+    _check_tensors(named, "x2")
     return b, hc, wc
 
 
@@ -641,11 +688,7 @@ def head_train_forward(x2: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, wd:
                                         (running_var, "running_var", s["running_var"]), (saved, "saved", None)))
     dev, n = x2.device, b * hc * wc
     l = lib()
-    need = l.balf_head_train_saved_bytes(n)
-    if saved is None:
-        saved = torch.empty(need, dtype=torch.uint8, device=dev)
-    elif saved.dtype != torch.uint8 or saved.numel() < need:
-        raise BalfHipError(f"saved must be a uint8 tensor of at least {need} bytes")
+    saved = _saved_block(saved, l.balf_head_train_saved_bytes(n), dev, False)
     logits = torch.empty((b, 65, hc, wc), dtype=torch.float32, device=dev)
     if prob is None and want_prob:
         prob = torch.empty((b, 8 * hc, 8 * wc), dtype=torch.float32, device=dev)
@@ -671,8 +714,7 @@ def head_train_backward(dlogits: torch.Tensor, x2: torch.Tensor, w2: torch.Tenso
                                         (gamma, "gamma", s["gamma"]), (saved, "saved", None), (dx2, "dx2", tuple(x2.shape))))
     dev, n = x2.device, b * hc * wc
     l = lib()
-    if saved.dtype != torch.uint8 or saved.numel() < l.balf_head_train_saved_bytes(n):
-        raise BalfHipError("saved must be the uint8 block that head_train_forward returned for this shape")
+    _saved_block(saved, l.balf_head_train_saved_bytes(n), dev, False, "head_train_forward")
     if dx2 is None and want_dx2:
         dx2 = torch.empty_like(x2)
     out = [torch.empty(s[k], dtype=torch.float32, device=dev) for k in ("w2", "b2", "wd", "bd", "gamma", "beta")]
@@ -710,29 +752,14 @@ class RcabTrainBackward(NamedTuple):
 
 
 def _rcab_train_checks(y, named, aligned=()):
-    """As _head_train_checks: metadata first, then the devices.  ``aligned``: names whose storage must start on 16 bytes (the
-    LayerNorm kernels move four channels at a time).  -> (B, Hc, Wc)."""
+    """``named``: (tensor or None, name, shape) triples, y first; ``aligned``: the names whose storage must start on 16 bytes (the
+    LayerNorm kernels move four channels at a time) (_check_tensors).  -> (B, Hc, Wc)."""
     if y.dim() != 4 or y.shape[3] != 256:
         raise BalfHipError(f"y must be [B,Hc,Wc,256] (the input of stage 4's RCAB, NHWC), got {tuple(y.shape)}")
     b, hc, wc, _ = y.shape
     if not 1 <= b <= 65535 or hc < 1 or wc < 1 or not 2 <= b * hc * wc <= 1 << 24:
         raise BalfHipError(f"rcab_train: 1 <= B <= 65535 and 2 <= B * Hc * Wc <= 2^24, got {tuple(y.shape)}")
-    for t, name, shape in named:
-        if t is None:
-            continue
-        if t.dtype != torch.float32 and name != "saved":
-            raise BalfHipError(f"{name} must be float32, got {t.dtype}")
-        if shape is not None and tuple(t.shape) != tuple(shape):
-            raise BalfHipError(f"{name} must be {list(shape)}, got {list(t.shape)}")
-        if not t.is_contiguous():
-            raise BalfHipError(f"{name} must be contiguous")
-        if name in aligned and t.storage_offset() * t.element_size() % 16:
-            raise BalfHipError(f"{name} must start on a 16-byte boundary of its storage")
-    for t, name, _ in named:
-        if t is not None:
-            require_gpu_tensor(t, name)
-            if t.device != y.device:
-                raise BalfHipError(f"{name} is on {t.device}, y on {y.device}")
+    _check_tensors(named, "y", aligned)
     return b, hc, wc
 
 
@@ -748,11 +775,7 @@ def rcab_train_forward(y: torch.Tensor, r: torch.Tensor, params, saved=None) -> 
     b, hc, wc = _rcab_train_checks(y, named + ((saved, "saved", None),), aligned=("y", "r", "ln_g", "ln_b"))
     dev = y.device
     l = lib()
-    need = l.balf_rcab_train_saved_bytes(b, hc, wc)
-    if saved is None:
-        saved = torch.empty(need, dtype=torch.uint8, device=dev)
-    elif saved.dtype != torch.uint8 or saved.numel() < need or saved.data_ptr() % 16:
-        raise BalfHipError(f"saved must be a 16-byte aligned uint8 tensor of at least {need} bytes")
+    saved = _saved_block(saved, l.balf_rcab_train_saved_bytes(b, hc, wc), dev, True)
     x2 = torch.empty_like(y)
     ws = _workspace("rcab_train", dev, l.balf_rcab_train_workspace_bytes(b, hc, wc))
     with torch.cuda.device(dev):
@@ -775,8 +798,7 @@ def rcab_train_backward(dx2: torch.Tensor, y: torch.Tensor, ln_g: torch.Tensor, 
     b, hc, wc = _rcab_train_checks(y, named, aligned=("y", "ln_g"))
     dev = y.device
     l = lib()
-    if saved.dtype != torch.uint8 or saved.numel() < l.balf_rcab_train_saved_bytes(b, hc, wc) or saved.data_ptr() % 16:
-        raise BalfHipError("saved must be the uint8 block that rcab_train_forward returned for this shape")
+    _saved_block(saved, l.balf_rcab_train_saved_bytes(b, hc, wc), dev, True, "rcab_train_forward")
     if dy is None and want_dy:
         dy = torch.empty_like(y)
     out = [torch.empty(s[k], dtype=torch.float32, device=dev) for k in RCAB_PARAMS]
@@ -795,22 +817,7 @@ def rcab_inputs(precision: int, workspace: torch.Tensor, b: int, hp: int, wp: in
     RCAB's input into ``y`` and y + the long shortcut into ``r``, both [b,hp/8,wp/8,256] float32 and contiguous on the
     workspace's GPU; ``conv0_w`` [256,128], ``conv0_b`` [256] are ``down4.conv.0``.  ``precision``: _lib.PREC_FP32 / PREC_FP16,
     the kernels that forward ran on."""
-    if hp <= 0 or wp <= 0 or hp % 64 or wp % 64 or b < 1:
-        raise BalfHipError(f"rcab_inputs: b >= 1 and hp, wp multiples of 64, got {(b, hp, wp)}")
-    shape = (b, hp // 8, wp // 8, 256)
-    for t, name, want in ((conv0_w, "conv0_w", (256, 128)), (conv0_b, "conv0_b", (256,)), (y, "y", shape), (r, "r", shape)):
-        if t.dtype != torch.float32:
-            raise BalfHipError(f"{name} must be float32, got {t.dtype}")
-        if tuple(t.shape) != want:
-            raise BalfHipError(f"{name} must be {list(want)}, got {list(t.shape)}")
-        if not t.is_contiguous():
-            raise BalfHipError(f"{name} must be contiguous")
-    if workspace.dtype != torch.uint8:
-        raise BalfHipError("workspace must be the uint8 workspace of the forward")
-    for t, name in ((workspace, "workspace"), (conv0_w, "conv0_w"), (conv0_b, "conv0_b"), (y, "y"), (r, "r")):
-        require_gpu_tensor(t, name)
-        if t.device != workspace.device:
-            raise BalfHipError(f"{name} is on {t.device}, the workspace on {workspace.device}")
+    _stage4_input_checks("rcab_inputs", workspace, b, hp, wp, conv0_w, conv0_b, ((y, "y"), (r, "r")))
     dev = workspace.device
     with torch.cuda.device(dev):
         check(lib().balf_forward_rcab_inputs(precision, workspace.data_ptr(), workspace.numel(), b, hp, wp, conv0_w.data_ptr(),
@@ -842,8 +849,8 @@ class GmlpTrainBackward(NamedTuple):
 
 
 def _gmlp_train_checks(x0, params, others):
-    """As _rcab_train_checks: metadata first, then the devices.  ``others``: (tensor or None, name, shape) triples.  Every tensor
-    but ``saved`` is float32, contiguous and starts on a 16-byte boundary of its storage.  -> (B, Hc, Wc)."""
+    """``others``: (tensor or None, name, shape) triples behind x0 and the parameters.  Every tensor but ``saved`` is float32,
+    contiguous and starts on a 16-byte boundary of its storage (_check_tensors).  -> (B, Hc, Wc, params)."""
     if x0.dim() != 4 or x0.shape[3] != 256:
         raise BalfHipError(f"x0 must be [B,Hc,Wc,256] (the input of stage 4's gMLP layer, NHWC), got {tuple(x0.shape)}")
     b, hc, wc, _ = x0.shape
@@ -853,26 +860,7 @@ def _gmlp_train_checks(x0, params, others):
     if len(params) != len(GMLP_PARAMS):
         raise BalfHipError(f"gmlp_train takes the {len(GMLP_PARAMS)} parameters of ops.GMLP_PARAMS, got {len(params)}")
     named = ((x0, "x0", None),) + tuple((t, k, _GMLP_PARAM_SHAPES[k]) for t, k in zip(params, GMLP_PARAMS)) + tuple(others)
-    for t, name, shape in named:
-        if t is None:
-            continue
-        if name == "saved":
-            if t.dtype != torch.uint8 or not t.is_contiguous():
-                raise BalfHipError("saved must be a contiguous uint8 tensor")
-            continue
-        if t.dtype != torch.float32:
-            raise BalfHipError(f"{name} must be float32, got {t.dtype}")
-        if shape is not None and tuple(t.shape) != tuple(shape):
-            raise BalfHipError(f"{name} must be {list(shape)}, got {list(t.shape)}")
-        if not t.is_contiguous():
-            raise BalfHipError(f"{name} must be contiguous")
-        if t.storage_offset() * t.element_size() % 16:
-            raise BalfHipError(f"{name} must start on a 16-byte boundary of its storage")
-    for t, name, _ in named:
-        if t is not None:
-            require_gpu_tensor(t, name)
-            if t.device != x0.device:
-                raise BalfHipError(f"{name} is on {t.device}, x0 on {x0.device}")
+    _check_tensors(named, "x0", aligned=True, strict_saved=True)
     return b, hc, wc, params
 
 
@@ -887,11 +875,7 @@ def gmlp_train_forward(x0: torch.Tensor, params, saved=None) -> GmlpTrainForward
     b, hc, wc, params = _gmlp_train_checks(x0, params, ((saved, "saved", None),))
     dev = x0.device
     l = lib()
-    need = l.balf_gmlp_train_saved_bytes(b, hc, wc)
-    if saved is None:
-        saved = torch.empty(need, dtype=torch.uint8, device=dev)
-    elif saved.numel() < need or saved.data_ptr() % 16:
-        raise BalfHipError(f"saved must be a 16-byte aligned uint8 tensor of at least {need} bytes")
+    saved = _saved_block(saved, l.balf_gmlp_train_saved_bytes(b, hc, wc), dev, True)
     y = torch.empty_like(x0)
     ws = _workspace("gmlp_train", dev, l.balf_gmlp_train_workspace_bytes(b, hc, wc))
     with torch.cuda.device(dev):
@@ -909,8 +893,7 @@ def gmlp_train_backward(dy: torch.Tensor, x0: torch.Tensor, params, saved: torch
     b, hc, wc, params = _gmlp_train_checks(x0, params, ((dy, "dy", shape), (saved, "saved", None), (dx0, "dx0", shape)))
     dev = x0.device
     l = lib()
-    if saved is None or saved.numel() < l.balf_gmlp_train_saved_bytes(b, hc, wc) or saved.data_ptr() % 16:
-        raise BalfHipError("saved must be the uint8 block that gmlp_train_forward returned for this shape")
+    _saved_block(saved, l.balf_gmlp_train_saved_bytes(b, hc, wc), dev, True, "gmlp_train_forward")
     if dx0 is None and want_dx0:
         dx0 = torch.empty_like(x0)
     out = tuple(torch.empty(_GMLP_PARAM_SHAPES[k], dtype=torch.float32, device=dev) for k in GMLP_PARAMS)
@@ -927,22 +910,7 @@ def gmlp_input(precision: int, workspace: torch.Tensor, b: int, hp: int, wp: int
     """After a forward of ``b`` padded ``hp x wp`` images whose workspace is ``workspace`` (balf_forward_gmlp_input): write the
     input of stage 4's gMLP layer into ``x0`` [b,hp/8,wp/8,256], float32 and contiguous on the workspace's GPU; ``conv0_w``
     [256,128], ``conv0_b`` [256] are ``down4.conv.0``.  ``precision``: _lib.PREC_FP32 / PREC_FP16, the kernels that forward ran on."""
-    if hp <= 0 or wp <= 0 or hp % 64 or wp % 64 or b < 1:
-        raise BalfHipError(f"gmlp_input: b >= 1 and hp, wp multiples of 64, got {(b, hp, wp)}")
-    shape = (b, hp // 8, wp // 8, 256)
-    for t, name, want in ((conv0_w, "conv0_w", (256, 128)), (conv0_b, "conv0_b", (256,)), (x0, "x0", shape)):
-        if t.dtype != torch.float32:
-            raise BalfHipError(f"{name} must be float32, got {t.dtype}")
-        if tuple(t.shape) != want:
-            raise BalfHipError(f"{name} must be {list(want)}, got {list(t.shape)}")
-        if not t.is_contiguous():
-            raise BalfHipError(f"{name} must be contiguous")
-    if workspace.dtype != torch.uint8:
-        raise BalfHipError("workspace must be the uint8 workspace of the forward")
-    for t, name in ((workspace, "workspace"), (conv0_w, "conv0_w"), (conv0_b, "conv0_b"), (x0, "x0")):
-        require_gpu_tensor(t, name)
-        if t.device != workspace.device:
-            raise BalfHipError(f"{name} is on {t.device}, the workspace on {workspace.device}")
+    _stage4_input_checks("gmlp_input", workspace, b, hp, wp, conv0_w, conv0_b, ((x0, "x0"),))
     dev = workspace.device
     scratch = None
     if precision == _lib.PREC_FP16:
@@ -968,31 +936,15 @@ class LinreluTrainBackward(NamedTuple):
 
 
 def _linrelu_train_checks(x, weight, others):
-    """As _gmlp_train_checks: metadata first, then the devices.  ``others``: (tensor or None, name, shape) triples.  Every tensor
-    is float32, contiguous and starts on a 16-byte boundary of its storage.  -> (N, c_in)."""
+    """``others``: (tensor or None, name, shape) triples behind x and weight.  Every tensor is float32, contiguous and starts on a
+    16-byte boundary of its storage (_check_tensors).  -> (N, c_in)."""
     if x.dim() < 2 or x.shape[-1] not in _LINRELU_WIDTHS:
         raise BalfHipError(f"x must be [..., c_in] with c_in one of {_LINRELU_WIDTHS} (pixels by channels, NHWC), got {tuple(x.shape)}")
     c_in = x.shape[-1]
     n = x.numel() // c_in
     if not 1 <= n <= 1 << 24:
         raise BalfHipError(f"linrelu_train: 1 <= N <= 2^24 pixels, got {tuple(x.shape)}")
-    named = ((x, "x", None), (weight, "weight", (2 * c_in, c_in))) + tuple(others)
-    for t, name, shape in named:
-        if t is None:
-            continue
-        if t.dtype != torch.float32:
-            raise BalfHipError(f"{name} must be float32, got {t.dtype}")
-        if shape is not None and tuple(t.shape) != tuple(shape):
-            raise BalfHipError(f"{name} must be {list(shape)}, got {list(t.shape)}")
-        if not t.is_contiguous():
-            raise BalfHipError(f"{name} must be contiguous")
-        if t.storage_offset() * t.element_size() % 16:
-            raise BalfHipError(f"{name} must start on a 16-byte boundary of its storage")
-    for t, name, _ in named:
-        if t is not None:
-            require_gpu_tensor(t, name)
-            if t.device != x.device:
-                raise BalfHipError(f"{name} is on {t.device}, x on {x.device}")
+    _check_tensors(((x, "x", None), (weight, "weight", (2 * c_in, c_in))) + tuple(others), "x", aligned=True)
     return n, c_in
 
 

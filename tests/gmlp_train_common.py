@@ -2,6 +2,7 @@
 tools/bench_gmlp_train.py: the fixture gmlp_train.npz, the float64 restatement of stage 4's multi-axis gated-MLP layer (include/
 balf_hip.h: balf_gmlp_train_forward) and of its backward as closed formulas, the same through float64 autograd over oracle.oracle's
 arithmetic, the float32 torch-op composition, the error measure of the gates, and the seeded case generators."""
+import functools
 import os
 
 import numpy as np
@@ -11,6 +12,7 @@ import torch.nn.functional as F
 from oracle import oracle
 from tests import head_train_common as H
 from tests import rcab_train_common as R
+from tests import train_common as T
 
 FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gmlp_train.npz")
 FIXTURE_CASES = ("model", "layout", "edges")
@@ -25,7 +27,7 @@ GATED = ("y",) + GRADS                      # the 28 outputs
 TOL_FLOOR = H.TOL_FLOOR
 LN_EPS = 1e-5
 SD_PREFIX = "down4.residual_split_head_multi_axis_gmlp_layer."
-inputs_digest = R.inputs_digest
+inputs_digest = T.inputs_digest
 
 
 def fixture():
@@ -33,11 +35,11 @@ def fixture():
 
 
 def err(got, want64, scale):
-    """max |got - want| / S, the measure of every gate (head_train_common.err).  S = 0 -- every term of the reduction is an exact
+    """max |got - want| / S, the measure of every gate (train_common.err).  S = 0 -- every term of the reduction is an exact
     zero, as the gain gradient of a LayerNorm whose input is constant on every pixel -- demands the exact zero."""
     if scale > 0:
-        return H.err(got, want64, scale)
-    return 0.0 if H.err(got, want64, 1.0) == 0.0 else float("inf")
+        return T.err(got, want64, scale)
+    return 0.0 if T.err(got, want64, 1.0) == 0.0 else float("inf")
 
 
 def token_index(b, hc, wc, grid):
@@ -284,19 +286,8 @@ def fixture_case(fx, name):
     return layout_inputs() if name == "layout" else edges_inputs()
 
 
-def recorded_part(t):
-    """What the fixture records of a reference RESULT ``t``: all of it up to RECORD_WHOLE elements, else -- as a matrix of rows
-    of its last axis -- rows 0..7 and every 32nd row.  The fixture must stay under 1 MB, and every output is checked whole
-    against the float64 restatement anyway; d_T was taken on the whole results."""
-    if t.numel() <= RECORD_WHOLE:
-        return t
-    rows = t.reshape(-1, t.shape[-1])
-    return rows[sorted(set(range(8)) | set(range(0, rows.shape[0], 32)))]
-
-
-def recorded(fx, name, k, full):
-    """-> (the reference's recorded float32 result, the same part of ``full``)."""
-    return torch.from_numpy(fx[f"{name}.{k}"]), recorded_part(full)
+recorded_part = functools.partial(T.recorded_part, whole=RECORD_WHOLE, every=32)
+recorded = functools.partial(T.recorded, part=recorded_part)
 
 
 # ---- the float64 restatement of train_head with a TrainableMixerTail ----------------------------------------------------------

@@ -8,6 +8,9 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from tests import train_common as T
+from tests.train_common import err                # noqa: F401  (H.err, as the tests and tools name it)
+
 FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "head_train.npz")
 FIXTURE_CASES = ("model", "edges")
 PARAMS = ("w2", "b2", "wd", "bd", "gamma", "beta")
@@ -104,13 +107,6 @@ def compose_f32(x2, p, dlogits=None, running=None, eps=EPS, momentum=MOMENTUM):
     return logits.detach(), grads
 
 
-def err(got, want64, scale):
-    """max |got - want| / S, the measure of every gate."""
-    got = torch.as_tensor(np.asarray(got)).double() if not isinstance(got, torch.Tensor) else got.detach().double().cpu()
-    want64 = torch.as_tensor(np.asarray(want64)).double() if not isinstance(want64, torch.Tensor) else want64.double()
-    return float((got.reshape(want64.shape) - want64).abs().max()) / scale
-
-
 def kink_distance(h):
     """The smallest |h| among the pre-activations that are not exactly zero."""
     nz = h[h != 0]
@@ -203,24 +199,8 @@ def edges_inputs():
 
 
 def inputs_digest(*tensors):
-    """SHA-256 over the float32 bytes of the given tensors, dicts of tensors (in PARAMS order) and tuples of tensors: recorded
-    next to the reference's results, so that a drift of the seeded generators or of synth.synthetic_state_dict -- which would
-    silently pair new inputs with old results -- fails loudly instead."""
-    import hashlib
-    h = hashlib.sha256()
-
-    def feed(t):
-        if isinstance(t, dict):
-            for k in PARAMS:
-                feed(t[k])
-        elif isinstance(t, (tuple, list)):
-            for u in t:
-                feed(u)
-        else:
-            h.update(np.ascontiguousarray(t.detach().cpu().numpy().astype(np.float32)).tobytes())
-
-    feed(tensors)
-    return h.hexdigest()
+    """train_common.inputs_digest, a dict of parameters in PARAMS order."""
+    return T.inputs_digest(*tensors, keys=lambda d: PARAMS)
 
 
 def regenerated_inputs_digest(name):

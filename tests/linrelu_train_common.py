@@ -12,6 +12,7 @@ import torch.nn.functional as F
 from tests import gmlp_train_common as G
 from tests import head_train_common as H
 from tests import rcab_train_common as R
+from tests import train_common as T
 
 FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "linrelu_train.npz")
 FIXTURE_CASES = ("model", "edges", "c32", "c64")
@@ -165,9 +166,9 @@ def _flat(case):
 
 
 def regenerated_inputs_digest(name):
-    """SHA-256 of everything of case ``name`` that the fixture does not store (head_train_common.inputs_digest)."""
+    """SHA-256 of everything of case ``name`` that the fixture does not store (train_common.inputs_digest)."""
     case = {"model": model_inputs, "edges": edges_inputs, "c32": lambda: width_inputs(32), "c64": lambda: width_inputs(64)}[name]()
-    return H.inputs_digest(*_flat(case))
+    return T.inputs_digest(*_flat(case))
 
 
 def fixture_case(fx, name):

@@ -2,6 +2,7 @@
 tools/bench_tail_train.py: the fixture rcab_train.npz, the float64 restatement of stage 4's channel-attention block (LayerNorm ->
 conv1 -> LeakyReLU(0.2) -> conv2 -> squeeze-excite scale, x2 = t * s + r) and of its backward as closed formulas, the same through
 float64 autograd, the float32 torch-op composition, the error measure of the gates, and the seeded case generators."""
+import functools
 import os
 
 import numpy as np
@@ -9,6 +10,7 @@ import torch
 import torch.nn.functional as F
 
 from tests import head_train_common as H
+from tests import train_common as T
 
 FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "rcab_train.npz")
 FIXTURE_CASES = ("model", "edges")
@@ -28,7 +30,7 @@ _SD_PREFIX = "down4.residual_channel_attention_block."
 _SD_NAMES = dict(zip(PARAMS, ("norm.weight", "norm.bias", "conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias",
                               "calayer.excite.0.weight", "calayer.excite.0.bias", "calayer.excite.2.weight",
                               "calayer.excite.2.bias")))
-err = H.err
+err, inputs_digest = T.err, T.inputs_digest
 
 
 def fixture():
@@ -225,26 +227,6 @@ def edges_inputs():
     return y, r, p, dx2
 
 
-def inputs_digest(*tensors):
-    """SHA-256 over the float32 bytes of tensors, dicts (sorted keys) and tuples of them: recorded next to the reference's
-    results, so that a drift of a seeded generator or of synth.synthetic_state_dict fails loudly."""
-    import hashlib
-    h = hashlib.sha256()
-
-    def feed(t):
-        if isinstance(t, dict):
-            for k in sorted(t):
-                feed(t[k])
-        elif isinstance(t, (tuple, list)):
-            for u in t:
-                feed(u)
-        else:
-            h.update(np.ascontiguousarray(t.detach().cpu().numpy().astype(np.float32)).tobytes())
-
-    feed(tensors)
-    return h.hexdigest()
-
-
 def regenerated_inputs_digest(name):
     return inputs_digest(*(model_inputs() if name == "model" else edges_inputs()))
 
@@ -257,19 +239,8 @@ def fixture_case(fx, name):
     return edges_inputs()
 
 
-def recorded_part(t):
-    """What the fixture records of a reference RESULT ``t``: all of it up to RECORD_WHOLE elements, else -- as a matrix of
-    rows of its last axis -- rows 0..7 and every fourth row.  The fixture must stay under 1 MB, and every output is checked
-    whole against the float64 restatement anyway; d_T was taken on the whole results."""
-    if t.numel() <= RECORD_WHOLE:
-        return t
-    rows = t.reshape(-1, t.shape[-1])
-    return rows[sorted(set(range(8)) | set(range(0, rows.shape[0], 4)))]
-
-
-def recorded(fx, name, k, full):
-    """-> (the reference's recorded float32 result, the same part of ``full``)."""
-    return torch.from_numpy(fx[f"{name}.{k}"]), recorded_part(full)
+recorded_part = functools.partial(T.recorded_part, whole=RECORD_WHOLE, every=4)
+recorded = functools.partial(T.recorded, part=recorded_part)
 
 
 # ---- the float64 restatement of train_head with a TrainableTail ---------------------------------------------------------------
