@@ -220,14 +220,15 @@ def sweep_params(seed):
     return p, g
 
 
-def sweep_case(shape, seed):
+def sweep_case(shape, seed, device=None):
     """Seeded general float32 inputs for a shape -> (x0, params, g = dy), on the CPU.  x0 >= 0 with a share of exact zeros, as the
-    ReLU in front of the layer leaves it.  GELU has no kink: nothing to keep away from."""
+    ReLU in front of the layer leaves it.  GELU has no kink: nothing to keep away from.  ``device``: where the case is moved to
+    after it was drawn, on the CPU generator either way."""
     b, hc, wc = shape
     p, g = sweep_params(seed)
     x0 = (torch.randn((b, hc, wc, 256), generator=g) * (0.5 + torch.rand((b, hc, wc, 1), generator=g)) + 0.3).clamp(min=0)
     dy = torch.randn(x0.shape, generator=g) / (b * hc * wc)
-    return x0, p, dy
+    return T.to_device((x0, p, dy), device)
 
 
 def model_inputs():

@@ -127,7 +127,7 @@ def sweep_params(seed, exact_z=False):
     return p
 
 
-def sweep_case(shape, seed):
+def sweep_case(shape, seed, device=None):
     """Seeded inputs for a shape without a fixture -> (x2 [B,Hc,Wc,256], params, dlogits [B,65,Hc,Wc], (running_mean,
     running_var)), float32 on the CPU.
 
@@ -144,13 +144,16 @@ def sweep_case(shape, seed):
     in ANY float32 implementation: torch's own float32 composition on the CPU measured dw2 2.3e-5 at (1,1,2) and 1.0e-3 at
     (2,1,1) on general wd, against a gate of 1.1e-6.  So for N = 2 wd and bd are quantised too (multiples of 1/4): z = a wd^T +
     bd is a sum of multiples of 1/1024 below 2^11, exact in float32, and what remains is what these two shapes are in the sweep
-    for: the two-sample statistics, the cancellation in dz, the batch stride at one pixel per image and the smallest grids."""
+    for: the two-sample statistics, the cancellation in dz, the batch stride at one pixel per image and the smallest grids.
+
+    ``device``: where the case is moved to after it was drawn, on the CPU generator either way, so that restate64 and
+    compose_f32 run there (a shape of tens of thousands of pixels)."""
     b, hc, wc = shape
     g = torch.Generator().manual_seed(1000 + seed)
     x2 = torch.randint(-8, 9, (b, hc, wc, 256), generator=g).float() / 8
     dlogits = torch.randn((b, 65, hc, wc), generator=g) / (b * hc * wc)
     running = (torch.randn((65,), generator=g), 0.5 + torch.rand((65,), generator=g))
-    return x2, sweep_params(seed, exact_z=b * hc * wc == 2), dlogits, running
+    return T.to_device((x2, sweep_params(seed, exact_z=b * hc * wc == 2), dlogits, running), device)
 
 
 # ---- the fixture cases' inputs that need not be stored: seeded, and the checkpoint's own tail -----------------------------------

@@ -84,19 +84,20 @@ def params_of(sd):
 
 
 # ---- seeded cases -------------------------------------------------------------------------------------------------------------
-def sweep_case(n, c_in, seed):
+def sweep_case(n, c_in, seed, device=None):
     """Seeded inputs of the sweep -> (x [n, c_in], w, b, g [n, 2 c_in]), float32 on the CPU.  As head_train_common.sweep_case: x holds
     multiples of 1/8 in [-1, 1], w multiples of 1/16 in [-1/2, 1/2] and b odd multiples of 1/256, so every pre-activation is an odd
     multiple of 1/256 below 2^7, exact in float32 in any order and never closer than 1/256 to the kink; the mask of a float32
     implementation cannot differ from the restatement's.  g is general, with a sixteenth of exact zeros; dw, db and dx are general
-    float32 sums.  The float32 rounding of the product itself is covered by the fixture cases, whose inputs are general."""
+    float32 sums.  The float32 rounding of the product itself is covered by the fixture cases, whose inputs are general.
+    ``device``: where the case is moved to after it was drawn, on the CPU generator either way."""
     gen = torch.Generator().manual_seed(3000 + seed)
     x = torch.randint(-8, 9, (n, c_in), generator=gen).float() / 8
     w = torch.randint(-8, 9, (2 * c_in, c_in), generator=gen).float() / 16
     b = (2 * torch.randint(-64, 64, (2 * c_in,), generator=gen) + 1).float() / 256
     g = torch.randn((n, 2 * c_in), generator=gen) / n
     g[torch.rand((n, 2 * c_in), generator=gen) < 1 / 16] = 0.0
-    return x, w, b, g
+    return T.to_device((x, w, b, g), device)
 
 
 def keypoint_map():

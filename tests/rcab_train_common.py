@@ -161,26 +161,32 @@ def redraw_rows_near_kink(y, p, draw, margin=SWEEP_MARGIN, rounds=64):
     raise AssertionError("rows near the LeakyReLU kink remain")
 
 
-def sweep_case(shape, seed):
+def sweep_case(shape, seed, device=None):
     """Seeded general float32 inputs for a shape -> (y, r, params, g = dx2), on the CPU.  No h within SWEEP_MARGIN of 0 (rows
     redrawn), no SE pre-activation within SWEEP_MARGIN of 0 (bs0 redrawn; asserted): a float32 rounding of a pre-activation
     across 0 would change a slope by 0.8 (LeakyReLU) or 1 (ReLU) of a whole term at any tolerance, and float32 moves h by
-    3.3e-6 at most here."""
+    3.3e-6 at most here.
+
+    ``device``: every value is drawn on the CPU generator, in the same order, and moved there at once, so that the float64
+    checks of the two margins -- restate64 several times over -- and everything after them run where the tensors are (a shape
+    of tens of thousands of pixels)."""
     b, hc, wc = shape
     n_pix = b * hc * wc
     p, g = sweep_params(seed)
+    p = T.to_device(p, device)
+    on = lambda t: T.to_device(t, device)                  # noqa: E731
 
     def draw(k):
-        return torch.randn((k, 256), generator=g) * (0.5 + torch.rand((k, 1), generator=g)) + 0.3 * torch.randn((k, 1), generator=g)
+        return on(torch.randn((k, 256), generator=g) * (0.5 + torch.rand((k, 1), generator=g)) + 0.3 * torch.randn((k, 1), generator=g))
 
     y, _ = redraw_rows_near_kink(draw(n_pix), p, draw)
     y = y.reshape(b, hc, wc, 256)
-    r = y + torch.randn(y.shape, generator=g).clamp(min=0)
-    dx2 = torch.randn(y.shape, generator=g) / n_pix
+    r = y + on(torch.randn(y.shape, generator=g)).clamp(min=0)
+    dx2 = on(torch.randn(y.shape, generator=g) / n_pix)
     for _ in range(64):
         if float(restate64(y, r, p)["se_pre"].abs().min()) >= SWEEP_MARGIN:
             break
-        p["bs0"] = 0.3 * torch.randn((64,), generator=g)
+        p["bs0"] = on(0.3 * torch.randn((64,), generator=g))
     assert float(restate64(y, r, p)["se_pre"].abs().min()) >= SWEEP_MARGIN
     return y, r, p, dx2
 

@@ -20,6 +20,7 @@ from tests import gmlp_train_common as G
 from tests import head_train_common as H
 from tests import pair_synth_common as S
 from tests import rcab_train_common as R
+from tests import train_common as T
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -27,9 +28,16 @@ LOGIT_TOL = 2e-3                # the gate tests/test_forward_gpu.py applies to 
 STAGE_REL = 2e-5                # the gate of tests/test_stage_parity_gpu.py
 # one group per map; two images; regions of 1 x 2 and 2 x 1 pixels; three images with regions of 2 x 3; N = 960, where the last of
 # the 64-row blocks of the column sums is short and several groups share a workgroup of the token-mix backward (960 / 64 = 15
-# groups; 272 at the last shape, two per workgroup); N = 17408, where rows_per_slice first exceeds 256
+# groups; 272 at the last shape, two per workgroup); N = 17408 = 34 x 512: two 256-pixel chunks per K slice (rows_per_slice
+# exceeds 256 from N = 16385 on), every slice and every column block full
 SWEEP = ((1, 8, 8), (2, 8, 16), (2, 16, 8), (3, 16, 24), (1, 24, 40), (1, 128, 136))
-NAN_BYTE = 0xFF                 # a buffer of these bytes reads as NaN in float32 and in float64
+# Where the slice geometry changes (tests/test_train_geometry_host.py asserts each figure).  (1, 8, 2056), N = 16448: 512 rows per K
+# slice, S = 33 with a last slice of 64 rows; 257 groups, two per workgroup of the token-mix backward, PW = 129 with ONE group in the
+# last; the grid map's regions are 1 x 257 pixels.  (2, 216, 152), N = 65664: 1280 rows per slice, S = 52, column blocks of 80 rows, PC
+# = 821 with a last block of 64 rows; 1026 groups, five per workgroup, PW = 206 with one group in the last.  Cases and restatement on
+# the device.
+LARGE = T.LARGE_SHAPES["gmlp"]
+NAN_BYTE = 0xFF                # a buffer of these bytes reads as NaN in float32 and in float64
 
 
 @pytest.fixture(scope="module")
@@ -182,11 +190,51 @@ def test_autograd_path_against_the_reference(fx, name):
             assert bits_equal(t.grad, got["d:" + k]), k
 
 
-@pytest.mark.parametrize("shape", SWEEP, ids=lambda s: "x".join(map(str, s)))
+_LARGEST = {}
+
+
+def largest():
+    """The last case of LARGE on the device and its first run, made once -> (case, outputs)."""
+    if not _LARGEST:
+        shape = LARGE[-1]
+        c = G.sweep_case(shape, 7 + shape[1] * 100 + shape[2], device=DEV)
+        _LARGEST.update(case=c, out=run(*c))
+    return _LARGEST["case"], _LARGEST["out"]
+
+
+@pytest.mark.parametrize("shape", SWEEP + LARGE, ids=lambda s: "x".join(map(str, s)))
 def test_shape_sweep(fx, shape):
-    x0, p, g = G.sweep_case(shape, 7 + shape[1] * 100 + shape[2])
+    if shape not in LARGE:
+        x0, p, g = G.sweep_case(shape, 7 + shape[1] * 100 + shape[2])
+        res = G.restate64(x0, p, g)
+        check_against(run(x0, p, g), res, fx, str(shape))
+        return
+    # the same gates with the case, the float64 restatement and the float32 composition on the device
+    if shape == LARGE[-1]:
+        (x0, p, g), out = largest()
+    else:
+        x0, p, g = G.sweep_case(shape, 7 + shape[1] * 100 + shape[2], device=DEV)
+        out = run(x0, p, g)
     res = G.restate64(x0, p, g)
-    check_against(run(x0, p, g), res, fx, str(shape))
+    y, grads = G.compose_f32(x0, p, g)
+    T.composition_figures(str(shape), dict(grads, y=y), res, G.GATED, measure=G.err)
+    check_against(out, res, fx, str(shape))
+
+
+def test_largest_shape_gives_the_same_bits_again_and_without_dx0():
+    """The fixed summation order over PC = 821 column blocks of 80 rows, 4 * PW = 824 wave partials of the token mix and S = 52
+    slabs; and ln_bwd_kernel<false>, the instantiation without dx0, at that block height: the parameter gradients are the same
+    bits."""
+    c, a = largest()
+    b = run(*c)
+    for k in G.GATED:
+        assert bits_equal(a[k], b[k]), k
+        assert bool(torch.isfinite(a[k]).all()), k
+    del b
+    lean = run(*c, want_dx0=False)
+    assert lean["dx0"] is None
+    for k in G.GATED[:-1]:
+        assert bits_equal(a[k], lean[k]), k
 
 
 def test_bitwise_repeatability():

@@ -14,11 +14,17 @@ from balf_amd.model.head_train import TrainableHead
 from balf_amd.utils import synth, train_utils
 from tests import head_train_common as H
 from tests import pair_synth_common as S
+from tests import train_common as T
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 LOGIT_TOL = 2e-3                # the gate tests/test_forward_gpu.py applies to the logits of the forward
 SWEEP = ((1, 1, 2), (2, 1, 1), (1, 3, 5), (1, 8, 8), (1, 5, 13), (2, 7, 9), (3, 24, 24), (2, 23, 37), (4, 32, 32))
+# Where the slice geometry changes (tests/test_train_geometry_host.py asserts each figure).  N = 16899: 512 rows per K slice, S = 34
+# with a last slice of 3 rows, a last column block of 3 rows, P = 17 row partials.  N = 66049: 1280 rows per slice, S = 52 with a
+# last slice of 769 rows (769 mod 16 = 1), column blocks of 80 rows, PC = 826 with a last block of 49 rows, and P = 65: one lane of
+# wave_sum_strided takes a second trip through the channel-major partials.  Cases and restatement on the device.
+LARGE = T.LARGE_SHAPES["head"]
 NAN_BYTE = 0xFF                 # a buffer of these bytes reads as NaN in float32 and in float64
 
 
@@ -68,7 +74,7 @@ def check_against(out, r, fx, what, names=H.GATED):
         assert np.isfinite(e) and e <= float(fx[f"tol_{k}"]), (what, k, e, float(fx[f"tol_{k}"]))
     if out.get("prob") is not None:
         # softmax is 2-Lipschitz in the largest logit error; exp and the division add a few float32 roundings of values <= 1
-        e = float((out["prob"].double().cpu() - r["prob"]).abs().max())
+        e = float((out["prob"].double().to(r["prob"].device) - r["prob"]).abs().max())
         print(what, f"prob {e:.2e}")
         assert e <= 2 * float(fx["tol_logits"]) * r["S"]["logits"] + 4e-7, (what, "prob", e)
     return errs
@@ -131,11 +137,47 @@ def test_autograd_path_against_the_reference(fx, name):
         assert head(x2.to(DEV))["logits"].grad_fn is None and int(head.norm.num_batches_tracked) == 3
 
 
-@pytest.mark.parametrize("shape", SWEEP, ids=lambda s: "x".join(map(str, s)))
+_LARGEST = {}
+
+
+def largest():
+    """The last case of LARGE on the device and its first run, made once -> (case, outputs)."""
+    if not _LARGEST:
+        shape = LARGE[-1]
+        c = H.sweep_case(shape, 7 + shape[1] * 100 + shape[2], device=DEV)
+        _LARGEST.update(case=c, out=run(*c))
+    return _LARGEST["case"], _LARGEST["out"]
+
+
+@pytest.mark.parametrize("shape", SWEEP + LARGE, ids=lambda s: "x".join(map(str, s)))
 def test_shape_sweep(fx, shape):
-    x2, p, dlogits, running = H.sweep_case(shape, 7 + shape[1] * 100 + shape[2])
+    if shape not in LARGE:
+        x2, p, dlogits, running = H.sweep_case(shape, 7 + shape[1] * 100 + shape[2])
+        r = H.restate64(x2, p, dlogits, running=running)
+        check_against(run(x2, p, dlogits, running), r, fx, str(shape))
+        return
+    # the same gates with the case and the float64 restatement on the device
+    if shape == LARGE[-1]:
+        (x2, p, dlogits, running), out = largest()
+    else:
+        x2, p, dlogits, running = H.sweep_case(shape, 7 + shape[1] * 100 + shape[2], device=DEV)
+        out = run(x2, p, dlogits, running)
     r = H.restate64(x2, p, dlogits, running=running)
-    check_against(run(x2, p, dlogits, running), r, fx, str(shape))
+    # the float32 composition on the CPU, where its three products take under a second: F.batch_norm of torch 2.10 / ROCm 7.0 on the
+    # device ended the process (a segmentation fault inside torch) at [1, 65, 257, 257], and the figure needs no device (DESIGN.md 7q)
+    cx2, cp, cg, (rm, rv) = T.to_device((x2, p, dlogits, (running[0].clone(), running[1].clone())), torch.device("cpu"))
+    logits, grads = H.compose_f32(cx2, cp, cg, running=(rm, rv))
+    T.composition_figures(str(shape), dict(grads, logits=logits, running_mean=rm, running_var=rv), r, H.GATED)
+    check_against(out, r, fx, str(shape))
+
+
+def test_largest_shape_gives_the_same_bits_again():
+    """The fixed summation order over more than 64 partials per channel, PC = 826 column blocks and S = 52 slabs."""
+    c, a = largest()
+    b = run(*c)
+    for k in H.GATED + ("prob",):
+        assert bits_equal(a[k], b[k]), k
+        assert bool(torch.isfinite(a[k]).all()), k
 
 
 def test_bitwise_repeatability():

@@ -20,14 +20,21 @@ from tests import head_train_common as H
 from tests import linrelu_train_common as L
 from tests import pair_synth_common as S
 from tests import rcab_train_common as R
+from tests import train_common as T
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 LOGIT_TOL = 2e-3                # the gate tests/test_gmlp_train_gpu.py applies to the mixer's logits against the model's forward
 # (N, c_in): N = 1, 63, 64, 257 -- partial GEMM tiles in M and a partial last 16-row MFMA tile; N = 960 -- S = 4 slices of which the
-# last is short, 15 workgroups of the mask kernel; N = 17408 -- where rows_per_slice first exceeds 256
+# last is short, 15 workgroups of the mask kernel; N = 17408 = 34 x 512 -- two 256-pixel chunks per K slice (rows_per_slice exceeds
+# 256 from N = 16385 on), every slice and every block of the mask kernel full
 SWEEP = ((1, 128), (63, 128), (960, 128), (17408, 128), (64, 32), (257, 32), (64, 64), (257, 64))
-NAN_BYTE = 0xFF                 # a buffer of these bytes reads as NaN in float32 and in float64
+# Where the slice geometry changes (tests/test_train_geometry_host.py asserts each figure).  N = 16899: 512 rows per K slice, S = 34
+# with a last slice of 3 rows, a last block of 3 rows.  N = 65536: the last N with blocks of 64 rows, S = 64 and PC = 1024, both caps
+# at once.  N = 65537: the first N with blocks of 80 rows -- 1280 rows per slice, S = 52, PC = 820 with a last block of 17 rows -- at
+# c_in = 32 and 128, the 16 and the 4 rows in flight of the mask kernel.  Cases and restatement on the device.
+LARGE = T.LARGE_SHAPES["linrelu"]
+NAN_BYTE = 0xFF                # a buffer of these bytes reads as NaN in float32 and in float64
 
 
 @pytest.fixture(scope="module")
@@ -95,13 +102,45 @@ def test_fixture_parity(fx, name):
         assert all(bool(torch.isfinite(out[k]).all()) for k in L.GATED)
 
 
-@pytest.mark.parametrize("n,c_in", SWEEP, ids=lambda v: str(v))
+_LARGEST = {}
+
+
+def largest():
+    """The last case of LARGE on the device and its first run, made once -> (case, outputs)."""
+    if not _LARGEST:
+        n, c_in = LARGE[-1]
+        c = L.sweep_case(n, c_in, n + c_in, device=DEV)
+        _LARGEST.update(case=c, out=run(*c))
+    return _LARGEST["case"], _LARGEST["out"]
+
+
+@pytest.mark.parametrize("n,c_in", SWEEP + LARGE, ids=lambda v: str(v))
 def test_shape_sweep(fx, n, c_in):
-    x, w, b, g = L.sweep_case(n, c_in, n + c_in)
-    res = L.restate64(x, w, b, g)
-    out = run(x, w, b, g)
-    check_against(out, res, fx, f"N {n} c_in {c_in}")
-    assert bool((out["y"].cpu().double() == res["y"]).all())   # every pre-activation of the sweep is exact in float32
+    what = f"N {n} c_in {c_in}"
+    if (n, c_in) not in LARGE:
+        x, w, b, g = L.sweep_case(n, c_in, n + c_in)
+        res = L.restate64(x, w, b, g)
+        out = run(x, w, b, g)
+    else:                       # the same gates with the case, the float64 restatement and the float32 composition on the device
+        if (n, c_in) == LARGE[-1]:
+            (x, w, b, g), out = largest()
+        else:
+            x, w, b, g = L.sweep_case(n, c_in, n + c_in, device=DEV)
+            out = run(x, w, b, g)
+        res = L.restate64(x, w, b, g)
+        y, grads = L.compose_f32(x, w, b, g)
+        T.composition_figures(what, dict(grads, y=y), res, L.GATED, measure=L.err)
+    check_against(out, res, fx, what)
+    assert bool((out["y"].double().to(res["y"].device) == res["y"]).all())     # every pre-activation of the sweep is exact in float32
+
+
+def test_largest_shape_gives_the_same_bits_again():
+    """The fixed summation order over PC = 820 column blocks of 80 rows and S = 52 slabs."""
+    c, a = largest()
+    b = run(*c)
+    for k in L.GATED:
+        assert bits_equal(a[k], b[k]), k
+        assert bool(torch.isfinite(a[k]).all()), k
 
 
 def test_derivative_at_zero_and_select_under_dead_units():

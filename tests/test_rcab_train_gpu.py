@@ -17,6 +17,7 @@ from oracle import oracle
 from tests import head_train_common as H
 from tests import pair_synth_common as S
 from tests import rcab_train_common as R
+from tests import train_common as T
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -25,7 +26,12 @@ STAGE_REL = 2e-5                # the gate of tests/test_stage_parity_gpu.py
 # one pixel per image (dm / 1, the SE mean of one value); N below one GEMM tile and N no multiple of 64; S = 9 slabs at N = 2304;
 # images of 851 pixels, which start and end inside the 64-row blocks of the sums over all pixels; N = 4096
 SWEEP = ((1, 1, 2), (2, 1, 1), (1, 3, 5), (1, 8, 8), (1, 5, 13), (2, 7, 9), (3, 24, 24), (2, 23, 37), (4, 32, 32))
-NAN_BYTE = 0xFF                 # a buffer of these bytes reads as NaN in float32 and in float64
+# Where the slice geometry changes (tests/test_train_geometry_host.py asserts each figure).  N = 16899: 512 rows per K slice, S = 34
+# with a last slice of 3 rows, a last column block of 3 rows.  (2, 257, 257), N = 132098: 2304 rows per slice, S = 58, column blocks
+# of 144 rows, PC = 918 with a last block of 50 rows; an image of 66049 pixels is summed in PI = 1017 blocks of 65 rows with a last
+# block of 9 rows, and image 1 begins inside column block 458.  Cases, margin checks and restatement on the device.
+LARGE = T.LARGE_SHAPES["rcab"]
+NAN_BYTE = 0xFF                # a buffer of these bytes reads as NaN in float32 and in float64
 
 
 @pytest.fixture(scope="module")
@@ -166,11 +172,50 @@ def _rcab_apply(tail, y, r):
     return _RcabTrain.apply(y, r, *tail.rcab_parameters())
 
 
-@pytest.mark.parametrize("shape", SWEEP, ids=lambda s: "x".join(map(str, s)))
+_LARGEST = {}
+
+
+def largest():
+    """The last case of LARGE on the device and its first run, made once -> (case, outputs)."""
+    if not _LARGEST:
+        shape = LARGE[-1]
+        c = R.sweep_case(shape, 7 + shape[1] * 100 + shape[2], device=DEV)
+        _LARGEST.update(case=c, out=run(*c))
+    return _LARGEST["case"], _LARGEST["out"]
+
+
+@pytest.mark.parametrize("shape", SWEEP + LARGE, ids=lambda s: "x".join(map(str, s)))
 def test_shape_sweep(fx, shape):
-    y, r, p, g = R.sweep_case(shape, 7 + shape[1] * 100 + shape[2])
+    if shape not in LARGE:
+        y, r, p, g = R.sweep_case(shape, 7 + shape[1] * 100 + shape[2])
+        res = R.restate64(y, r, p, g)
+        check_against(run(y, r, p, g), res, fx, str(shape))
+        return
+    # the same gates with the case (its margin checks too), the float64 restatement and the float32 composition on the device
+    if shape == LARGE[-1]:
+        (y, r, p, g), out = largest()
+    else:
+        y, r, p, g = R.sweep_case(shape, 7 + shape[1] * 100 + shape[2], device=DEV)
+        out = run(y, r, p, g)
     res = R.restate64(y, r, p, g)
-    check_against(run(y, r, p, g), res, fx, str(shape))
+    x2, grads = R.compose_f32(y, r, p, g)
+    T.composition_figures(str(shape), dict(grads, x2=x2), res, R.GATED)
+    check_against(out, res, fx, str(shape))
+
+
+def test_largest_shape_gives_the_same_bits_again_and_without_dy():
+    """The fixed summation order over PC = 918 column blocks of 144 rows, PI = 1017 image blocks of 65 rows and S = 58 slabs; and
+    ln_bwd_kernel<false>, the instantiation without dy, at that block height: the parameter gradients are the same bits."""
+    c, a = largest()
+    b = run(*c)
+    for k in R.GATED:
+        assert bits_equal(a[k], b[k]), k
+        assert bool(torch.isfinite(a[k]).all()), k
+    del b
+    lean = run(*c, want_dy=False)
+    assert lean["dy"] is None
+    for k in R.GATED[:-1]:
+        assert bits_equal(a[k], lean[k]), k
 
 
 def test_bitwise_repeatability():

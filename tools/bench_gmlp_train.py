@@ -14,8 +14,8 @@ Shapes: 4 x 24 x 24 (the reference's training batch: four 192-pixel patches) and
 * the FLOPs of the matrix products (the channel products and the three token products per branch) and the achieved FLOP/s of the
   HIP step -- a whole-step rate that includes the launch gaps and the row kernels, not a kernel's share of peak;
 * the 28 outputs of both paths against the float64 restatement of the tests, evaluated on the device, in the gates' measure, on
-  the inputs of the tests' sweep: `against_float64`.  The suite stops at N = 17408, so the 16 x 64 x 80 run (N = 81920) is what
-  vouches for longer slices and for five groups per workgroup of the token-mix backward.
+  the inputs of the tests' sweep: `against_float64`.  The suite gates the same at N = 65664 (1280-pixel slices,
+  80-row column blocks, five groups per workgroup of the token-mix backward); the 16 x 64 x 80 run is the figure at the size timed.
 
 `--hip-only`: the HIP steps alone, a few of them, for a kernel trace.  The exit status is 0 either way: DESIGN.md 7n records what
 was found."""

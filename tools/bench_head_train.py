@@ -61,8 +61,8 @@ def stats(v):
 def accuracy(dev, b, hc, wc):
     """Both paths against the float64 restatement (tests/head_train_common.py: restate64, evaluated on the device) in the
     gates' measure err(T) = max |T - T64| / S_T, on the dyadic inputs of the tests' shape sweep (sweep_case: h is exact in
-    float32, so no ReLU mask element can flip by a rounding).  The test suite stops at N = 4096; this is what vouches for the
-    slices of more than 256 pixels and the column blocks of more than 64 rows that larger N use."""
+    float32, so no ReLU mask element can flip by a rounding).  The test suite gates the same at N = 66049 (slices of
+    1280 pixels, column blocks of 80 rows, 65 row partials); this is the figure at the size that is timed."""
     x2, p, dlogits, running = H.sweep_case((b, hc, wc), 900 + b)
     x2, dlogits = x2.to(dev), dlogits.to(dev)
     p = {k: v.to(dev) for k, v in p.items()}

@@ -15,8 +15,8 @@ x3.grad as well:
   them; median and spread ((max - min) / median) of the three;
 * the new layer alone (`ops.linrelu_train_forward` + `ops.linrelu_train_backward`), timed the same way;
 * the four outputs of the new layer on both paths against the float64 restatement of the tests, evaluated on the device, in the
-  gates' measure, on the inputs of the tests' sweep: `against_float64`.  The suite stops at N = 17408, so the 16 x 64 x 80 run (N =
-  81920) is what vouches for longer slices.
+  gates' measure, on the inputs of the tests' sweep: `against_float64`.  The suite gates the same at N = 65537 (1280-pixel
+  slices, 80-row blocks); the 16 x 64 x 80 run (N = 81920) is the figure at the size that is timed.
 
 `--hip-only`: the HIP steps alone, a few of them, for a kernel trace.  The exit status is 0 either way: DESIGN.md 7o records what
 was found."""

@@ -19,7 +19,8 @@ Shapes: 4 x 24 x 24 (the reference's training batch: four 192-pixel patches) and
   handful of the general pre-activations round to the other side of a kink in one path or the other, each worth a whole term);
 * the block's twelve outputs of both paths against the float64 restatement of the tests, evaluated on the device, in the
   gates' measure, on the inputs of the tests' sweep (no pre-activation within 1e-3 of a kink): `against_float64`.  The suite
-  stops at N = 4096, so this is what vouches for the slices of more than 256 pixels and the row blocks of more than 64 rows.
+  gates the same at (2, 257, 257), the smallest shape with row blocks of more than 64 rows; this is the figure at
+  the size that is timed.
 
 `--hip-only`: the HIP steps alone, a few of them, for a kernel trace.  The exit status is 0 either way: nobody had measured
 either side when this tool was written, and DESIGN.md 7m records what it found."""
