@@ -625,8 +625,9 @@ int balf_head_train_backward(const float *dlogits_dev, const float *x2_dev, cons
  *              dy = g + rstd (u - mean_c u - xhat mean_c(u xhat))  (dy_dev NULL ok) -- the gradient at the block's input, its own
  *              shortcut included.  The long shortcut's gradient is g itself and is not written.
  * saved_dev: an opaque caller-owned block of balf_rcab_train_saved_bytes bytes that the forward writes and the backward of the
- * same (B, Hc, Wc) reads: n, a, t [N,256], (mean, rstd) per pixel, m, e, s per image.  The backward recomputes xhat from y and
- * the saved (mean, rstd) with the forward's operations (ln_g may be 0).
+ * same (B, Hc, Wc) reads: n, a, t [N,256], (mean, rstd) per pixel, m [256], e [64], s [256] per image as float64, and s once more
+ * as float32 (the factor of x2).  The backward recomputes xhat from y and the saved (mean, rstd) with the forward's operations
+ * (ln_g may be 0).
  * Arithmetic: the six 256 x 256 products run on v_mfma_f32_16x16x4_f32 (the GEMM of the head, train_gemm.h), dwc1 / dwc2 over
  * S = ceil(N / rows) slices of the pixels with a float64 slab sum, as dW2 of the head.  A LayerNorm row is one wave, four
  * channels per lane, every channel sum (v0 + v1) + (v2 + v3) and then the xor butterfly.  Every sum over pixels (m, ds, dbc1,
