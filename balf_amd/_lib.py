@@ -19,6 +19,7 @@ PYR_SRC_U8, PYR_SRC_F32, PYR_SRC_LEVEL = 0, 1, 2                   # include/bal
 PYR_MAX_RADIUS, MAX_PYRAMID_LEVELS = 8, 32
 VAL_LEG_GREEDY, VAL_LEG_WINDOW = 0, 1                              # include/balf_hip.h: balf_val_points
 STATUS_SCORE, STATUS_RANGE, STATUS_SE, STATUS_WORDS = 0, 1, 2, 4      # include/balf_hip.h: balf_forward_status
+OPTIM_MAX_TENSORS = 64                                             # include/balf_hip.h: balf_adam_step / balf_sgd_step
 
 # name -> (restype, argtypes); kept in step with include/balf_hip.h (tests/test_abi.py checks)
 _vp, _i, _sz, _fp = C.c_void_p, C.c_int, C.c_size_t, C.c_void_p
@@ -108,6 +109,10 @@ PROTOTYPES = {
     "balf_linrelu_train_workspace_bytes": (_sz, [_i, _i]),
     "balf_linrelu_train_forward": (_i, [_fp, _fp, _fp, _i, _i, _fp, _vp]),
     "balf_linrelu_train_backward": (_i, [_fp, _fp, _fp, _fp, _i, _i, _fp, _fp, _fp, _vp, _sz, _vp]),
+    "balf_optim_chunk_elems": (_i, []),
+    "balf_adam_step": (_i, [_i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(C.c_int64), C.c_double,
+                           C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64, _vp]),
+    "balf_sgd_step": (_i, [_i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(C.c_int64), C.c_double, _vp]),
     "balf_profile_num_slots": (_i, []),
     "balf_profile_slot_name": (C.c_char_p, [_i]),
     "balf_profile_begin": (_i, []),

@@ -981,3 +981,137 @@ def linrelu_train_backward(g: torch.Tensor, y: torch.Tensor, x: torch.Tensor, we
                                             db.data_ptr(), _ptr(dx), ws.data_ptr(), ws.numel(), current_stream_ptr(dev)),
               "balf_linrelu_train_backward")
     return LinreluTrainBackward(dw, db, dx)
+
+
+class OptimArgumentError(BalfHipError, ValueError):
+    """A tensor handed to the optimiser step is not what the kernel takes (also a ValueError: torch's optimisers raise that)."""
+
+
+class OptimPointers:
+    """What balf_adam_step / balf_sgd_step take of up to ``_lib.OPTIM_MAX_TENSORS`` parameters, gathered once and kept by the caller
+    across steps: the host arrays of the parameters' (and, for Adam, the two moments') device pointers and element counts, and the
+    array that each step fills with that step's gradient pointers.  ``key``: the ``data_ptr`` of every tensor it was made of -- a
+    holder compares it to know when to gather again."""
+    __slots__ = ("n", "device", "index", "numels", "key", "p", "m", "v", "numel", "g")
+
+
+def _optim_tensor_check(t, name: str, dev, numel=None) -> None:
+    if not isinstance(t, torch.Tensor) or t.layout != torch.strided:
+        raise OptimArgumentError(f"{name} must be a dense tensor (sparse gradients are not supported)")
+    if t.dtype != torch.float32:
+        raise OptimArgumentError(f"{name} must be float32, got {t.dtype}")
+    if not t.is_contiguous():
+        raise OptimArgumentError(f"{name} must be contiguous")
+    if t.device != dev:
+        raise OptimArgumentError(f"{name} is on {t.device}, params[0] on {dev}")
+    if numel is not None and t.numel() != numel:
+        raise OptimArgumentError(f"{name} has {t.numel()} elements, its parameter {numel}")
+
+
+def optim_pointers(params, exp_avgs=None, exp_avg_sqs=None) -> OptimPointers:
+    """Check and gather 1..64 parameters (and their moments: both lists or neither) -> :class:`OptimPointers`.  Every tensor is
+    float32, contiguous and on the GPU of ``params[0]``; a moment has its parameter's element count."""
+    n = len(params)
+    adam = exp_avgs is not None
+    if (exp_avg_sqs is not None) != adam:
+        raise BalfHipError("optim_pointers: give both moment lists or neither")
+    if not 1 <= n <= _lib.OPTIM_MAX_TENSORS or (adam and not len(exp_avgs) == len(exp_avg_sqs) == n):
+        raise BalfHipError(f"optim_pointers: 1..{_lib.OPTIM_MAX_TENSORS} parameters and as many of each moment, got {n}")
+    dev = params[0].device if isinstance(params[0], torch.Tensor) else None
+    for i, t in enumerate(params):
+        _optim_tensor_check(t, f"params[{i}]", dev)
+    for name, ts in (("exp_avgs", exp_avgs), ("exp_avg_sqs", exp_avg_sqs)):
+        for i, t in enumerate(ts or ()):
+            _optim_tensor_check(t, f"{name}[{i}]", dev, params[i].numel())
+    require_gpu_tensor(params[0], "params[0]")
+    o = OptimPointers()
+    o.n, o.device, o.index = n, dev, params[0].get_device()
+    o.numels = tuple(t.numel() for t in params)
+    lists = (params, exp_avgs, exp_avg_sqs) if adam else (params,)
+    o.key = tuple(t.data_ptr() for ts in lists for t in ts)
+    arr = C.c_void_p * n
+    o.p = arr(*o.key[:n])
+    o.m = arr(*o.key[n:2 * n]) if adam else None
+    o.v = arr(*o.key[2 * n:]) if adam else None
+    o.numel = (C.c_int64 * n)(*o.numels)
+    o.g = arr()
+    return o
+
+
+_F32, _STRIDED = torch.float32, torch.strided
+
+
+def _optim_gradients(o: OptimPointers, grads) -> None:
+    """This step's gradient pointers into ``o.g``; None (the parameter is skipped) as NULL.  This loop is most of what a step costs
+    the host: one look per property, the message made only when one fails."""
+    if len(grads) != o.n:
+        raise BalfHipError(f"{len(grads)} gradients for {o.n} parameters")
+    garr, numels, index = o.g, o.numels, o.index
+    for i, g in enumerate(grads):
+        if g is None:
+            garr[i] = None
+        elif (g.dtype is _F32 and g.layout is _STRIDED and g.get_device() == index and g.numel() == numels[i]
+              and g.is_contiguous()):
+            garr[i] = g.data_ptr()
+        else:
+            _optim_tensor_check(g, f"grads[{i}]", o.device, numels[i])
+            raise BalfHipError(f"grads[{i}] is not what the kernel takes")        # (not reached: the check above names the reason)
+
+
+def _optim_runs(n: int):
+    return [(at, min(n, at + _lib.OPTIM_MAX_TENSORS)) for at in range(0, n, _lib.OPTIM_MAX_TENSORS)]
+
+
+def _raw_stream(index: int) -> int:
+    """The current stream of device ``index`` as the pointer the library takes: torch's direct accessor where this build has
+    it (a tenth of the cost of making a ``torch.cuda.Stream`` object, which shows in a 37 us step), else through that object."""
+    get = getattr(torch._C, "_cuda_getCurrentRawStream", None)
+    return get(index) if get is not None else torch.cuda.current_stream(index).cuda_stream
+
+
+def _optim_launch(o: OptimPointers, call) -> int:
+    """``call(stream)`` with ``o``'s device current: without the context manager when it already is (the common case)."""
+    if torch.cuda.current_device() == o.index:
+        return call(_raw_stream(o.index))
+    with torch.cuda.device(o.device):
+        return call(_raw_stream(o.index))
+
+
+def adam_step(params, grads, exp_avgs, exp_avg_sqs, lr: float, beta1: float, beta2: float, eps: float, weight_decay: float,
+              step: int, pointers: Optional[OptimPointers] = None) -> None:
+    """One step of ``torch.optim.Adam`` (amsgrad=False, maximize=False, L2 weight decay) in place on lists of tensors, ONE launch per
+    64 tensors (balf_adam_step in include/balf_hip.h).  ``grads[i]`` None skips parameter i: it and its moments keep their bits.
+    ``step`` is the number of this step (1 for the first) and is shared by all the tensors.  Every tensor is float32, contiguous and
+    on one GPU, a gradient and the moments have their parameter's element count; lists longer than 64 are split into several calls.
+    ``pointers``: :func:`optim_pointers` of exactly these parameters and moments (at most 64), kept by the caller across steps --
+    then only the gradients are looked at."""
+    if pointers is not None:
+        if len(params) != pointers.n or pointers.m is None:
+            raise BalfHipError("adam_step: pointers were not gathered from these lists")
+        runs = ((pointers, grads),)
+    else:
+        if not len(params) == len(grads) == len(exp_avgs) == len(exp_avg_sqs) or not params:
+            raise BalfHipError("adam_step: four non-empty lists of one length")
+        runs = [(optim_pointers(params[a:b], exp_avgs[a:b], exp_avg_sqs[a:b]), grads[a:b]) for a, b in _optim_runs(len(params))]
+    fn = lib().balf_adam_step
+    step = int(step)
+    for o, gs in runs:
+        _optim_gradients(o, gs)
+        check(_optim_launch(o, lambda stream: fn(o.n, o.p, o.g, o.m, o.v, o.numel, lr, beta1, beta2, eps, weight_decay, step, stream)),
+              "balf_adam_step")
+
+
+def sgd_step(params, grads, lr: float, pointers: Optional[OptimPointers] = None) -> None:
+    """``p -= lr * g`` in place on lists of tensors, one launch per 64 tensors (balf_sgd_step); the rules of :func:`adam_step`."""
+    if pointers is not None:
+        if len(params) != pointers.n:
+            raise BalfHipError("sgd_step: pointers were not gathered from these lists")
+        runs = ((pointers, grads),)
+    else:
+        if len(params) != len(grads) or not params:
+            raise BalfHipError("sgd_step: two non-empty lists of one length")
+        runs = [(optim_pointers(params[a:b]), grads[a:b]) for a, b in _optim_runs(len(params))]
+    fn = lib().balf_sgd_step
+    for o, gs in runs:
+        _optim_gradients(o, gs)
+        check(_optim_launch(o, lambda stream: fn(o.n, o.p, o.g, o.numel, lr, stream)), "balf_sgd_step")

@@ -1,7 +1,9 @@
 """The inference / evaluation helpers of /root/reference/balf/utils/train_utils.py with every stage on the GPU.
 Of training (``train_model``, train_utils.py:79-160) the head's part is here: ``train_head`` fits the trainable tail on the
 features of the frozen encoder (:mod:`balf_amd.model.head_train`) against :mod:`balf_amd.loss.loss_function`; the encoder's
-backward is out of scope, optimisers are torch's.
+backward is out of scope.  The set-up of the reference's train.py is here too: ``build_optimizer`` (:mod:`balf_amd.optim`'s fused
+Adam / SGD for GPU parameters), ``build_scheduler``, ``WarmRestart``, ``LinearDecay`` and ``ckpt_state`` (train_utils.py:20-76,
+199-203); ``train_model`` itself is not.
 
 * ``extract_detections`` (train_utils.py:416-454) -- see :mod:`balf_amd.pipeline`.
 * ``compute_repeatability_with_maximum_filter`` (train_utils.py:170-196): window-max NMS of both score maps, common-
@@ -18,6 +20,9 @@ backward is out of scope, optimisers are torch's.
 * ``train_head``: one epoch of ``train_model``'s step (train_utils.py:104-124) for the head alone, encoder frozen.
 """
 from __future__ import annotations
+
+import logging
+import math
 
 import numpy as np
 import torch
@@ -232,7 +237,8 @@ def train_head(dataloader, model, head, optimizer, device, grid_size=8, chunk_ba
     frozen and runs on the forward kernels (``model.encode``), ``head`` (``model.head_train.TrainableHead``, or one of
     ``model.tail_train.TrainableTail``, ``model.mixer_train.TrainableMixerTail`` and ``model.stage4_train.TrainableStage4`` -- all
     of stage 4 --, whose ``encode_level`` attribute selects ``model.encode(x, level=...)``) runs forward in
-    training mode and backward on the library, ``optimizer`` (torch's, over ``head.parameters()``) steps once per loader batch.
+    training mode and backward on the library, ``optimizer`` (any ``torch.optim.Optimizer`` over ``head.parameters()``; the intended
+    one is ``balf_amd.optim.FusedAdam``, one launch per step, which ``build_optimizer`` returns) steps once per loader batch.
     ``dataloader`` yields the reference's 6-tuples ``(images_src, images_dst, heatmap_src, heatmap_dst, h_src_2_dst,
     h_dst_2_src)``; images ``[B,3,H,W]`` with H, W multiples of 64.  Per chunk of ``chunk_batches`` batches: every source and
     destination batch is encoded, the split-f16 guard is asked (``fp16_guard_check(synchronize=True)``), and on a flag -- found
@@ -284,3 +290,85 @@ def train_head(dataloader, model, head, optimizer, device, grid_size=8, chunk_ba
     if not values:
         raise ValueError("train_head: the dataloader is empty")
     return float(np.concatenate(values).astype(np.float64).mean())
+
+
+# ---- what the reference's train.py sets a run up with (train_utils.py:20-76,199-203) ------------------------------------------------
+def _all_float32_on_gpu(params) -> bool:
+    """Every parameter -- of a list of tensors or of a list of group dicts -- is a dense float32 tensor on a GPU."""
+    tensors = []
+    for entry in params:
+        tensors.extend(entry["params"] if isinstance(entry, dict) else [entry])
+    return bool(tensors) and all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32
+                                 and t.layout == torch.strided for t in tensors)
+
+
+def build_optimizer(params, optim_cfg):
+    """The reference's ``build_optimizer``: ``optim_cfg['name']`` 'adam' (``lr``, ``weight_decay``) or 'sgd' (``lr``), anything
+    else a ValueError.  For float32 parameters on a GPU the optimiser is ``balf_amd.optim.FusedAdam`` / ``FusedSGD`` -- the same
+    update in one launch per group, with a ``state_dict`` that torch's class loads and vice versa --, otherwise
+    (parameters on the CPU, another dtype) it is torch's own class."""
+    from .. import optim as fused_optim
+    logging.info("build_optimizer: %s", optim_cfg['name'])
+    params = list(params)
+    fused = _all_float32_on_gpu(params)
+    if optim_cfg['name'] == 'adam':
+        cls = fused_optim.FusedAdam if fused else torch.optim.Adam
+        return cls(params, lr=optim_cfg['lr'], weight_decay=optim_cfg['weight_decay'])
+    if optim_cfg['name'] == 'sgd':
+        cls = fused_optim.FusedSGD if fused else torch.optim.SGD
+        return cls(params, lr=optim_cfg['lr'])
+    raise ValueError("Optimizer [%s] not recognized." % optim_cfg['name'])
+
+
+class WarmRestart(torch.optim.lr_scheduler.CosineAnnealingLR):
+    """Cosine annealing from the base lr to ``eta_min`` over ``T_max`` epochs in closed form, started again from the base lr when
+    the epoch counter reaches ``T_max`` (the counter returns to 0 and the period is multiplied by ``T_mult``)."""
+
+    def __init__(self, optimizer, T_max=30, T_mult=1, eta_min=0, last_epoch=-1):
+        self.T_mult = T_mult
+        super().__init__(optimizer, T_max, eta_min, last_epoch)
+
+    def get_lr(self):
+        if self.last_epoch == self.T_max:
+            self.last_epoch = 0
+            self.T_max *= self.T_mult
+        half_cos = (1 + math.cos(math.pi * self.last_epoch / self.T_max)) / 2        # 1 at a (re)start, 0 at T_max
+        return [self.eta_min + (base - self.eta_min) * half_cos for base in self.base_lrs]
+
+
+class LinearDecay(torch.optim.lr_scheduler.LRScheduler):
+    """The base lr until ``start_epoch``, then a straight line that falls by ``(base - min_lr) / max_epoch`` per epoch."""
+
+    def __init__(self, optimizer, max_epoch, start_epoch=0, min_lr=0, last_epoch=-1):
+        self.max_epoch, self.start_epoch, self.min_lr = max_epoch, start_epoch, min_lr
+        super().__init__(optimizer, last_epoch)
+
+    def get_lr(self):
+        past = self.last_epoch - self.start_epoch
+        if past < 0:
+            return self.base_lrs
+        return [base - ((base - self.min_lr) / self.max_epoch) * past for base in self.base_lrs]
+
+
+def build_scheduler(optimizer, total_epochs, last_epoch, scheduler_cfg):
+    """The reference's ``build_scheduler``: ``scheduler_cfg['name']`` 'plateau' (``patience``, ``factor``, ``min_lr``), 'sgdr'
+    (:class:`WarmRestart` with its defaults) or 'linear' (:class:`LinearDecay`: ``min_lr``, ``start_epoch``, resumed at
+    ``last_epoch``), anything else a ValueError."""
+    logging.info("build_scheduler: %s", scheduler_cfg['name'])
+    name = scheduler_cfg['name']
+    if name == 'plateau':
+        return torch.optim.lr_scheduler.ReduceLROnPlateau(optimizer, mode='min', patience=scheduler_cfg['patience'],
+                                                          factor=scheduler_cfg['factor'], min_lr=scheduler_cfg['min_lr'])
+    if name == 'sgdr':
+        return WarmRestart(optimizer)
+    if name == 'linear':
+        return LinearDecay(optimizer, min_lr=scheduler_cfg['min_lr'], max_epoch=total_epochs,
+                           start_epoch=scheduler_cfg['start_epoch'], last_epoch=last_epoch)
+    raise ValueError("Scheduler [%s] not recognized." % name)
+
+
+def ckpt_state(model=None, optimizer=None, epoch=None, rep_s=0.):
+    """What the reference's train.py saves per checkpoint: ``epoch``, ``model_state``, ``optimizer_state`` (None without a model /
+    an optimizer) and ``repeatability``."""
+    return {'epoch': epoch, 'model_state': None if model is None else model.state_dict(),
+            'optimizer_state': None if optimizer is None else optimizer.state_dict(), 'repeatability': rep_s}

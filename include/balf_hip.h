@@ -743,6 +743,31 @@ int balf_linrelu_train_backward(const float *g_dev, const float *y_dev, const fl
                                 float *dw_dev, float *db_dev, float *dx_dev, void *workspace_dev, size_t workspace_bytes,
                                 void *stream);
 
+/* ---- the optimiser step over many tensors in one launch ---------------------------------------------------------
+ * balf_adam_step: one step of torch.optim.Adam (amsgrad=False, maximize=False, L2 weight decay) on n float32 tensors.  p, g, m, v
+ * and numel are HOST arrays of n entries; the pointers in them are device pointers (parameter, gradient, exp_avg, exp_avg_sq of
+ * numel[i] elements).  The library copies them by value into the kernel's argument block (the multi-tensor-apply scheme, 2.8 KB at
+ * n = 64): no device table, no upload, no workspace, ONE launch for all n tensors.  Workgroup b finds its tensor from per-tensor
+ * first-chunk prefixes in the same block (uniform per workgroup) and handles balf_optim_chunk_elems() elements of it, with 16-byte
+ * accesses where all of that tensor's pointers are 16-byte aligned, 4-byte accesses otherwise and for the tail.  Both paths run the
+ * same operations in the same order: an element's result bits do not depend on alignment or on how the data is cut into tensors.
+ *   g' = fma(wd, p, g) (wd != 0; else g)     m' = fma(1 - b1, g', b1 m)     v' = fma(1 - b2, g' g', b2 v)
+ *   p' = p - ((lr / bc1) m') / (sqrt(v') / sqrt(bc2) + eps),   bc1 = 1 - b1^step, bc2 = 1 - b2^step
+ * b1, 1 - b1, b2, 1 - b2, wd, eps, lr / bc1 and sqrt(bc2) are computed on the host in double and passed as float; everything per
+ * element is float32, every operation written here rounded once (the three FMAs are the only fused ones), division and square
+ * root correctly rounded.  NaN and Inf in g reach that element alone.  step: the number of THIS step, 1 for the first.
+ * balf_sgd_step: p' = p - lr g.
+ * g[i] == NULL or numel[i] == 0 skips tensor i: its p, m and v keep their bits.  A call in which every tensor is skipped launches
+ * nothing and returns BALF_OK.  g is only read.  Tensors must not overlap one another.
+ * BALF_ERR_ARG: n outside 1..BALF_OPTIM_MAX_TENSORS, a NULL array, a NULL p, m or v entry with numel > 0, a pointer that is not
+ * 4-byte aligned, a negative numel, lr, eps or weight_decay negative or not finite, a beta outside [0, 1), step < 1.
+ * BALF_ERR_SHAPE: more than 2^31 - 1 chunks in all.  Stream-ordered, nothing synchronised, allocated or read back, capturable. */
+#define BALF_OPTIM_MAX_TENSORS 64
+int balf_optim_chunk_elems(void);            /* elements one workgroup handles; a constant of the build */
+int balf_adam_step(int n, float *const *p, const float *const *g, float *const *m, float *const *v, const int64_t *numel,
+                   double lr, double beta1, double beta2, double eps, double weight_decay, int64_t step, void *stream);
+int balf_sgd_step(int n, float *const *p, const float *const *g, const int64_t *numel, double lr, void *stream);
+
 /* ---- measurement aid (not part of the data path) ---------------------------------------------
  * Between balf_profile_begin() and balf_profile_end() every kernel launch of the library is bracketed
  * by a hipEvent pair on its launch stream.  balf_profile_end() waits for those events and returns,
