@@ -12,8 +12,15 @@ synchronises.
 The kernel takes a few microseconds; what a step costs is the host's walk over the parameters.  So each group keeps
 a plan: its parameters' state dictionaries, the pointers gathered by ``ops.optim_pointers`` (gathered again when a ``data_ptr`` of
 a parameter or a moment has changed), and -- FusedAdam -- one CPU tensor whose elements ARE the ``step`` scalars of the group (each
-``state[p]['step']`` is a 0-d view of it), so that reading every step count is one ``tolist()`` and advancing them one ``add_``."""
+``state[p]['step']`` is a 0-d view of it), so that reading every step count is one ``tolist()`` and advancing them one ``add_``.
+When a plan is dropped is listed at ``_FusedOptimizer._plan``.
+
+``step()`` cannot be captured into a graph: the step number, ``lr``, ``lr / bc1`` and ``sqrt(bc2)`` are launch arguments, passed by
+value, so a replay would repeat the captured step's bias corrections and learning rate.  Under a capture it raises RuntimeError
+before anything is launched (as ``torch.optim.Adam(capturable=False)`` does)."""
 from __future__ import annotations
+
+import operator
 
 import torch
 
@@ -21,6 +28,9 @@ from . import _lib, ops
 
 _RUN = _lib.OPTIM_MAX_TENSORS
 _data_ptr = torch.Tensor.data_ptr
+_is = operator.is_
+_cuda_ready = torch.cuda.is_initialized                                  # (False on a host without a GPU: nothing is asked of one)
+_capturing = getattr(torch._C, "_cuda_isCurrentStreamCapturing", torch.cuda.is_current_stream_capturing)
 
 
 def _round4(n: int) -> int:
@@ -33,8 +43,9 @@ class _Run:
 
 
 class _Plan:
-    """What a group keeps between steps.  ``params`` is the group's own list (a new list, or a new length, makes a new plan)."""
-    __slots__ = ("params", "n", "steps", "runs", "state", "state_len", "fresh")
+    """What a group keeps between steps.  ``params`` is the group's own list (a new list, or a new length, makes a new plan),
+    ``members`` the parameters that were in it when the plan was made (another one in a position makes a new plan too)."""
+    __slots__ = ("params", "members", "n", "steps", "runs", "state", "state_len", "fresh")
 
 
 class _FusedOptimizer(torch.optim.Optimizer):
@@ -82,13 +93,26 @@ class _FusedOptimizer(torch.optim.Optimizer):
                              "after backward, and step() would keep it alive)")
         return loss
 
-    def _plan(self, gi: int, group) -> _Plan:
+    def _refuse_capture(self) -> None:
+        """What ``step()`` does first when the current stream is capturing (``_cuda_ready() and _capturing()``, inline)."""
+        raise RuntimeError(f"{type(self).__name__}.step() cannot be captured into a graph: the step number and lr (lr / bc1, "
+                           "sqrt(bc2)) are launch arguments passed by value, so a replay would repeat this step's bias "
+                           "corrections and learning rate; call step() outside the capture")
+
+    def _plan(self, gi: int, group, entries: int) -> _Plan:
+        """The group's plan, made anew when one of these changed since the last step: the group's list object; its length; the
+        identity of a parameter in any position (``group['params'][i] = new_p``, two entries swapped); the optimiser's ``state``
+        object; the number of its entries (a state that was cleared, popped from or replaced behind our back).  ``entries`` is
+        that number as it was when ``step()`` began, the same for every group: the first step of a parameter adds an entry, and
+        one popped since the last step and one added by an earlier group of this step would cancel.  A new plan reads the step
+        counts from the state, gives a parameter without state torch's state at step 0 at its first gradient, and leaves the
+        state of a parameter that is no longer in the group alone, as torch does."""
         params = group["params"]
         plan = self._plans.get(gi)
         if (plan is None or plan.params is not params or plan.n != len(params) or plan.state is not self.state
-                or plan.state_len != len(self.state)):                  # (a state that was cleared or replaced behind our back)
+                or plan.state_len != entries or not all(map(_is, params, plan.members))):
             plan = self._plans[gi] = _Plan()
-            plan.params, plan.n, plan.runs = params, len(params), {}
+            plan.params, plan.members, plan.n, plan.runs = params, tuple(params), len(params), {}
             plan.state, plan.state_len = self.state, len(self.state)
             plan.steps, plan.fresh = None, set()
             self._new_plan(plan)
@@ -111,7 +135,7 @@ class _FusedOptimizer(torch.optim.Optimizer):
             run = plan.runs[idx] = _Run()
             run.whole = idx is None
             run.idx = tuple(range(plan.n)) if idx is None else idx
-            run.params = [plan.params[i] for i in run.idx]
+            run.params = [plan.members[i] for i in run.idx]
             run.states = [self.state[p] for p in run.params] if plan.steps is not None else None
             run.pointers = None
             run.at = None
@@ -215,10 +239,13 @@ class FusedAdam(_FusedOptimizer):
 
     @torch.no_grad()
     def step(self, closure=None):
+        if _cuda_ready() and _capturing():
+            self._refuse_capture()
         loss = self._closure_loss(closure)
+        entries = len(self.state)
         for gi, group in enumerate(self.param_groups):
             self._check_flags(group)
-            plan = self._plan(gi, group)
+            plan = self._plan(gi, group, entries)
             grads = [p.grad for p in plan.params]
             idx = None                                              # None: every parameter has a gradient
             for g in grads:                                         # (`None in grads` would compare tensors with ==)
@@ -272,10 +299,13 @@ class FusedSGD(_FusedOptimizer):
 
     @torch.no_grad()
     def step(self, closure=None):
+        if _cuda_ready() and _capturing():
+            self._refuse_capture()
         loss = self._closure_loss(closure)
+        entries = len(self.state)
         for gi, group in enumerate(self.param_groups):
             self._check_flags(group)
-            plan = self._plan(gi, group)
+            plan = self._plan(gi, group, entries)
             grads = [p.grad for p in plan.params]
             idx = tuple(i for i, g in enumerate(grads) if g is not None)
             for at in range(0, len(idx), _RUN):

@@ -1,7 +1,9 @@
-"""What tests/test_optim_host.py and tests/test_optim_gpu.py share: one Adam / SGD step restated in float64 with the error bounds of
-DESIGN.md 7s, the seeded inputs those bounds were checked on, a float32 NumPy restatement of the kernel's arithmetic with three
-deliberately wrong variants (so that the gate is shown to fail without a GPU), and the driver that records a scheduler's lr
-sequence (tests/golden/make_scheduler_golden.py runs it on the reference's classes, the host test on this package's).
+"""What tests/test_optim_host.py, tests/test_optim_gpu.py and the two tests/test_optim_life_*.py share: one Adam / SGD step restated
+in float64 with the error bounds of DESIGN.md 7s, the seeded inputs those bounds were checked on, a float32 NumPy restatement of the
+kernel's arithmetic with three deliberately wrong variants (so that the gate is shown to fail without a GPU), the driver that
+records a scheduler's lr sequence (tests/golden/make_scheduler_golden.py runs it on the reference's classes, the host test on this
+package's), and what drives an optimiser object step by step under those bounds on a device given by the caller (five_params ..
+gate_step).
 
 THE BOUNDS count roundings; u = 2^-24.  From the float32 inputs, in float64:
     G = |g| + wd |p|      A = b1 |m| + (1 - b1) G      D = sqrt(v') / sqrt(bc2) + eps      U = (lr / bc1) |m'| / D
@@ -163,3 +165,184 @@ def lr_sequence(classes, name):
         opt.step()
         sched.step()
     return seq
+
+
+# ---- an optimiser object, step by step, on the device the caller names -------------------------------------------------------------------
+CHUNK = 2048                                 # balf_optim_chunk_elems(), for the callers that run without the library
+
+
+def five_params(device, seed=11, chunk=CHUNK):
+    g = torch.Generator().manual_seed(seed)
+    shapes = ((1,), (65,), (256, 65), (chunk + 1,), (3,))
+    return [torch.nn.Parameter((0.1 * torch.randn(s, generator=g)).to(device)) for s in shapes]
+
+
+def groups_of(params):
+    return [{"params": params[:3], "lr": 1e-3, "weight_decay": 0.0}, {"params": params[3:], "lr": 3e-3, "weight_decay": 0.01}]
+
+
+def fresh_grads(params, seed, device):
+    g = torch.Generator().manual_seed(seed)
+    return [(torch.randn(p.shape, generator=g) * float(10.0 ** torch.empty(1).uniform_(-3, 0, generator=g))).to(device) for p in params]
+
+
+def snapshot(opt):
+    """(p, m, v, steps done) per parameter from the optimiser's own float32 state (zeros before the first step)."""
+    out = []
+    for grp in opt.param_groups:
+        for p in grp["params"]:
+            st = opt.state.get(p, {})
+            zeros = np.zeros(p.numel(), np.float32)
+            out.append((p.detach().cpu().numpy().reshape(-1).copy(),
+                        st["exp_avg"].cpu().numpy().reshape(-1).copy() if "exp_avg" in st else zeros,
+                        st["exp_avg_sq"].cpu().numpy().reshape(-1).copy() if "exp_avg_sq" in st else zeros,
+                        int(st["step"]) if "step" in st else 0))
+    return out
+
+
+def gate_step(what, opt, before, grads):
+    """Every tensor of ``opt`` after a step is within the one-step bounds of the float64 step from ``before``.  (The state is read
+    with ``get``: looking must not add an entry to the optimiser's state, whose length the fused classes watch.)"""
+    i = 0
+    for grp in opt.param_groups:
+        for p in grp["params"]:
+            p0, m0, v0, done = before[i]
+            g = grads[i]
+            st = opt.state.get(p, {})
+            if g is None:
+                assert bits_equal(p.detach().reshape(-1), torch.from_numpy(p0).to(p.device)) and int(st.get("step", 0)) == done, (what, i)
+            else:
+                assert int(st["step"]) == done + 1 and st["step"].device.type == "cpu" and st["step"].dtype == torch.float32
+                ref = adam64(p0, g.cpu().numpy().reshape(-1), m0, v0, step=done + 1, wd=grp["weight_decay"], lr=grp["lr"],
+                             b1=grp["betas"][0], b2=grp["betas"][1], eps=grp["eps"])
+                check_adam(f"{what} tensor {i}", p.detach(), st["exp_avg"], st["exp_avg_sq"], ref)
+            i += 1
+
+
+def gate_sgd_step(what, opt, before, grads):
+    """The same for ``p -= lr * g``: every parameter within the SGD bound of the float64 step from ``before``, or its bits kept."""
+    i = 0
+    for grp in opt.param_groups:
+        for p in grp["params"]:
+            p0, g = before[i][0], grads[i]
+            if g is None:
+                assert bits_equal(p.detach().reshape(-1), torch.from_numpy(p0).to(p.device)), (what, i)
+            else:
+                ref = sgd64(p0, g.cpu().numpy().reshape(-1), grp["lr"])
+                assert excess(p.detach(), ref["p"], ref["bp"]) <= 1.0, (what, i)
+            i += 1
+
+
+def set_grads(opt, grads):
+    i = 0
+    for grp in opt.param_groups:
+        for p in grp["params"]:
+            p.grad = None if grads[i] is None else grads[i].clone()
+            i += 1
+
+
+# ---- the fused classes against two oracles, on the device the caller names ----------------------------------------------------------------
+def flat(opt):
+    return [p for grp in opt.param_groups for p in grp["params"]]
+
+
+def new_param(shape, seed, device):
+    return torch.nn.Parameter((0.1 * torch.randn(shape, generator=torch.Generator().manual_seed(seed))).to(device))
+
+
+def five_groups(kind, device, chunk=CHUNK):
+    """-> a function that makes the two groups of ``groups_of`` on fresh, equal parameters (one of them of c + 1 elements)."""
+    def make():
+        params = five_params(device, chunk=chunk)
+        assert params[3].numel() == chunk + 1
+        if kind == "adam":
+            return groups_of(params)
+        return [{"params": params[:3], "lr": 1e-2}, {"params": params[3:], "lr": 3e-2}]
+    return make
+
+
+def seventy(kind, device, chunk=CHUNK):
+    """-> a function that makes ONE group of 70 parameters of 1 .. 40 elements, two of them of c + 1: two launches, 64 + 6."""
+    def make():
+        sizes = [chunk + 1 if i in (5, 66) else i * 7 % 40 + 1 for i in range(70)]
+        grp = {"params": [new_param((n,), 100 + i, device) for i, n in enumerate(sizes)], "lr": 1e-3}
+        return [dict(grp, weight_decay=0.01) if kind == "adam" else grp]
+    return make
+
+
+class Trio:
+    """The instance under test (``fused``), its plan-free twin (``free``) and torch's optimiser (``torch``) on equal tensors, stepped
+    together and judged after every step:
+    (a) the twin, whose ``_plans`` is emptied before every ``step()`` -- no cache, so nothing stale -- has the same bits in every
+        parameter and moment and the same step counts;
+    (b) ``torch.optim.Adam(foreach=False)`` / ``torch.optim.SGD`` under the same mutation passes the one-step float64 gate above (so
+        do the fused instances), has the same step counts and the same parameters with state, and its parameters agree with the
+        fused ones within rtol 1e-5 / atol 1e-7: both are float32 Adam, one step differs by ~1e-6 of an update of at most 3e-3,
+        which is ~3e-9 per step over the at most 70 steps taken by any caller.
+    ``kernel``: an object whose ``opt`` is set to the optimiser about to step and whose ``calls`` collects the sizes of its launches."""
+    NAMES = ("fused", "plan-free", "torch")
+
+    def __init__(self, kernel, kind, device, make=None, opts=None):
+        from balf_amd.optim import FusedAdam, FusedSGD
+        self.kernel, self.kind, self.device, self.k = kernel, kind, device, 0
+        make = make or five_groups(kind, device)
+        if opts is None:
+            cls, theirs = (FusedAdam, torch.optim.Adam) if kind == "adam" else (FusedSGD, torch.optim.SGD)
+            opts = (cls(make()), cls(make()), theirs(make(), foreach=False))
+        self.opts = tuple(opts)
+        self.fused, self.free, self.torch = self.opts
+        self.calls = {}
+
+    def each(self, f):
+        return [f(opt) for opt in self.opts]
+
+    def step(self, none=()):
+        """One step of all three on the same gradients (``none``: the flat positions without one), gated and compared."""
+        self.k += 1
+        grads = fresh_grads(flat(self.fused), 1000 + self.k, self.device)
+        for i in none:
+            grads[i] = None
+        gate = gate_step if self.kind == "adam" else gate_sgd_step
+        for name, opt in zip(self.NAMES, self.opts):
+            before = snapshot(opt)
+            set_grads(opt, grads)
+            if opt is self.free:
+                opt._plans = {}
+            self.kernel.opt, self.kernel.calls = opt, []
+            opt.step()
+            self.calls[name] = self.kernel.calls
+            gate(f"{name} step {self.k}", opt, before, grads)
+        self.compare()
+
+    def steps(self, n, none=()):
+        for _ in range(n):
+            self.step(none)
+
+    def counts(self, opt=None):
+        opt = opt or self.fused
+        return [float(opt.state[p]["step"]) if opt.state.get(p) else None for p in flat(opt)]
+
+    def compare(self):
+        a, b, t = (flat(opt) for opt in self.opts)
+        assert len(a) == len(b) == len(t)
+        for i, (p, q, r) in enumerate(zip(a, b, t)):
+            assert bits_equal(p.detach(), q.detach()), (i, "the plan-free twin's parameter differs")
+            sp, sq, sr = self.fused.state.get(p, {}), self.free.state.get(q, {}), self.torch.state.get(r, {})
+            assert set(sp) == set(sq) == set(sr), (i, set(sp), set(sq), set(sr))
+            for key in sp:
+                if key == "step":
+                    assert float(sp[key]) == float(sq[key]) == float(sr[key]), (i, float(sp[key]), float(sq[key]), float(sr[key]))
+                else:
+                    assert sp[key].shape == p.shape and bits_equal(sp[key], sq[key]), (i, key)
+            torch.testing.assert_close(p.detach(), r.detach(), rtol=1e-5, atol=1e-7, msg=lambda m: f"parameter {i} against torch: {m}")
+        entries = [sum(1 for v in opt.state.values() if v) for opt in self.opts]      # (those of parameters that left a list too)
+        assert entries[0] == entries[1] == entries[2], entries
+
+
+def life(kernel, kind, device, mutate, before=3, after=3, none_before=(), none_after=()):
+    """``before`` steps, ``mutate(opt)`` on each of the three, ``after`` steps -> (the trio, what mutate returned per optimiser)."""
+    trio = Trio(kernel, kind, device)
+    trio.steps(before, none_before)
+    out = trio.each(mutate)
+    trio.steps(after, none_after)
+    return trio, out

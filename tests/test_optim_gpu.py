@@ -200,59 +200,14 @@ def test_nan_and_inf_gradients():
 
 # ---- 6. the optimiser classes over several steps ----------------------------------------------------------------------------------------
 def five_params(seed=11):
-    c = chunk()
-    g = torch.Generator().manual_seed(seed)
-    shapes = ((1,), (65,), (256, 65), (c + 1,), (3,))
-    return [torch.nn.Parameter((0.1 * torch.randn(s, generator=g)).to(DEV)) for s in shapes]
-
-
-def groups_of(params):
-    return [{"params": params[:3], "lr": 1e-3, "weight_decay": 0.0}, {"params": params[3:], "lr": 3e-3, "weight_decay": 0.01}]
+    return OC.five_params(DEV, seed, chunk())
 
 
 def fresh_grads(params, seed):
-    g = torch.Generator().manual_seed(seed)
-    return [(torch.randn(p.shape, generator=g) * float(10.0 ** torch.empty(1).uniform_(-3, 0, generator=g))).to(DEV) for p in params]
+    return OC.fresh_grads(params, seed, DEV)
 
 
-def snapshot(opt):
-    """(p, m, v, steps done) per parameter from the optimiser's own float32 state (zeros before the first step)."""
-    out = []
-    for grp in opt.param_groups:
-        for p in grp["params"]:
-            st = opt.state.get(p, {})
-            zeros = np.zeros(p.numel(), np.float32)
-            out.append((p.detach().cpu().numpy().reshape(-1).copy(),
-                        st["exp_avg"].cpu().numpy().reshape(-1).copy() if "exp_avg" in st else zeros,
-                        st["exp_avg_sq"].cpu().numpy().reshape(-1).copy() if "exp_avg_sq" in st else zeros,
-                        int(st["step"]) if "step" in st else 0))
-    return out
-
-
-def gate_step(what, opt, before, grads):
-    """Every tensor of ``opt`` after a step is within the one-step bounds of the float64 step from ``before``."""
-    i = 0
-    for grp in opt.param_groups:
-        for p in grp["params"]:
-            p0, m0, v0, done = before[i]
-            g = grads[i]
-            st = opt.state[p]
-            if g is None:
-                assert bits_equal(p.detach().reshape(-1), torch.from_numpy(p0).to(p.device)) and int(st.get("step", 0)) == done, (what, i)
-            else:
-                assert int(st["step"]) == done + 1 and st["step"].device.type == "cpu" and st["step"].dtype == torch.float32
-                ref = OC.adam64(p0, g.cpu().numpy().reshape(-1), m0, v0, step=done + 1, wd=grp["weight_decay"], lr=grp["lr"],
-                                b1=grp["betas"][0], b2=grp["betas"][1], eps=grp["eps"])
-                OC.check_adam(f"{what} tensor {i}", p.detach(), st["exp_avg"], st["exp_avg_sq"], ref)
-            i += 1
-
-
-def set_grads(opt, grads):
-    i = 0
-    for grp in opt.param_groups:
-        for p in grp["params"]:
-            p.grad = None if grads[i] is None else grads[i].clone()
-            i += 1
+groups_of, snapshot, gate_step, set_grads = OC.groups_of, OC.snapshot, OC.gate_step, OC.set_grads
 
 
 def test_fused_adam_six_steps_and_torch_under_the_same_gate():
