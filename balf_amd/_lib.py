@@ -187,6 +187,56 @@ def current_stream_ptr(device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
 
+# ---- the one door into the library ---------------------------------------------------------------------------
+def raw_stream(index: int) -> int:
+    """The current stream of device ``index`` as the pointer the library takes: torch's direct accessor where this build has
+    it (a tenth of the cost of making a ``torch.cuda.Stream`` object, which shows in a 37 us step), else through that object."""
+    import torch
+    get = getattr(torch._C, "_cuda_getCurrentRawStream", None)
+    return get(index) if get is not None else torch.cuda.current_stream(index).cuda_stream
+
+
+def on_device(dev, call):
+    """The low layer: ``call(stream)`` with ``dev`` (a ``torch.device`` or a device index) current and ``stream`` its current
+    stream -> what ``call`` returns.  Without the context manager when the device already is current (the common case).  For
+    a caller that keeps its C arguments across calls, as the optimiser step does; everything else goes through launch()."""
+    import torch
+    index = dev if isinstance(dev, int) else dev.index
+    current = torch.cuda.current_device()
+    if index is None or index == current:
+        return call(raw_stream(current))
+    with torch.cuda.device(index):
+        return call(raw_stream(index))
+
+
+class Workspace:
+    """Marks a scratch tensor among launch()'s arguments: the library takes it as two, its pointer and its byte count."""
+    __slots__ = ("tensor",)
+
+    def __init__(self, tensor):
+        self.tensor = tensor
+
+
+def launch(name: str, dev, *args, what=None) -> None:
+    """The high layer: entry ``name`` of the library on the current stream of ``dev``, with ``dev`` current (on_device).  Of
+    ``args``, a tensor goes as its ``data_ptr()``, None as NULL, a :class:`Workspace` as pointer and byte count; everything
+    else -- numbers, ctypes arrays, host pointers -- goes as it is, and the stream is appended last.  A failure is reported
+    under ``what or name`` (check).  The tensors are arguments of this call, so they live until the work is enqueued."""
+    import torch
+    fn = getattr(lib(), name, None)
+    if fn is None:
+        raise BalfHipError(f"{name} is not an entry of libbalf_hip.so")
+    c_args = []
+    for a in args:
+        if isinstance(a, torch.Tensor):
+            c_args.append(a.data_ptr())
+        elif isinstance(a, Workspace):
+            c_args += (a.tensor.data_ptr(), a.tensor.nbytes)
+        else:
+            c_args.append(a)
+    check(on_device(dev, lambda stream: fn(*c_args, stream)), what or name)
+
+
 def tensor_key(t):
     """(storage address, version) of a parameter/buffer, for the packed-weight caches.  Inference tensors
     (a model moved under torch.inference_mode()) do not track versions and cannot be modified in place."""

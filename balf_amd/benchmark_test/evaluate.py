@@ -21,7 +21,7 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
-from .._lib import BalfHipError, check, current_stream_ptr, lib, require_gpu_tensor
+from .._lib import BalfHipError, launch, require_gpu_tensor
 from . import _chunked
 from ._chunked import detection_rows  # noqa: F401
 from .metrics_results import create_metrics_results
@@ -70,8 +70,8 @@ class CommonPointsIndex(NamedTuple):
 
 
 def _common_points_args(src_pts, src_count, dst_pts, dst_count, h_dst_2_src, shapes):
-    """The checked inputs and the four outputs both filter calls share -> (the outputs as a CommonPoints, the leading C
-    arguments up to valid_dev)."""
+    """The checked inputs and the four outputs both filter calls share -> (the outputs as a CommonPoints, the leading
+    arguments of launch() up to valid_dev)."""
     for t, name in ((src_pts, "src_pts"), (dst_pts, "dst_pts")):
         require_gpu_tensor(t, name)
         if t.dtype != torch.float64 or t.dim() != 3 or t.shape[2] != 4:
@@ -86,11 +86,7 @@ def _common_points_args(src_pts, src_count, dst_pts, dst_count, h_dst_2_src, sha
     sh = _pair_tensor(shapes, dev, "shapes", ((p, 4),), torch.int32)
     out = CommonPoints(torch.empty_like(src_pts), torch.empty_like(dst_pts),
                        torch.empty((p, 2), dtype=torch.int32, device=dev), torch.empty((p,), dtype=torch.int32, device=dev))
-    # (ns, nd, h, sh may be fresh conversions: the tuple keeps them alive until the launch is enqueued)
-    keep = (ns, nd, h, sh)
-    args = (src_pts.data_ptr(), ns.data_ptr(), ns_max, dst_pts.data_ptr(), nd.data_ptr(), nd_max, p, h.data_ptr(), sh.data_ptr(),
-            out.src.data_ptr(), out.dst_to_src.data_ptr(), out.kept.data_ptr(), out.valid.data_ptr())
-    return out, args, keep
+    return out, (src_pts, ns, ns_max, dst_pts, nd, nd_max, p, h, sh, *out)
 
 
 def common_points_batch(src_pts, src_count, dst_pts, dst_count, h_dst_2_src, shapes) -> CommonPoints:
@@ -98,10 +94,8 @@ def common_points_batch(src_pts, src_count, dst_pts, dst_count, h_dst_2_src, sha
     the kept destination rows (``balf_common_points_batch``, include/balf_hip.h).  ``src_pts`` [P,Ns,4] / ``dst_pts``
     [P,Nd,4] float64 rows (x, y, radius, score) with counts ``src_count`` / ``dst_count`` [P] int32, ``h_dst_2_src``
     [P,3,3] float64, ``shapes`` [P,4] int32 = (h_src, w_src, h_dst, w_dst), all on the GPU."""
-    out, args, _keep = _common_points_args(src_pts, src_count, dst_pts, dst_count, h_dst_2_src, shapes)
-    dev = src_pts.device
-    with torch.cuda.device(dev):
-        check(lib().balf_common_points_batch(*args, current_stream_ptr(dev)), "balf_common_points_batch")
+    out, args = _common_points_args(src_pts, src_count, dst_pts, dst_count, h_dst_2_src, shapes)
+    launch("balf_common_points_batch", src_pts.device, *args)
     return out
 
 
@@ -110,13 +104,11 @@ def common_points_index_batch(src_pts, src_count, dst_pts, dst_count, h_dst_2_sr
     ``dst_index`` [P,Nd] int32: the original row of each kept row in kept order, -1 past the kept count
     (``balf_common_points_index_batch``).  Whatever was computed per detected row -- a descriptor -- follows its row into
     the kept list through them."""
-    out, args, _keep = _common_points_args(src_pts, src_count, dst_pts, dst_count, h_dst_2_src, shapes)
+    out, args = _common_points_args(src_pts, src_count, dst_pts, dst_count, h_dst_2_src, shapes)
     dev = src_pts.device
     src_index = torch.empty(src_pts.shape[:2], dtype=torch.int32, device=dev)
     dst_index = torch.empty(dst_pts.shape[:2], dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        check(lib().balf_common_points_index_batch(*args, src_index.data_ptr(), dst_index.data_ptr(), current_stream_ptr(dev)),
-              "balf_common_points_index_batch")
+    launch("balf_common_points_index_batch", dev, *args, src_index, dst_index)
     return CommonPointsIndex(*out, src_index, dst_index)
 
 
@@ -210,10 +202,8 @@ def match_accuracy_batch(src, dst, kept, match_idx, match_count, thresholds):
     correct = torch.empty((p, len(ths)), dtype=torch.int32, device=dev)
     if cap == 0:
         return err, correct.zero_()
-    with torch.cuda.device(dev):
-        check(lib().balf_match_accuracy_batch(src.data_ptr(), src.shape[1], dst.data_ptr(), dst.shape[1], kept.data_ptr(),
-                                              match_idx.data_ptr(), count.data_ptr(), cap, p, th_arr, len(ths), err.data_ptr(),
-                                              correct.data_ptr(), current_stream_ptr(dev)), "balf_match_accuracy_batch")
+    launch("balf_match_accuracy_batch", dev, src, src.shape[1], dst, dst.shape[1], kept, match_idx, count, cap, p, th_arr, len(ths),
+           err, correct)
     return err, correct
 
 

@@ -6,7 +6,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .._lib import check, current_stream_ptr, lib
+from .._lib import launch
 from .repeatability_tools import _device
 
 
@@ -20,9 +20,7 @@ def apply_homography_to_points(points, h):
     p = torch.from_numpy(np.ascontiguousarray(pts[:, :4])).to(dev)
     hm = torch.from_numpy(np.ascontiguousarray(np.asarray(h, dtype=np.float64).reshape(9))).to(dev)
     out = torch.empty_like(p)
-    with torch.cuda.device(dev):
-        check(lib().balf_apply_homography(p.data_ptr(), len(pts), hm.data_ptr(), out.data_ptr(), current_stream_ptr(dev)),
-              "balf_apply_homography")
+    launch("balf_apply_homography", dev, p, len(pts), hm, out)
     return out.cpu().numpy()
 
 
@@ -37,7 +35,5 @@ def create_common_region_masks(h_dst_2_src, shape_src, shape_dst):
     dev = _device()
     ms = torch.empty((hs, ws), dtype=torch.float64, device=dev)
     md = torch.empty((hd, wd), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        check(lib().balf_common_region_masks(hm.ctypes.data_as(C.c_void_p), hs, ws, hd, wd, 15, ms.data_ptr(), md.data_ptr(),
-                                             current_stream_ptr(dev)), "balf_common_region_masks")
+    launch("balf_common_region_masks", dev, hm.ctypes.data_as(C.c_void_p), hs, ws, hd, wd, 15, ms, md)
     return ms.cpu().numpy(), md.cpu().numpy()

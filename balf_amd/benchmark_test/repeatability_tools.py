@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from .._lib import BalfHipError, check, current_stream_ptr, lib, require_gpu_tensor
+from .._lib import BalfHipError, Workspace, launch, lib, require_gpu_tensor
 
 MAX_EDGES = 1 << 22
 
@@ -47,11 +47,8 @@ def compute_repeatability(src_indexes, dst_indexes, overlap_err=0.4, eps=1e-6, d
         cm = torch.empty((points, 2), dtype=torch.int32, device=dev)
         cap = int(min(ns * nd, MAX_EDGES))
         ws = ops._workspace("repeat", dev, lib().balf_repeatability_workspace_bytes(ns, nd, cap))
-        with torch.cuda.device(dev):
-            check(lib().balf_repeatability(s.data_ptr(), ns, d.data_ptr(), nd, float(overlap_err), float(eps),
-                                           float(dist_match_thresh), float(radious_size), cap, counts.data_ptr(),
-                                           errors.data_ptr(), cs.data_ptr(), cm.data_ptr(), ws.data_ptr(), ws.numel(),
-                                           current_stream_ptr(dev)), "balf_repeatability")
+        launch("balf_repeatability", dev, s, ns, d, nd, float(overlap_err), float(eps), float(dist_match_thresh),
+               float(radious_size), cap, counts, errors, cs, cm, Workspace(ws))
         c = counts.cpu().numpy()
         e = errors.cpu().numpy()
         if c[0] < 0 or c[1] < 0:            # the candidate list of a scale did not fit max_edges (reported by the device)
@@ -116,17 +113,12 @@ def compute_repeatability_batch(src, ns, dst, nd, overlap_err=0.4, eps=1e-6, dis
         max_edges = max(1, min(p * ns_max * nd_max, MAX_EDGES))
     rep = torch.empty((p, 4), dtype=torch.float64, device=dev)
     cnt = torch.empty((p, 6), dtype=torch.int32, device=dev)
-    l = lib()
-    nbytes = l.balf_repeatability_batch_workspace_bytes(p, ns_max, nd_max, int(max_edges))
+    nbytes = lib().balf_repeatability_batch_workspace_bytes(p, ns_max, nd_max, int(max_edges))
     if nbytes == 0:
         raise BalfHipError(f"balf_repeatability_batch: unsupported sizes P={p}, Ns={ns_max}, Nd={nd_max}, max_edges={max_edges}")
     ws = ops._workspace("repeat_batch", dev, nbytes)
-    with torch.cuda.device(dev):
-        check(l.balf_repeatability_batch(src.data_ptr(), ns.data_ptr(), ns_max, src.shape[2], dst.data_ptr(), nd.data_ptr(),
-                                         nd_max, dst.shape[2], ns.stride(0), p, float(overlap_err), float(eps),
-                                         float(dist_match_thresh), float(radious_size), int(max_edges), rep.data_ptr(),
-                                         cnt.data_ptr(), ws.data_ptr(), ws.numel(), current_stream_ptr(dev)),
-              "balf_repeatability_batch")
+    launch("balf_repeatability_batch", dev, src, ns, ns_max, src.shape[2], dst, nd, nd_max, dst.shape[2], ns.stride(0), p,
+           float(overlap_err), float(eps), float(dist_match_thresh), float(radious_size), int(max_edges), rep, cnt, Workspace(ws))
     return RepeatabilityBatch(rep[:, 0], rep[:, 1], rep[:, 2], rep[:, 3], cnt[:, 0], cnt[:, 1], cnt[:, 2], cnt[:, 3],
                               cnt[:, 4], cnt[:, 5])
 

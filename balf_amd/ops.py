@@ -10,7 +10,7 @@ import torch
 
 from . import _lib
 from .arch import padded_hw
-from ._lib import BalfHipError, check, current_stream_ptr, lib, require_gpu_tensor
+from ._lib import BalfHipError, Workspace, check, launch, lib, on_device, require_gpu_tensor
 
 _workspaces: Dict[Tuple[str, int, int], torch.Tensor] = {}      # insertion order = least recently used first
 _MAX_STREAMS_PER_TAG = 2        # the forward workspace of 8 x 1088x1920 is ~7 GB: a process that keeps creating streams
@@ -51,9 +51,7 @@ def window_nms(score: torch.Tensor, border: int, nms_size: int) -> torch.Tensor:
         raise BalfHipError("score must be a [B,H,W] float32 tensor")
     out = torch.empty_like(score)
     b, h, w = score.shape
-    with torch.cuda.device(score.device):
-        check(lib().balf_window_nms(score.data_ptr(), b, h, w, int(border), int(nms_size), out.data_ptr(),
-                                    current_stream_ptr(score.device)), "balf_window_nms")
+    launch("balf_window_nms", score.device, score, b, h, w, int(border), int(nms_size), out)
     return out
 
 
@@ -75,17 +73,12 @@ def nms_topk(prob: torch.Tensor, crop_y: int, crop_x: int, h: int, w: int, borde
     count = torch.empty((b,), dtype=torch.int32, device=dev)
     nbytes = lib().balf_nms_topk_workspace_bytes(b, h, w, k)
     ws = _workspace("nms", dev, nbytes)
-    with torch.cuda.device(dev):
-        if threshold == -1:
-            check(lib().balf_nms_topk(prob.data_ptr(), b, hp, wp, int(crop_y), int(crop_x), int(h), int(w),
-                                      int(border), int(nms_size), int(k), idx.data_ptr(), score.data_ptr(),
-                                      count.data_ptr(), ws.data_ptr(), ws.numel(), current_stream_ptr(dev)),
-                  "balf_nms_topk")
-        else:
-            check(lib().balf_nms_threshold(prob.data_ptr(), b, hp, wp, int(crop_y), int(crop_x), int(h), int(w),
-                                           int(border), int(nms_size), float(threshold), int(k), idx.data_ptr(),
-                                           score.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel(),
-                                           current_stream_ptr(dev)), "balf_nms_threshold")
+    if threshold == -1:
+        launch("balf_nms_topk", dev, prob, b, hp, wp, int(crop_y), int(crop_x), int(h), int(w), int(border), int(nms_size), int(k),
+               idx, score, count, Workspace(ws))
+    else:
+        launch("balf_nms_threshold", dev, prob, b, hp, wp, int(crop_y), int(crop_x), int(h), int(w), int(border), int(nms_size),
+               float(threshold), int(k), idx, score, count, Workspace(ws))
     return idx, score, count
 
 
@@ -104,12 +97,8 @@ def greedy_nms(prob: torch.Tensor, crop_y: int, crop_x: int, h: int, w: int, bor
     count = torch.empty((b,), dtype=torch.int32, device=dev)
     total = torch.empty((b,), dtype=torch.int32, device=dev)
     ws = _workspace("greedy", dev, lib().balf_greedy_nms_workspace_bytes(b, h, w, k))
-    with torch.cuda.device(dev):
-        check(lib().balf_greedy_nms(prob.data_ptr(), b, hp, wp, int(crop_y), int(crop_x), int(h), int(w), int(border),
-                                    float(conf_thresh), int(dist_thresh), int(k), int(subpixel_patch), idx.data_ptr(),
-                                    score.data_ptr(), xy.data_ptr() if xy is not None else None, count.data_ptr(),
-                                    total.data_ptr(), ws.data_ptr(), ws.numel(), current_stream_ptr(dev)),
-              "balf_greedy_nms")
+    launch("balf_greedy_nms", dev, prob, b, hp, wp, int(crop_y), int(crop_x), int(h), int(w), int(border), float(conf_thresh),
+           int(dist_thresh), int(k), int(subpixel_patch), idx, score, xy, count, total, Workspace(ws))
     return idx, score, xy, count, total
 
 
@@ -147,9 +136,7 @@ def extract_patches(gray_u8: torch.Tensor, xy: torch.Tensor, scale: float) -> to
         return out
     nbytes = lib().balf_extract_patches_workspace_bytes(h, w, float(scale))
     ws = _workspace("patches", dev, nbytes)
-    with torch.cuda.device(dev):
-        check(lib().balf_extract_patches(gray_u8.data_ptr(), h, w, xy.data_ptr(), n, float(scale), out.data_ptr(),
-                                         ws.data_ptr(), ws.numel(), current_stream_ptr(dev)), "balf_extract_patches")
+    launch("balf_extract_patches", dev, gray_u8, h, w, xy, n, float(scale), out, Workspace(ws))
     return out
 
 
@@ -161,9 +148,7 @@ def rgb_to_gray_u8(rgb_u8: torch.Tensor) -> torch.Tensor:
         raise BalfHipError("rgb_u8 must be a uint8 tensor with a last dimension of 3")
     out = torch.empty(rgb_u8.shape[:-1], dtype=torch.uint8, device=rgb_u8.device)
     if out.numel():
-        with torch.cuda.device(rgb_u8.device):
-            check(lib().balf_rgb_to_gray(rgb_u8.data_ptr(), out.numel(), out.data_ptr(), current_stream_ptr(rgb_u8.device)),
-                  "balf_rgb_to_gray")
+        launch("balf_rgb_to_gray", rgb_u8.device, rgb_u8, out.numel(), out)
     return out
 
 
@@ -185,11 +170,7 @@ def extract_patches_batch(gray_u8: torch.Tensor, xy: torch.Tensor, count, scale:
     if count is not None:
         count = count.to(device=dev, dtype=torch.int32).contiguous()
     ws = _workspace("patches", dev, lib().balf_extract_patches_batch_workspace_bytes(b, h, w, float(scale)))
-    with torch.cuda.device(dev):
-        check(lib().balf_extract_patches_batch(gray_u8.data_ptr(), b, h, w, xy.data_ptr(),
-                                               count.data_ptr() if count is not None else None, k, float(scale),
-                                               out.data_ptr(), ws.data_ptr(), ws.numel(), current_stream_ptr(dev)),
-              "balf_extract_patches_batch")
+    launch("balf_extract_patches_batch", dev, gray_u8, b, h, w, xy, count, k, float(scale), out, Workspace(ws))
     return out
 
 
@@ -210,10 +191,7 @@ def match_smnn(desc1: torch.Tensor, desc2: torch.Tensor, th: float = 0.8) -> Tup
     dist = torch.empty((cap,), dtype=torch.float32, device=dev)
     count = torch.empty((1,), dtype=torch.int32, device=dev)
     ws = _workspace("match", dev, lib().balf_match_smnn_workspace_bytes(n1, n2))
-    with torch.cuda.device(dev):
-        check(lib().balf_match_smnn(desc1.data_ptr(), n1, desc2.data_ptr(), n2, float(th), idx.data_ptr(),
-                                    dist.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel(),
-                                    current_stream_ptr(dev)), "balf_match_smnn")
+    launch("balf_match_smnn", dev, desc1, n1, desc2, n2, float(th), idx, dist, count, Workspace(ws))
     m = int(count.item())
     return dist[:m].view(-1, 1), idx[:m].long()
 
@@ -239,10 +217,7 @@ def match_smnn_batch(desc1: torch.Tensor, n1: torch.Tensor, desc2: torch.Tensor,
     n1 = n1.to(device=dev, dtype=torch.int32).contiguous()
     n2 = n2.to(device=dev, dtype=torch.int32).contiguous()
     ws = _workspace("match", dev, lib().balf_match_smnn_batch_workspace_bytes(p, k1, k2))
-    with torch.cuda.device(dev):
-        check(lib().balf_match_smnn_batch(desc1.data_ptr(), k1, n1.data_ptr(), desc2.data_ptr(), k2, n2.data_ptr(), p,
-                                          float(th), idx.data_ptr(), dist.data_ptr(), count.data_ptr(), ws.data_ptr(),
-                                          ws.numel(), current_stream_ptr(dev)), "balf_match_smnn_batch")
+    launch("balf_match_smnn_batch", dev, desc1, k1, n1, desc2, k2, n2, p, float(th), idx, dist, count, Workspace(ws))
     return dist, idx, count
 
 
@@ -257,10 +232,8 @@ def pyramid_level(src: torch.Tensor, kind: int, channels: int, h_in: int, w_in: 
     hp, wp = padded_hw(h_out, w_out)[:2]
     dev = src.device
     out = torch.empty((b, 3, hp, wp), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        check(lib().balf_pyramid_level(src.data_ptr(), int(kind), int(channels), b, int(h_in), int(w_in), float(sigma),
-                                       int(h_out), int(w_out), out.data_ptr(), current_stream_ptr(dev)),
-              "balf_pyramid_level")
+    launch("balf_pyramid_level", dev, src, int(kind), int(channels), b, int(h_in), int(w_in), float(sigma), int(h_out), int(w_out),
+           out)
     return out
 
 
@@ -314,11 +287,8 @@ def nms_topk_budget(prob: torch.Tensor, crop_y: int, crop_x: int, h: int, w: int
         if t.shape != shape or t.dtype != dt:
             raise BalfHipError(f"output must be {dt} {shape}, got {t.dtype} {tuple(t.shape)}")
     ws = _workspace("nms", dev, lib().balf_nms_topk_workspace_bytes(b, h, w, 1))
-    with torch.cuda.device(dev):
-        check(lib().balf_nms_topk_budget(prob.data_ptr(), b, hp, wp, int(crop_y), int(crop_x), int(h), int(w), int(border),
-                                         int(nms_size), int(cum_budget), int(k_max), taken.data_ptr(), idx.data_ptr(),
-                                         score.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel(),
-                                         current_stream_ptr(dev)), "balf_nms_topk_budget")
+    launch("balf_nms_topk_budget", dev, prob, b, hp, wp, int(crop_y), int(crop_x), int(h), int(w), int(border), int(nms_size),
+           int(cum_budget), int(k_max), taken, idx, score, count, Workspace(ws))
     return idx, score, count
 
 
@@ -342,10 +312,7 @@ def multiscale_merge(idx: torch.Tensor, score: torch.Tensor, count: torch.Tensor
     dev = idx.device
     pts = torch.empty((b, n, 4), dtype=torch.float64, device=dev)
     cnt = torch.empty((b,), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        check(lib().balf_multiscale_merge(idx.data_ptr(), score.data_ptr(), count.data_ptr(), nl, b, k_max, w_host, h_host,
-                                          int(n), int(bool(order_yx)), pts.data_ptr(), cnt.data_ptr(),
-                                          current_stream_ptr(dev)), "balf_multiscale_merge")
+    launch("balf_multiscale_merge", dev, idx, score, count, nl, b, k_max, w_host, h_host, int(n), int(bool(order_yx)), pts, cnt)
     return pts, cnt
 
 
@@ -379,8 +346,7 @@ def val_points(prob_src: torch.Tensor, prob_dst: torch.Tensor, h_dst_2_src: torc
         raise ValueError(f"num_points must be positive, got {num_points}")
     if k > min(hs * ws_, hd * wd):
         raise IndexError(f"index {k - 1} is out of bounds for axis 0 with size {min(hs * ws_, hd * wd)}")
-    l = lib()
-    nbytes = l.balf_val_points_workspace_bytes(p, hs, ws_, hd, wd, VAL_LEGS[leg], int(nms_size), k)
+    nbytes = lib().balf_val_points_workspace_bytes(p, hs, ws_, hd, wd, VAL_LEGS[leg], int(nms_size), k)
     if nbytes == 0:
         raise BalfHipError(f"balf_val_points: unsupported sizes P={p}, {hs}x{ws_} / {hd}x{wd}, leg={leg}, nms_size={nms_size}, "
                            f"num_points={k}")
@@ -388,11 +354,18 @@ def val_points(prob_src: torch.Tensor, prob_dst: torch.Tensor, h_dst_2_src: torc
     dst = torch.empty((p, k, 4), dtype=torch.float64, device=dev)
     count = torch.empty((p, 2), dtype=torch.int32, device=dev)
     ws = _workspace("val_points", dev, nbytes)
-    with torch.cuda.device(dev):
-        check(l.balf_val_points(prob_src.data_ptr(), hs, ws_, prob_dst.data_ptr(), hd, wd, p, h_dst_2_src.data_ptr(),
-                                VAL_LEGS[leg], float(conf_thresh), int(nms_size), k, src.data_ptr(), dst.data_ptr(),
-                                count.data_ptr(), ws.data_ptr(), ws.numel(), current_stream_ptr(dev)), "balf_val_points")
+    launch("balf_val_points", dev, prob_src, hs, ws_, prob_dst, hd, wd, p, h_dst_2_src, VAL_LEGS[leg], float(conf_thresh),
+           int(nms_size), k, src, dst, count, Workspace(ws))
     return src, dst, count
+
+
+def _check_layouts(named, dev) -> None:
+    """``named``: (tensor, name, allowed shapes, dtype) tuples.  Every tensor is contiguous on the GPU ``dev``, of its dtype and of
+    one of its shapes."""
+    for t, name, shapes_ok, dt in named:
+        require_gpu_tensor(t, name)
+        if tuple(t.shape) not in shapes_ok or t.dtype != dt or t.device != dev:
+            raise BalfHipError(f"{name} must be a {' or '.join(map(str, shapes_ok))} {dt} tensor on {dev}")
 
 
 # ---- the resize protocol of the HSequences evaluation (benchmark_test/evaluate.py, datasets/dataset_utils.py drive these) ---
@@ -424,25 +397,16 @@ def resize_repeatability_batch(src: torch.Tensor, ns: torch.Tensor, dst: torch.T
     dev = src.device
     if dst.shape[0] != p or p == 0 or dst.device != dev:
         raise BalfHipError(f"src and dst must hold the same number (> 0) of pairs on one device, got {p} and {dst.shape[0]}")
-    for t, name, shapes_ok, dt in ((ns, "ns", ((p,),), torch.int32), (nd, "nd", ((p,),), torch.int32),
-                                   (h, "h", ((p, 3, 3), (p, 9)), torch.float64),
-                                   (h_inv, "h_inv", ((p, 3, 3), (p, 9)), torch.float64), (shapes, "shapes", ((p, 4),), torch.int32)):
-        require_gpu_tensor(t, name)
-        if tuple(t.shape) not in shapes_ok or t.dtype != dt or t.device != dev:
-            raise BalfHipError(f"{name} must be a {' or '.join(map(str, shapes_ok))} {dt} tensor on {dev}")
-    l = lib()
-    nbytes = l.balf_resize_repeatability_batch_workspace_bytes(p, ns_max, nd_max, k)
+    _check_layouts(((ns, "ns", ((p,),), torch.int32), (nd, "nd", ((p,),), torch.int32), (h, "h", ((p, 3, 3), (p, 9)), torch.float64),
+                    (h_inv, "h_inv", ((p, 3, 3), (p, 9)), torch.float64), (shapes, "shapes", ((p, 4),), torch.int32)), dev)
+    nbytes = lib().balf_resize_repeatability_batch_workspace_bytes(p, ns_max, nd_max, k)
     if nbytes == 0:
         raise BalfHipError(f"balf_resize_repeatability_batch: unsupported sizes P={p}, Ns={ns_max}, Nd={nd_max}, k={k}")
     rep = torch.empty((p, 2), dtype=torch.float64, device=dev)
     cnt = torch.empty((p, 4), dtype=torch.int32, device=dev)
     ws = _workspace("resize_repeat", dev, nbytes)
-    with torch.cuda.device(dev):
-        check(l.balf_resize_repeatability_batch(src.data_ptr(), ns.data_ptr(), ns_max, src.shape[2], dst.data_ptr(),
-                                                nd.data_ptr(), nd_max, dst.shape[2], 1, ROW_ORDERS[order], p, h.data_ptr(),
-                                                h_inv.data_ptr(), shapes.data_ptr(), k, float(distance_thresh),
-                                                rep.data_ptr(), cnt.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                current_stream_ptr(dev)), "balf_resize_repeatability_batch")
+    launch("balf_resize_repeatability_batch", dev, src, ns, ns_max, src.shape[2], dst, nd, nd_max, dst.shape[2], 1,
+           ROW_ORDERS[order], p, h, h_inv, shapes, k, float(distance_thresh), rep, cnt, Workspace(ws))
     return rep, cnt
 
 
@@ -462,10 +426,7 @@ def resize_crop_u8(packed: torch.Tensor, offsets: torch.Tensor, sizes: torch.Ten
         raise ValueError(f"channels must be 1 or 3, got {channels}")
     dev = packed.device
     out = torch.empty((b, int(target_h), int(target_w)) + ((3,) if channels == 3 else ()), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        check(lib().balf_resize_crop_u8(packed.data_ptr(), packed.numel(), offsets.data_ptr(), sizes.data_ptr(), b,
-                                        int(channels), int(target_h), int(target_w), out.data_ptr(),
-                                        current_stream_ptr(dev)), "balf_resize_crop_u8")
+    launch("balf_resize_crop_u8", dev, packed, packed.numel(), offsets, sizes, b, int(channels), int(target_h), int(target_w), out)
     return out
 
 
@@ -487,11 +448,8 @@ def synth_pairs(packed: torch.Tensor, offsets: torch.Tensor, sizes: torch.Tensor
             sizes.dtype != torch.int32 or tuple(sizes.shape) != (p, 2):
         raise BalfHipError("packed must be a 1-D uint8 tensor, offsets [P] int64 and sizes [P,2] int32 with P > 0")
     dev = packed.device
-    for t, name, shapes_ok, dt in ((inv_h, "inv_h", ((p, 3, 3), (p, 9)), torch.float64), (win_src, "win_src", ((p, 2),), torch.int32),
-                                   (win_dst, "win_dst", ((p, 2),), torch.int32),
-                                   (pts_offsets, "pts_offsets", ((p + 1,),), torch.int32)):
-        if tuple(t.shape) not in shapes_ok or t.dtype != dt or t.device != dev:
-            raise BalfHipError(f"{name} must be a {' or '.join(map(str, shapes_ok))} {dt} tensor on {dev}")
+    _check_layouts(((inv_h, "inv_h", ((p, 3, 3), (p, 9)), torch.float64), (win_src, "win_src", ((p, 2),), torch.int32),
+                    (win_dst, "win_dst", ((p, 2),), torch.int32), (pts_offsets, "pts_offsets", ((p + 1,),), torch.int32)), dev)
     if pts.dtype != torch.float32 or pts.dim() != 2 or pts.shape[1] != 3 or pts.device != dev:
         raise BalfHipError(f"pts must be an [N,3] float32 tensor on {dev}")
     top_k, patch = int(top_k), int(patch)
@@ -499,8 +457,7 @@ def synth_pairs(packed: torch.Tensor, offsets: torch.Tensor, sizes: torch.Tensor
         raise ValueError(f"top_k must be >= 0 (0 keeps every row), got {top_k}")
     if patch <= 0:
         raise ValueError(f"patch must be positive, got {patch}")
-    l = lib()
-    nbytes = l.balf_synth_pairs_workspace_bytes(p, patch)
+    nbytes = lib().balf_synth_pairs_workspace_bytes(p, patch)
     if nbytes == 0:
         raise BalfHipError(f"balf_synth_pairs: unsupported sizes P={p}, patch={patch}")
     shapes = ((p, 3, patch, patch), (p, 3, patch, patch), (p, 1, patch, patch), (p, 1, patch, patch), (p,))
@@ -514,12 +471,8 @@ def synth_pairs(packed: torch.Tensor, offsets: torch.Tensor, sizes: torch.Tensor
             if tuple(t.shape) != s or t.dtype != (torch.int32 if len(s) == 1 else torch.float32) or t.device != dev:
                 raise BalfHipError(f"out tensors must be {shapes} (float32, dst_max int32) on {dev}")
     ws = _workspace("synth_pairs", dev, nbytes)
-    with torch.cuda.device(dev):
-        check(l.balf_synth_pairs(packed.data_ptr(), packed.numel(), offsets.data_ptr(), sizes.data_ptr(), p, inv_h.data_ptr(),
-                                 win_src.data_ptr(), win_dst.data_ptr(), pts.data_ptr() if pts.shape[0] else None,
-                                 pts.shape[0], pts_offsets.data_ptr(), top_k, patch, out[0].data_ptr(), out[1].data_ptr(),
-                                 out[2].data_ptr(), out[3].data_ptr(), out[4].data_ptr(), ws.data_ptr(), ws.numel(),
-                                 current_stream_ptr(dev)), "balf_synth_pairs")
+    launch("balf_synth_pairs", dev, packed, packed.numel(), offsets, sizes, p, inv_h, win_src, win_dst,
+           pts if pts.shape[0] else None, pts.shape[0], pts_offsets, top_k, patch, *out, Workspace(ws))
     return tuple(out)
 
 
@@ -624,14 +577,8 @@ def detector_loss(logits: torch.Tensor, keypoint_map: torch.Tensor, valid_mask=N
     labels = torch.empty((b, hc, wc), dtype=torch.int32, device=dev) if want_labels else None
     dlogits = torch.empty_like(logits) if want_grad else None
     ws = _workspace("detector_loss", dev, lib().balf_detector_loss_workspace_bytes(b, hc, wc))
-
-    def ptr(t):
-        return t.data_ptr() if t is not None else None
-
-    with torch.cuda.device(dev):
-        check(lib().balf_detector_loss(logits.data_ptr(), keypoint_map.data_ptr(), ptr(valid_mask), ptr(noise), b, hc, wc,
-                                       loss.data_ptr(), ptr(per_image), ptr(labels), ptr(dlogits), ws.data_ptr(), ws.numel(),
-                                       current_stream_ptr(dev)), "balf_detector_loss")
+    launch("balf_detector_loss", dev, logits, keypoint_map, valid_mask, noise, b, hc, wc, loss, per_image, labels, dlogits,
+           Workspace(ws))
     return DetectorLoss(loss, per_image, labels, dlogits)
 
 
@@ -666,10 +613,6 @@ def _head_train_checks(x2, named):
     return b, hc, wc
 
 
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
-
-
 def head_train_forward(x2: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, wd: torch.Tensor, bd: torch.Tensor,
                        gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5, stats=None, want_prob=True,
                        running_mean=None, running_var=None, momentum: float = 0.1, saved=None) -> HeadTrainForward:
@@ -693,12 +636,8 @@ def head_train_forward(x2: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, wd:
     if prob is None and want_prob:
         prob = torch.empty((b, 8 * hc, 8 * wc), dtype=torch.float32, device=dev)
     ws = _workspace("head_train", dev, l.balf_head_train_workspace_bytes(n))
-    with torch.cuda.device(dev):
-        check(l.balf_head_train_forward(x2.data_ptr(), w2.data_ptr(), b2.data_ptr(), wd.data_ptr(), bd.data_ptr(),
-                                        gamma.data_ptr(), beta.data_ptr(), b, hc, wc, float(eps), 0 if stats is None else 1,
-                                        _ptr(stats), logits.data_ptr(), _ptr(prob), _ptr(running_mean), _ptr(running_var),
-                                        float(momentum), saved.data_ptr(), ws.data_ptr(), ws.numel(), current_stream_ptr(dev)),
-              "balf_head_train_forward")
+    launch("balf_head_train_forward", dev, x2, w2, b2, wd, bd, gamma, beta, b, hc, wc, float(eps), 0 if stats is None else 1, stats,
+           logits, prob, running_mean, running_var, float(momentum), saved, Workspace(ws))
     return HeadTrainForward(logits, prob, saved)
 
 
@@ -719,10 +658,7 @@ def head_train_backward(dlogits: torch.Tensor, x2: torch.Tensor, w2: torch.Tenso
         dx2 = torch.empty_like(x2)
     out = [torch.empty(s[k], dtype=torch.float32, device=dev) for k in ("w2", "b2", "wd", "bd", "gamma", "beta")]
     ws = _workspace("head_train", dev, l.balf_head_train_workspace_bytes(n))
-    with torch.cuda.device(dev):
-        check(l.balf_head_train_backward(dlogits.data_ptr(), x2.data_ptr(), w2.data_ptr(), wd.data_ptr(), gamma.data_ptr(),
-                                         saved.data_ptr(), b, hc, wc, *[t.data_ptr() for t in out], _ptr(dx2), ws.data_ptr(),
-                                         ws.numel(), current_stream_ptr(dev)), "balf_head_train_backward")
+    launch("balf_head_train_backward", dev, dlogits, x2, w2, wd, gamma, saved, b, hc, wc, *out, dx2, Workspace(ws))
     return HeadTrainBackward(*out, dx2)
 
 
@@ -778,10 +714,7 @@ def rcab_train_forward(y: torch.Tensor, r: torch.Tensor, params, saved=None) -> 
     saved = _saved_block(saved, l.balf_rcab_train_saved_bytes(b, hc, wc), dev, True)
     x2 = torch.empty_like(y)
     ws = _workspace("rcab_train", dev, l.balf_rcab_train_workspace_bytes(b, hc, wc))
-    with torch.cuda.device(dev):
-        check(l.balf_rcab_train_forward(y.data_ptr(), r.data_ptr(), *[t.data_ptr() for t in params], b, hc, wc, x2.data_ptr(),
-                                        saved.data_ptr(), ws.data_ptr(), ws.numel(), current_stream_ptr(dev)),
-              "balf_rcab_train_forward")
+    launch("balf_rcab_train_forward", dev, y, r, *params, b, hc, wc, x2, saved, Workspace(ws))
     return RcabTrainForward(x2, saved)
 
 
@@ -803,11 +736,7 @@ def rcab_train_backward(dx2: torch.Tensor, y: torch.Tensor, ln_g: torch.Tensor, 
         dy = torch.empty_like(y)
     out = [torch.empty(s[k], dtype=torch.float32, device=dev) for k in RCAB_PARAMS]
     ws = _workspace("rcab_train", dev, l.balf_rcab_train_workspace_bytes(b, hc, wc))
-    with torch.cuda.device(dev):
-        check(l.balf_rcab_train_backward(dx2.data_ptr(), y.data_ptr(), ln_g.data_ptr(), wc1.data_ptr(), wc2.data_ptr(),
-                                         ws0.data_ptr(), ws2.data_ptr(), saved.data_ptr(), b, hc, wc,
-                                         *[t.data_ptr() for t in out], _ptr(dy), ws.data_ptr(), ws.numel(),
-                                         current_stream_ptr(dev)), "balf_rcab_train_backward")
+    launch("balf_rcab_train_backward", dev, dx2, y, ln_g, wc1, wc2, ws0, ws2, saved, b, hc, wc, *out, dy, Workspace(ws))
     return RcabTrainBackward(*out, dy)
 
 
@@ -818,11 +747,7 @@ def rcab_inputs(precision: int, workspace: torch.Tensor, b: int, hp: int, wp: in
     workspace's GPU; ``conv0_w`` [256,128], ``conv0_b`` [256] are ``down4.conv.0``.  ``precision``: _lib.PREC_FP32 / PREC_FP16,
     the kernels that forward ran on."""
     _stage4_input_checks("rcab_inputs", workspace, b, hp, wp, conv0_w, conv0_b, ((y, "y"), (r, "r")))
-    dev = workspace.device
-    with torch.cuda.device(dev):
-        check(lib().balf_forward_rcab_inputs(precision, workspace.data_ptr(), workspace.numel(), b, hp, wp, conv0_w.data_ptr(),
-                                             conv0_b.data_ptr(), y.data_ptr(), r.data_ptr(), current_stream_ptr(dev)),
-              "balf_forward_rcab_inputs")
+    launch("balf_forward_rcab_inputs", workspace.device, precision, Workspace(workspace), b, hp, wp, conv0_w, conv0_b, y, r)
 
 
 _GMLP_BRANCH = ("norm.weight", "norm.bias", "dense1.weight", "dense1.bias", "{u}.norm.weight", "{u}.norm.bias", "{u}.dense.weight",
@@ -878,9 +803,7 @@ def gmlp_train_forward(x0: torch.Tensor, params, saved=None) -> GmlpTrainForward
     saved = _saved_block(saved, l.balf_gmlp_train_saved_bytes(b, hc, wc), dev, True)
     y = torch.empty_like(x0)
     ws = _workspace("gmlp_train", dev, l.balf_gmlp_train_workspace_bytes(b, hc, wc))
-    with torch.cuda.device(dev):
-        check(l.balf_gmlp_train_forward(x0.data_ptr(), _pointer_array(params), b, hc, wc, y.data_ptr(), saved.data_ptr(),
-                                        ws.data_ptr(), ws.numel(), current_stream_ptr(dev)), "balf_gmlp_train_forward")
+    launch("balf_gmlp_train_forward", dev, x0, _pointer_array(params), b, hc, wc, y, saved, Workspace(ws))
     return GmlpTrainForward(y, saved)
 
 
@@ -898,10 +821,8 @@ def gmlp_train_backward(dy: torch.Tensor, x0: torch.Tensor, params, saved: torch
         dx0 = torch.empty_like(x0)
     out = tuple(torch.empty(_GMLP_PARAM_SHAPES[k], dtype=torch.float32, device=dev) for k in GMLP_PARAMS)
     ws = _workspace("gmlp_train", dev, l.balf_gmlp_train_workspace_bytes(b, hc, wc))
-    with torch.cuda.device(dev):
-        check(l.balf_gmlp_train_backward(dy.data_ptr(), x0.data_ptr(), _pointer_array(params), saved.data_ptr(), b, hc, wc,
-                                         _pointer_array(out), _ptr(dx0), ws.data_ptr(), ws.numel(), current_stream_ptr(dev)),
-              "balf_gmlp_train_backward")
+    launch("balf_gmlp_train_backward", dev, dy, x0, _pointer_array(params), saved, b, hc, wc, _pointer_array(out), dx0,
+           Workspace(ws))
     return GmlpTrainBackward(out, dx0)
 
 
@@ -915,10 +836,7 @@ def gmlp_input(precision: int, workspace: torch.Tensor, b: int, hp: int, wp: int
     scratch = None
     if precision == _lib.PREC_FP16:
         scratch = _workspace("gmlp_input", dev, x0.numel() // 2 * 4)
-    with torch.cuda.device(dev):
-        check(lib().balf_forward_gmlp_input(precision, workspace.data_ptr(), workspace.numel(), b, hp, wp, conv0_w.data_ptr(),
-                                            conv0_b.data_ptr(), x0.data_ptr(), _ptr(scratch), current_stream_ptr(dev)),
-              "balf_forward_gmlp_input")
+    launch("balf_forward_gmlp_input", dev, precision, Workspace(workspace), b, hp, wp, conv0_w, conv0_b, x0, scratch)
 
 
 LINRELU_PARAMS = ("weight", "bias")       # of the Linear c_in -> 2 c_in in front of a ReLU (down4.conv.0 at c_in = 128)
@@ -956,9 +874,7 @@ def linrelu_train_forward(x: torch.Tensor, weight: torch.Tensor, bias: torch.Ten
     n, c_in = _linrelu_train_checks(x, weight, ((bias, "bias", (2 * c,)),))
     dev = x.device
     y = torch.empty(tuple(x.shape[:-1]) + (2 * c_in,), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        check(lib().balf_linrelu_train_forward(x.data_ptr(), weight.data_ptr(), bias.data_ptr(), n, c_in, y.data_ptr(),
-                                               current_stream_ptr(dev)), "balf_linrelu_train_forward")
+    launch("balf_linrelu_train_forward", dev, x, weight, bias, n, c_in, y)
     return LinreluTrainForward(y)
 
 
@@ -976,10 +892,7 @@ def linrelu_train_backward(g: torch.Tensor, y: torch.Tensor, x: torch.Tensor, we
     dw = torch.empty((2 * c_in, c_in), dtype=torch.float32, device=dev)
     db = torch.empty((2 * c_in,), dtype=torch.float32, device=dev)
     ws = _workspace("linrelu_train", dev, l.balf_linrelu_train_workspace_bytes(n, c_in))
-    with torch.cuda.device(dev):
-        check(l.balf_linrelu_train_backward(g.data_ptr(), y.data_ptr(), x.data_ptr(), weight.data_ptr(), n, c_in, dw.data_ptr(),
-                                            db.data_ptr(), _ptr(dx), ws.data_ptr(), ws.numel(), current_stream_ptr(dev)),
-              "balf_linrelu_train_backward")
+    launch("balf_linrelu_train_backward", dev, g, y, x, weight, n, c_in, dw, db, dx, Workspace(ws))
     return LinreluTrainBackward(dw, db, dx)
 
 
@@ -1062,21 +975,6 @@ def _optim_runs(n: int):
     return [(at, min(n, at + _lib.OPTIM_MAX_TENSORS)) for at in range(0, n, _lib.OPTIM_MAX_TENSORS)]
 
 
-def _raw_stream(index: int) -> int:
-    """The current stream of device ``index`` as the pointer the library takes: torch's direct accessor where this build has
-    it (a tenth of the cost of making a ``torch.cuda.Stream`` object, which shows in a 37 us step), else through that object."""
-    get = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-    return get(index) if get is not None else torch.cuda.current_stream(index).cuda_stream
-
-
-def _optim_launch(o: OptimPointers, call) -> int:
-    """``call(stream)`` with ``o``'s device current: without the context manager when it already is (the common case)."""
-    if torch.cuda.current_device() == o.index:
-        return call(_raw_stream(o.index))
-    with torch.cuda.device(o.device):
-        return call(_raw_stream(o.index))
-
-
 def adam_step(params, grads, exp_avgs, exp_avg_sqs, lr: float, beta1: float, beta2: float, eps: float, weight_decay: float,
               step: int, pointers: Optional[OptimPointers] = None) -> None:
     """One step of ``torch.optim.Adam`` (amsgrad=False, maximize=False, L2 weight decay) in place on lists of tensors, ONE launch per
@@ -1097,7 +995,7 @@ def adam_step(params, grads, exp_avgs, exp_avg_sqs, lr: float, beta1: float, bet
     step = int(step)
     for o, gs in runs:
         _optim_gradients(o, gs)
-        check(_optim_launch(o, lambda stream: fn(o.n, o.p, o.g, o.m, o.v, o.numel, lr, beta1, beta2, eps, weight_decay, step, stream)),
+        check(on_device(o.index, lambda stream: fn(o.n, o.p, o.g, o.m, o.v, o.numel, lr, beta1, beta2, eps, weight_decay, step, stream)),
               "balf_adam_step")
 
 
@@ -1114,4 +1012,4 @@ def sgd_step(params, grads, lr: float, pointers: Optional[OptimPointers] = None)
     fn = lib().balf_sgd_step
     for o, gs in runs:
         _optim_gradients(o, gs)
-        check(_optim_launch(o, lambda stream: fn(o.n, o.p, o.g, o.numel, lr, stream)), "balf_sgd_step")
+        check(on_device(o.index, lambda stream: fn(o.n, o.p, o.g, o.numel, lr, stream)), "balf_sgd_step")
