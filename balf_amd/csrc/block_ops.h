@@ -6,6 +6,7 @@
 // only), with the same arguments where a comment says "uniform".  The LDS is the caller's: nothing here declares __shared__,
 // so a kernel that must keep zero static LDS keeps it.  Each function frees its own scratch with the barriers its comment
 // lists, so it may be called again on the same LDS at once.
+// Device building blocks (the host shares next_pow2 and kMaxPairs); the host's own helpers are in common.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -23,17 +24,6 @@ __host__ __device__ __forceinline__ int next_pow2(int v) {
     while (p < v) p <<= 1;
     return p;
 }
-
-// ---- host side ----------------------------------------------------------------------------------------------------------------
-// Bump allocator over a workspace: slices of 256-byte granularity in call order.  `used` is the layout's size so far (start it
-// at a byte offset to continue a layout); base == nullptr sizes a layout without handing out pointers.
-struct WorkspaceCursor {
-    char *base;
-    size_t used;
-    size_t offset(size_t bytes) { const size_t at = used; used += balf_align_up(bytes, 256); return at; }
-    template <typename T>
-    T *take(size_t bytes) { const size_t at = offset(bytes); return base ? reinterpret_cast<T *>(base + at) : nullptr; }
-};
 
 // ---- wave level (64 lanes, all active) ----------------------------------------------------------------------------------------
 // (summed in the type of the argument: a bool or a comparison would be summed as such, hence the list)

@@ -424,7 +424,8 @@ struct HeadArgs {
 #endif
 struct Plan {
     int mb;                 // images per micro-batch
-    size_t off_U, off_T, off_R, off_X[3], off_partial, off_chunk, off_scale, total;
+    float *U, *T, *R, *X[3], *partial, *chunk, *scale;      // null when the plan only sizes the workspace
+    size_t total;
 };
 
 // Run-time knob: BALF_MB_MPIXELS = 1 .. 64 in the environment of the process overrides the compiled default, in
@@ -439,34 +440,34 @@ inline long mb_pixels() {
     return v;
 }
 
-inline Plan make_plan(int B, int Hp, int Wp) {
+// The workspace of one micro-batch, laid out once: sized with base == nullptr, handed out with the caller's pointer.
+inline Plan make_plan(int B, int Hp, int Wp, void *base = nullptr) {
     Plan p{};
     const long px = (long)Hp * Wp;
     long mb = mb_pixels() / px;                        // <= 33.5 Mpx of stage-1 activations in flight (default)
     if (mb < 1) mb = 1;
     if (mb > B) mb = B;
     p.mb = (int)mb;
-    size_t o = 0;
-    auto take = [&](size_t floats) { size_t r = o; o = balf_align_up(o + floats * sizeof(float), 256); return r; };
+    WorkspaceCursor c{static_cast<char *>(base), 0};
+    auto take = [&](size_t floats) { return c.take<float>(floats * sizeof(float)); };
     const size_t big = (size_t)mb * px * 32;           // every stage: H*W*C = px * 32 / 2^(s)
-    p.off_U = take(big);
-    p.off_T = take(big);
-    p.off_R = take(big);
-    p.off_X[0] = take((size_t)mb * (px / 4) * 32);
-    p.off_X[1] = take((size_t)mb * (px / 16) * 64);
-    p.off_X[2] = take((size_t)mb * (px / 64) * 128);
-    p.off_partial = take((size_t)mb * (px / 64) * 32);  // groups/P * C <= px/64 * 32 for every stage
-    p.off_chunk = take((size_t)mb * kSeChunks * 256);
-    p.off_scale = take((size_t)mb * 256);
-    p.total = o;
+    p.U = take(big);
+    p.T = take(big);
+    p.R = take(big);
+    p.X[0] = take((size_t)mb * (px / 4) * 32);
+    p.X[1] = take((size_t)mb * (px / 16) * 64);
+    p.X[2] = take((size_t)mb * (px / 64) * 128);
+    p.partial = take((size_t)mb * (px / 64) * 32);      // groups/P * C <= px/64 * 32 for every stage
+    p.chunk = take((size_t)mb * kSeChunks * 256);
+    p.scale = take((size_t)mb * 256);
+    p.total = c.used;
     return p;
 }
 
-
 // entry points of the two implementations (detector.hip / detector_f16.hip)
 int forward_f32(const float *blob, const float *x, const InputU8 &u8, int B, int Hp, int Wp, float *logits, float *prob,
-                char *ws, const Plan &pl, int *status, hipStream_t st);
+                const Plan &pl, int *status, hipStream_t st);
 int forward_f16(const float *blob, const float *x, const InputU8 &u8, int B, int Hp, int Wp, float *logits, float *prob,
-                char *ws, const Plan &pl, int *status, hipStream_t st);
+                const Plan &pl, int *status, hipStream_t st);
 
 }  // namespace balf

@@ -24,7 +24,6 @@
 //   se_kernel        per image: mean(t) -> C/4 -> C MLP -> sigmoid                (deterministic order)
 //   pool_kernel      stages 1-3: x2 = t*s + r, 2x2 max pool -> next stage's NHWC input
 //   head_kernel      stage 4: x2 -> conv2 -> relu -> dense(256->65) -> BN -> softmax -> pixel shuffle
-#include <atomic>
 
 #include "det_common.h"
 
@@ -396,20 +395,6 @@ __global__ __launch_bounds__(256, 2) void head_kernel(HeadArgs A) {
 #define BALF_F32_S1_GENERIC 0     // 1: stage 1 on the generic kernel (rounds 1-4), for A/B timing
 #endif
 
-// hipFuncSetAttribute is a driver round trip (tens of microseconds): once per kernel and device of the process, not per launch
-// (as ensure_kernel_attributes of detector_f16.hip; a single-image call on the fp32 path made four of them)
-template <auto Kernel>
-bool allow_lds32(int bytes) {
-    static std::atomic<unsigned long long> done{0};              // bit d: device d has the attribute
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
-    if (done.load(std::memory_order_acquire) >> dev & 1) return true;
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess)
-        return false;
-    done.fetch_or(1ull << dev, std::memory_order_release);
-    return true;
-}
-
 template <int C, int CIN>
 int run_stage(int *status, const float *blob, int s, const float *X, const InputU8 &u8, int B, int H, int W, float *U, float *T, float *R,
               float *partial, float *chunk, float *scale, hipStream_t st) {
@@ -422,7 +407,7 @@ int run_stage(int *status, const float *blob, int s, const float *X, const Input
         long wgs = (groups + kF1NW - 1) / kF1NW;
         wgs = (wgs + 7) / 8 * 8;
         if (wgs > 256) wgs = 256;
-        if (!allow_lds32<stage1_kernel32<0>>(f1_lds_bytes<0>()) || !allow_lds32<stage1_kernel32<1>>(f1_lds_bytes<1>())) return BALF_ERR_LAUNCH;
+        if (!balf_allow_dynamic_lds<stage1_kernel32<0>>(f1_lds_bytes<0>()) || !balf_allow_dynamic_lds<stage1_kernel32<1>>(f1_lds_bytes<1>())) return BALF_ERR_LAUNCH;
         BALF_PROF(4 * s + 0, st, hipLaunchKernelGGL(stage1_kernel32<0>, dim3((unsigned)wgs), dim3(kF1NW * 64), f1_lds_bytes<0>(), st, a));
 #if BALF_F32_DBG
         if (getenv("BALF_DEBUG_STOP_STAGE")) return BALF_OK;
@@ -435,9 +420,7 @@ int run_stage(int *status, const float *blob, int s, const float *X, const Input
         const int nwg = B * per_img;
         auto k0 = stage_branch_kernel<C, CIN, 0>;
         auto k1 = stage_branch_kernel<C, CIN, 1>;
-        if (lds > 48 * 1024) {
-            if (!allow_lds32<stage_branch_kernel<C, CIN, 0>>(lds) || !allow_lds32<stage_branch_kernel<C, CIN, 1>>(lds)) return BALF_ERR_LAUNCH;
-        }
+        if (!balf_allow_dynamic_lds<stage_branch_kernel<C, CIN, 0>>(lds) || !balf_allow_dynamic_lds<stage_branch_kernel<C, CIN, 1>>(lds)) return BALF_ERR_LAUNCH;
         BALF_PROF(4 * s + 0, st, hipLaunchKernelGGL(k0, dim3(nwg), dim3(256), lds, st, a));
         BALF_PROF(4 * s + 1, st, hipLaunchKernelGGL(k1, dim3(nwg), dim3(256), lds, st, a));
     }
@@ -465,14 +448,11 @@ int run_pool(int s, const float *T, const float *R, const float *scale, int B, i
 }  // namespace
 
 int forward_f32(const float *blob, const float *x_nchw_dev, const InputU8 &u8, int B, int Hp, int Wp, float *logits_dev,
-                float *prob_dev, char *ws, const Plan &pl, int *status, hipStream_t st) {
+                float *prob_dev, const Plan &pl, int *status, hipStream_t st) {
     balf_prof::Chain prof_chain;       // the launches below follow each other on `st` with nothing in between
 
-    float *U = reinterpret_cast<float *>(ws + pl.off_U), *T = reinterpret_cast<float *>(ws + pl.off_T),
-          *R = reinterpret_cast<float *>(ws + pl.off_R), *partial = reinterpret_cast<float *>(ws + pl.off_partial),
-          *chunk = reinterpret_cast<float *>(ws + pl.off_chunk), *scale = reinterpret_cast<float *>(ws + pl.off_scale);
-    float *X2 = reinterpret_cast<float *>(ws + pl.off_X[0]), *X3 = reinterpret_cast<float *>(ws + pl.off_X[1]),
-          *X4 = reinterpret_cast<float *>(ws + pl.off_X[2]);
+    float *const U = pl.U, *const T = pl.T, *const R = pl.R, *const partial = pl.partial, *const chunk = pl.chunk,
+                 *const scale = pl.scale, *const X2 = pl.X[0], *const X3 = pl.X[1], *const X4 = pl.X[2];
     const int h8 = Hp / 8, w8 = Wp / 8;
 
     for (int b0 = 0; b0 < B; b0 += pl.mb) {
@@ -525,13 +505,12 @@ static int forward_common(const void *packed_dev, int precision, const float *x_
     // the kernels address a pixel's row inside ONE image with 32-bit byte offsets (up to 128 B per stage-1 pixel): 2^25 pixels
     // per padded image (5792 x 5792) is the limit; it is also what one micro-batch holds (BALF_MB_PIXELS)
     if ((long)Hp * Wp > (1L << 25)) return BALF_ERR_SHAPE;
-    const balf::Plan pl = balf::make_plan(B, Hp, Wp);
+    const balf::Plan pl = balf::make_plan(B, Hp, Wp, workspace_dev);
     if (workspace_bytes < pl.total) return BALF_ERR_WORKSPACE;
     const float *blob = static_cast<const float *>(packed_dev);
-    char *ws = static_cast<char *>(workspace_dev);
     return precision == BALF_PREC_FP32
-               ? balf::forward_f32(blob, x_nchw_dev, u8, B, Hp, Wp, logits_dev, prob_dev, ws, pl, status_dev, (hipStream_t)stream)
-               : balf::forward_f16(blob, x_nchw_dev, u8, B, Hp, Wp, logits_dev, prob_dev, ws, pl, status_dev, (hipStream_t)stream);
+               ? balf::forward_f32(blob, x_nchw_dev, u8, B, Hp, Wp, logits_dev, prob_dev, pl, status_dev, (hipStream_t)stream)
+               : balf::forward_f16(blob, x_nchw_dev, u8, B, Hp, Wp, logits_dev, prob_dev, pl, status_dev, (hipStream_t)stream);
 }
 
 extern "C" int balf_forward_status(const void *packed_dev, int precision, const float *x_nchw_dev, int B, int Hp, int Wp,

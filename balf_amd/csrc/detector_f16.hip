@@ -23,7 +23,6 @@
 // halves][lo: q0..q3 x 8 halves] -- the same bytes per pixel as fp32 NHWC.
 #include <stdlib.h>
 
-#include <mutex>
 #include <type_traits>
 
 #include "det_common.h"
@@ -473,32 +472,19 @@ static_assert(s2_lds_bytes<0>() <= 160 * 1024 && s2_lds_bytes<1>() <= 160 * 1024
 static_assert(cs_launch_lds<128, 0>() <= 160 * 1024 && cs_launch_lds<128, 1>() <= 160 * 1024 && cs_launch_lds<256, 0>() <= 160 * 1024 &&
               cs_launch_lds<256, 1>() <= 160 * 1024, "channel-split LDS image");
 
-template <typename K>
-bool allow_lds(K k, int bytes) {
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess;
-}
-
-// hipFuncSetAttribute is a driver round trip (tens of microseconds each, 17 kernels): done once per device of the process
-// instead of before every launch -- what a single-image call (the reference's only calling pattern, demo_match.py:29) feels.
+// Every kernel of this file that takes dynamic LDS, with its size: the driver is asked once per kernel and device of the process (17
+// round trips of tens of microseconds), not before every launch -- what a single-image call (demo_match.py:29) feels.
 int ensure_kernel_attributes() {
-    static std::mutex mu;
-    static unsigned long long done = 0;              // bit d: device d has its attributes
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return BALF_ERR_LAUNCH;
-    std::lock_guard<std::mutex> lock(mu);
-    if (done >> dev & 1) return BALF_OK;
     bool ok = true;
-    ok = ok && allow_lds(stage1_kernel16<0, false>, s1_lds_bytes<0>()) && allow_lds(stage1_kernel16<0, true>, s1_lds_bytes<0>());
-    ok = ok && allow_lds(stage1_kernel16<1, false>, s1_lds_bytes<1>()) && allow_lds(stage1_kernel16<1, true>, s1_lds_bytes<1>());
-    ok = ok && allow_lds(stage1_kernel16<2, false>, s1_lds_bytes<2>()) && allow_lds(stage1_kernel16<2, true>, s1_lds_bytes<2>());
-    ok = ok && allow_lds(stage2_kernel16<0>, s2_lds_bytes<0>()) && allow_lds(stage2_kernel16<1>, s2_lds_bytes<1>()) &&
-         allow_lds(stage2_kernel16<2>, s2_lds_bytes<2>());
-    ok = ok && allow_lds(stage_cs_kernel16<128, 64, 0>, cs_launch_lds<128, 0>()) && allow_lds(stage_cs_kernel16<128, 64, 1>, cs_launch_lds<128, 1>()) &&
-         allow_lds(stage3_tail_kernel16, kT3LdsBytes);
-    ok = ok && allow_lds(stage_cs_kernel16<256, 128, 0>, cs_launch_lds<256, 0>()) && allow_lds(stage_cs_kernel16<256, 128, 1>, cs_launch_lds<256, 1>());
-    if (!ok) return BALF_ERR_LAUNCH;
-    done |= 1ull << dev;
-    return BALF_OK;
+    ok = ok && balf_allow_dynamic_lds<stage1_kernel16<0, false>>(s1_lds_bytes<0>()) && balf_allow_dynamic_lds<stage1_kernel16<0, true>>(s1_lds_bytes<0>());
+    ok = ok && balf_allow_dynamic_lds<stage1_kernel16<1, false>>(s1_lds_bytes<1>()) && balf_allow_dynamic_lds<stage1_kernel16<1, true>>(s1_lds_bytes<1>());
+    ok = ok && balf_allow_dynamic_lds<stage1_kernel16<2, false>>(s1_lds_bytes<2>()) && balf_allow_dynamic_lds<stage1_kernel16<2, true>>(s1_lds_bytes<2>());
+    ok = ok && balf_allow_dynamic_lds<stage2_kernel16<0>>(s2_lds_bytes<0>()) && balf_allow_dynamic_lds<stage2_kernel16<1>>(s2_lds_bytes<1>()) &&
+         balf_allow_dynamic_lds<stage2_kernel16<2>>(s2_lds_bytes<2>());
+    ok = ok && balf_allow_dynamic_lds<stage_cs_kernel16<128, 64, 0>>(cs_launch_lds<128, 0>()) && balf_allow_dynamic_lds<stage_cs_kernel16<128, 64, 1>>(cs_launch_lds<128, 1>());
+    ok = ok && balf_allow_dynamic_lds<stage_cs_kernel16<256, 128, 0>>(cs_launch_lds<256, 0>()) && balf_allow_dynamic_lds<stage_cs_kernel16<256, 128, 1>>(cs_launch_lds<256, 1>());
+    ok = ok && balf_allow_dynamic_lds<stage3_tail_kernel16>(kT3LdsBytes);
+    return ok ? BALF_OK : BALF_ERR_LAUNCH;
 }
 
 // grid of the persistent stage-1 kernels: one workgroup per CU at most (256 CUs on MI355X; any multiple of 8 is correct),
@@ -599,15 +585,12 @@ extern "C" int balf_debug_stamps(unsigned long long *sums /*[16*40]*/, unsigned 
 #endif
 
 int forward_f16(const float *blob, const float *x_nchw_dev, const InputU8 &u8, int B, int Hp, int Wp, float *logits_dev,
-                float *prob_dev, char *ws, const Plan &pl, int *status, hipStream_t st) {
+                float *prob_dev, const Plan &pl, int *status, hipStream_t st) {
     if (const int rc = ensure_kernel_attributes(); rc != BALF_OK) return rc;
     balf_prof::Chain prof_chain;       // the launches below follow each other on `st` with nothing in between
 
-    float *U = reinterpret_cast<float *>(ws + pl.off_U), *T = reinterpret_cast<float *>(ws + pl.off_T),
-          *R = reinterpret_cast<float *>(ws + pl.off_R), *partial = reinterpret_cast<float *>(ws + pl.off_partial),
-          *chunk = reinterpret_cast<float *>(ws + pl.off_chunk), *scale = reinterpret_cast<float *>(ws + pl.off_scale);
-    float *X2 = reinterpret_cast<float *>(ws + pl.off_X[0]), *X3 = reinterpret_cast<float *>(ws + pl.off_X[1]),
-          *X4 = reinterpret_cast<float *>(ws + pl.off_X[2]);
+    float *const U = pl.U, *const T = pl.T, *const R = pl.R, *const partial = pl.partial, *const chunk = pl.chunk,
+                 *const scale = pl.scale, *const X2 = pl.X[0], *const X3 = pl.X[1], *const X4 = pl.X[2];
     const int h8 = Hp / 8, w8 = Wp / 8;
 
     for (int b0 = 0; b0 < B; b0 += pl.mb) {

@@ -535,15 +535,23 @@ int hn_chunk() {
     return c;
 }
 
+// bufA and bufB hold one chunk of patches (hn_chunk() of them, or all when there are fewer) and are reused by every chunk; a6
+// holds the whole batch.  (Every size is a multiple of 256 bytes per patch: the cursor rounds nothing up.)
+struct HnWs { int chunk; char *bufA, *bufB, *a6; size_t total; };
+HnWs hn_layout(int n_patches, void *base = nullptr) {
+    HnWs l{};
+    l.chunk = n_patches < hn_chunk() ? n_patches : hn_chunk();
+    WorkspaceCursor c{static_cast<char *>(base), 0};
+    l.bufA = c.take<char>((size_t)l.chunk * kBufA);
+    l.bufB = c.take<char>((size_t)l.chunk * kBufB);
+    l.a6 = c.take<char>((size_t)n_patches * kBufA6);
+    l.total = c.used;
+    return l;
+}
+
 template <typename Cfg>
 int launch_conv(int slot, const ConvArgs &a, hipStream_t st) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&hn_conv_kernel<Cfg>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES) != hipSuccess)
-            return BALF_ERR_LAUNCH;
-        attr_set = true;
-    }
+    if (!balf_allow_dynamic_lds<hn_conv_kernel<Cfg>>(Cfg::LDS_BYTES)) return BALF_ERR_LAUNCH;
     BALF_PROF(slot, st, (hn_conv_kernel<Cfg><<<a.n_patches * Cfg::BANDS, 256, Cfg::LDS_BYTES, st>>>(a)));
     BALF_LAUNCH_CHECK();
     return BALF_OK;
@@ -620,19 +628,16 @@ extern "C" int balf_hardnet_pack_weights(const float *const *tensors, int n_tens
 
 extern "C" size_t balf_hardnet_workspace_bytes(int n_patches) {
     if (n_patches <= 0) return 0;
-    const size_t c = n_patches < hn_chunk() ? n_patches : hn_chunk();
-    return c * (kBufA + kBufB) + (size_t)n_patches * kBufA6;
+    return hn_layout(n_patches).total;
 }
 
 namespace {
 template <bool SP>
 int hardnet_forward_impl(const void *packed_dev, const float *patches_dev, int n_patches, int group, const int32_t *count_dev,
-                         float *desc_dev, void *workspace_dev, hipStream_t st) {
+                         float *desc_dev, const HnWs &ws, hipStream_t st) {
     const char *blob = static_cast<const char *>(packed_dev);
-    const int chunk = n_patches < hn_chunk() ? n_patches : hn_chunk();
-    char *bufA = static_cast<char *>(workspace_dev);
-    char *bufB = bufA + (size_t)chunk * kBufA;
-    char *a6 = bufB + (size_t)chunk * kBufB;
+    const int chunk = ws.chunk;
+    char *bufA = ws.bufA, *bufB = ws.bufB, *a6 = ws.a6;
     constexpr size_t a6_bytes = SP ? kBufA6 : kBufA6 / 2;              // one plane in plain-f16 mode
     auto bias = [&](int l) { return reinterpret_cast<const float *>(blob + hn_boff(l)); };
     for (int c0 = 0; c0 < n_patches; c0 += chunk) {
@@ -668,11 +673,12 @@ extern "C" int balf_hardnet_forward_ex(const void *packed_dev, const float *patc
     if (!packed_dev || !patches_dev || !desc_dev || !workspace_dev || n_patches <= 0) return BALF_ERR_ARG;
     if (count_dev && (group <= 0 || n_patches % group != 0)) return BALF_ERR_ARG;
     if (precision != BALF_HARDNET_SPLIT_F16 && precision != BALF_HARDNET_PLAIN_F16) return BALF_ERR_ARG;
-    if (workspace_bytes < balf_hardnet_workspace_bytes(n_patches)) return BALF_ERR_WORKSPACE;
+    const HnWs ws = hn_layout(n_patches, workspace_dev);
+    if (workspace_bytes < ws.total) return BALF_ERR_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     return precision == BALF_HARDNET_SPLIT_F16
-               ? hardnet_forward_impl<true>(packed_dev, patches_dev, n_patches, group, count_dev, desc_dev, workspace_dev, st)
-               : hardnet_forward_impl<false>(packed_dev, patches_dev, n_patches, group, count_dev, desc_dev, workspace_dev, st);
+               ? hardnet_forward_impl<true>(packed_dev, patches_dev, n_patches, group, count_dev, desc_dev, ws, st)
+               : hardnet_forward_impl<false>(packed_dev, patches_dev, n_patches, group, count_dev, desc_dev, ws, st);
 }
 
 extern "C" int balf_hardnet_forward_masked(const void *packed_dev, const float *patches_dev, int n_patches, int group,

@@ -173,32 +173,38 @@ __global__ __launch_bounds__(1024) void match_mutual_kernel(const int *idx1, con
 
 using namespace balf;
 
+// per side ONE 256-aligned slice of two halves: the nearest neighbour's index [pairs, k], then its ratio to the second [pairs, k]
+struct MatchWs { int *idx1, *idx2; float *r1, *r2; size_t total; };
+static MatchWs match_layout(int pairs, int k1, int k2, void *base = nullptr) {
+    WorkspaceCursor c{static_cast<char *>(base), 0};
+    MatchWs l{c.take<int>((size_t)pairs * k1 * 8), c.take<int>((size_t)pairs * k2 * 8), nullptr, nullptr, 0};
+    if (base) l.r1 = reinterpret_cast<float *>(l.idx1 + (size_t)pairs * k1), l.r2 = reinterpret_cast<float *>(l.idx2 + (size_t)pairs * k2);
+    l.total = c.used;
+    return l;
+}
+
 extern "C" size_t balf_match_smnn_batch_workspace_bytes(int pairs, int k1, int k2) {
     if (pairs <= 0 || k1 <= 0 || k2 <= 0) return 0;
-    return balf_align_up((size_t)pairs * k1 * 8, 256) + balf_align_up((size_t)pairs * k2 * 8, 256);
+    return match_layout(pairs, k1, k2).total;
 }
 
 // pairs > 1 (or count pointers given): desc1 [pairs,k1,128], desc2 [pairs,k2,128] with n1_dev/n2_dev [pairs] valid rows
 static int match_launch(const float *d1, int k1, const int *n1_dev, const float *d2, int k2, const int *n2_dev, int pairs,
                         float th, int32_t *idx_dev, float *dist_dev, int32_t *count_dev, void *workspace_dev,
-                        hipStream_t st) {
-    char *ws = static_cast<char *>(workspace_dev);
-    int *idx1 = reinterpret_cast<int *>(ws);
-    float *r1 = reinterpret_cast<float *>(ws + (size_t)pairs * k1 * 4);
-    char *ws2 = ws + balf_align_up((size_t)pairs * k1 * 8, 256);
-    int *idx2 = reinterpret_cast<int *>(ws2);
-    float *r2 = reinterpret_cast<float *>(ws2 + (size_t)pairs * k2 * 4);
+                        size_t workspace_bytes, hipStream_t st) {
+    const MatchWs l = match_layout(pairs, k1, k2, workspace_dev);
+    if (workspace_bytes < l.total) return BALF_ERR_WORKSPACE;
     BALF_PROF(balf_prof::kMatchNN, st,
               (match_nn_kernel<<<dim3(balf_ceil_div(k1, 16), pairs), 64, 0, st>>>(d1, k1, n1_dev, (long)k1 * kD, d2, k2, n2_dev,
-                                                                                 (long)k2 * kD, idx1, r1, k1)));
+                                                                                 (long)k2 * kD, l.idx1, l.r1, k1)));
     BALF_LAUNCH_CHECK();
     BALF_PROF(balf_prof::kMatchNN, st,
               (match_nn_kernel<<<dim3(balf_ceil_div(k2, 16), pairs), 64, 0, st>>>(d2, k2, n2_dev, (long)k2 * kD, d1, k1, n1_dev,
-                                                                                 (long)k1 * kD, idx2, r2, k2)));
+                                                                                 (long)k1 * kD, l.idx2, l.r2, k2)));
     BALF_LAUNCH_CHECK();
     const int cap = k1 < k2 ? k1 : k2;
     BALF_PROF(balf_prof::kMatchMutual, st,
-              (match_mutual_kernel<<<pairs, 1024, 0, st>>>(idx1, r1, k1, n1_dev, k1, idx2, r2, k2, n2_dev, k2, th, idx_dev,
+              (match_mutual_kernel<<<pairs, 1024, 0, st>>>(l.idx1, l.r1, k1, n1_dev, k1, l.idx2, l.r2, k2, n2_dev, k2, th, idx_dev,
                                                             dist_dev, count_dev, cap)));
     BALF_LAUNCH_CHECK();
     return BALF_OK;
@@ -210,9 +216,8 @@ extern "C" int balf_match_smnn_batch(const float *desc1_dev, int k1, const int32
     if (!desc1_dev || !desc2_dev || !n1_dev || !n2_dev || !idx_dev || !dist_dev || !count_dev || !workspace_dev)
         return BALF_ERR_ARG;
     if (pairs <= 0 || pairs > 65535 || k1 <= 0 || k2 <= 0) return BALF_ERR_ARG;
-    if (workspace_bytes < balf_match_smnn_batch_workspace_bytes(pairs, k1, k2)) return BALF_ERR_WORKSPACE;
     return match_launch(desc1_dev, k1, n1_dev, desc2_dev, k2, n2_dev, pairs, th, idx_dev, dist_dev, count_dev, workspace_dev,
-                        static_cast<hipStream_t>(stream));
+                        workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
 extern "C" size_t balf_match_smnn_workspace_bytes(int n1, int n2) {
@@ -224,7 +229,6 @@ extern "C" int balf_match_smnn(const float *desc1_dev, int n1, const float *desc
                                size_t workspace_bytes, void *stream) {
     if (!desc1_dev || !desc2_dev || !idx_dev || !dist_dev || !count_dev || !workspace_dev || n1 <= 0 || n2 <= 0)
         return BALF_ERR_ARG;
-    if (workspace_bytes < balf_match_smnn_workspace_bytes(n1, n2)) return BALF_ERR_WORKSPACE;
     return match_launch(desc1_dev, n1, nullptr, desc2_dev, n2, nullptr, 1, th, idx_dev, dist_dev, count_dev, workspace_dev,
-                        static_cast<hipStream_t>(stream));
+                        workspace_bytes, static_cast<hipStream_t>(stream));
 }

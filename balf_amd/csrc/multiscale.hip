@@ -288,10 +288,7 @@ extern "C" int balf_pyramid_level(const void *src_dev, int src_kind, int channel
     a.ty = ty; a.fh = fh; a.fw = fw;
     a.dst = dst_dev;
     const size_t smem = (size_t)2 * fh * fw * sizeof(float);
-    if (smem > 48 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void *>(pyramid_level_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)smem) != hipSuccess)
-        return BALF_ERR_LAUNCH;
+    if (!balf_allow_dynamic_lds<pyramid_level_kernel>((int)smem)) return BALF_ERR_LAUNCH;
     hipStream_t st = (hipStream_t)stream;
     BALF_PROF(balf_prof::kMsPyramid, st,
               hipLaunchKernelGGL(pyramid_level_kernel, dim3(balf_ceil_div(a.wp, PYR_TX), balf_ceil_div(a.hp, ty), B),
@@ -319,10 +316,7 @@ extern "C" int balf_multiscale_merge(const int32_t *idx_dev, const float *score_
     a.cap = (int)(all < BALF_MAX_TOPK ? all : BALF_MAX_TOPK);
     a.npow2_cap = balf::next_pow2(a.cap);
     const size_t smem = (size_t)a.npow2_cap * 8;
-    if (smem > 48 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void *>(merge_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)smem) != hipSuccess)
-        return BALF_ERR_LAUNCH;
+    if (!balf_allow_dynamic_lds<merge_kernel>((int)smem)) return BALF_ERR_LAUNCH;
     hipStream_t st = (hipStream_t)stream;
     BALF_PROF(balf_prof::kMsMerge, st,
               hipLaunchKernelGGL(merge_kernel, dim3(B), dim3(MERGE_THREADS), smem, st, a));

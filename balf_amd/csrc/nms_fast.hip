@@ -35,8 +35,6 @@
 // Then the top-K / sort kernel of nms_topk.hip and the optional sub-pixel soft-argmax.
 #include <stdlib.h>
 
-#include <atomic>
-
 #include "block_ops.h"
 #include "common.h"
 #include "prof.h"
@@ -720,39 +718,33 @@ __global__ void subpixel_kernel(GreedyArgs a, const int32_t *idx, const int32_t 
 }
 
 struct Layout {
-    size_t zero_bytes;            // the counters (one line each) + counts [B]: cleared per call
-    size_t off_counts, off_chg, off_keptr, off_dead, dead_bytes, off_list, off_dlist, off_alive, off_kept, off_surv, total;
+    int *ctr, *counts, *chg, *keptr, *dead, *list, *dlist;
+    u64 *alive, *kept;
+    int2 *surv;
+    size_t zero_bytes, dead_bytes;     // ctr, counts, chg, keptr: cleared per call; dead: filled with ALIVE_FOREVER per call
+    size_t total;
 };
-Layout layout(int B, int H, int W) {
+Layout layout(int B, int H, int W, void *base = nullptr) {
     const size_t ntx = balf_ceil_div(W, TW), nty = balf_ceil_div(H, TH), tiles = ntx * nty;
-    Layout l;
-    l.off_counts = (size_t)4 * B * CTR_STRIDE * sizeof(int);
-    l.dead_bytes = balf_align_up((size_t)B * tiles * sizeof(int), 256);
-    l.off_chg = l.off_counts + balf_align_up((size_t)B * sizeof(int), 256);
-    l.off_keptr = l.off_chg + l.dead_bytes;
-    l.zero_bytes = l.off_keptr + l.dead_bytes;
-    l.off_dead = l.zero_bytes;
-    l.off_list = l.off_dead + l.dead_bytes;
-    l.off_dlist = l.off_list + balf_align_up((size_t)2 * B * tiles * sizeof(int), 256);
-    l.off_alive = l.off_dlist + balf_align_up((size_t)B * tiles * sizeof(int), 256);
-    const size_t map = balf_align_up((size_t)B * H * ntx * sizeof(u64), 256);
-    l.off_kept = l.off_alive + map;
-    l.off_surv = l.off_kept + map;
-    l.total = l.off_surv + (size_t)B * H * W * sizeof(int2);
+    const size_t per_tile = (size_t)B * tiles * sizeof(int), map = (size_t)B * H * ntx * sizeof(u64);
+    Layout l{};
+    WorkspaceCursor c{static_cast<char *>(base), 0};
+    // INVARIANT the two fills of balf_greedy_nms rest on: ctr, counts, chg, keptr come first and follow each other, so that
+    // [0, zero_bytes) is one fill; dead comes next, [zero_bytes, zero_bytes + dead_bytes), and is the other
+    l.ctr = c.take<int>((size_t)4 * B * CTR_STRIDE * sizeof(int));      // one 256-byte line per counter
+    l.counts = c.take<int>((size_t)B * sizeof(int));
+    l.chg = c.take<int>(per_tile);
+    l.keptr = c.take<int>(per_tile);
+    l.zero_bytes = c.used;
+    l.dead = c.take<int>(per_tile);
+    l.dead_bytes = c.used - l.zero_bytes;
+    l.list = c.take<int>(2 * per_tile);
+    l.dlist = c.take<int>(per_tile);
+    l.alive = c.take<u64>(map);
+    l.kept = c.take<u64>(map);
+    l.surv = c.take_exact<int2>((size_t)B * H * W * sizeof(int2));
+    l.total = c.used;
     return l;
-}
-
-// hipFuncSetAttribute is a driver round trip: once per kernel and device of the process (as allow_lds32 of detector.hip)
-template <auto Kernel>
-bool allow_lds(int bytes) {
-    static std::atomic<unsigned long long> done{0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
-    if (done.load(std::memory_order_acquire) >> dev & 1) return true;
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess)
-        return false;
-    done.fetch_or(1ull << dev, std::memory_order_release);
-    return true;
 }
 
 // rounds enqueued before the tail kernel; BALF_GREEDY_ROUNDS overrides it (read per call: the tests run the tail with 1)
@@ -781,28 +773,23 @@ extern "C" int balf_greedy_nms(const float *prob_dev, int B, int Hp, int Wp, int
     if (crop_y < 0 || crop_x < 0 || crop_y + H > Hp || crop_x + W > Wp) return BALF_ERR_SHAPE;
     if ((long)H * W > 0x7fffffffL) return BALF_ERR_SHAPE;
     if ((long)balf_ceil_div(W, TW) * balf_ceil_div(H, TH) * B > 0x7fffffffL) return BALF_ERR_SHAPE;
-    const Layout l = layout(B, H, W);
+    const Layout l = layout(B, H, W, workspace_dev);
     if (workspace_bytes < l.total) return BALF_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    char *w = static_cast<char *>(workspace_dev);
     const int ntx = balf_ceil_div(W, TW), nty = balf_ceil_div(H, TH), tiles = ntx * nty;
 
     GreedyArgs a{prob_dev, Hp, Wp, crop_y, crop_x, H, W, border, conf_thresh, dist_thresh, B, ntx, nty,
                  getenv("BALF_GREEDY_NOSKIP") != nullptr,
-                 reinterpret_cast<u64 *>(w + l.off_alive), reinterpret_cast<u64 *>(w + l.off_kept),
-                 reinterpret_cast<int *>(w + l.off_dead), reinterpret_cast<int *>(w + l.off_chg),
-                 reinterpret_cast<int *>(w + l.off_keptr), reinterpret_cast<int *>(w + l.off_list),
-                 reinterpret_cast<int *>(w + l.off_dlist), reinterpret_cast<int *>(w),
-                 reinterpret_cast<int2 *>(w + l.off_surv), reinterpret_cast<int *>(w + l.off_counts), total_dev};
+                 l.alive, l.kept, l.dead, l.chg, l.keptr, l.list, l.dlist, l.ctr, l.surv, l.counts, total_dev};
     // (fill kernels, not hipMemsetAsync: see balf_fill_u32 in common.h)
-    if (balf_fill_u32(w, 0u, l.zero_bytes / 4, st) != BALF_OK) return BALF_ERR_LAUNCH;
-    if (balf_fill_u32(w + l.off_dead, (unsigned)ALIVE_FOREVER, l.dead_bytes / 4, st) != BALF_OK) return BALF_ERR_LAUNCH;
+    if (balf_fill_u32(l.ctr, 0u, l.zero_bytes / 4, st) != BALF_OK) return BALF_ERR_LAUNCH;
+    if (balf_fill_u32(l.dead, (unsigned)ALIVE_FOREVER, l.dead_bytes / 4, st) != BALF_OK) return BALF_ERR_LAUNCH;
 
     constexpr int keep_lds = (int)sizeof(KeepLds), tail_lds = (int)(sizeof(KeepLds) + sizeof(KillLds) + sizeof(TailLds));
     static_assert(sizeof(KeepLds) % 16 == 0 && 2 * sizeof(KeepLds) <= 160 * 1024, "two window-mode workgroups per CU");
-    if (!allow_lds<greedy_keep_first_kernel<15>>(keep_lds) || !allow_lds<greedy_keep_first_kernel<-1>>(keep_lds) ||
-        !allow_lds<greedy_keep_window_kernel>(keep_lds) ||
-        !allow_lds<greedy_tail_kernel>(tail_lds))
+    if (!balf_allow_dynamic_lds<greedy_keep_first_kernel<15>>(keep_lds) ||
+        !balf_allow_dynamic_lds<greedy_keep_first_kernel<-1>>(keep_lds) ||
+        !balf_allow_dynamic_lds<greedy_keep_window_kernel>(keep_lds) || !balf_allow_dynamic_lds<greedy_tail_kernel>(tail_lds))
         return BALF_ERR_LAUNCH;
     // round 1 over every tile; rounds 2.. over the lists: launches sized for a full list that return at once on an empty one
     // (pairwise keep and kill: one wave per tile, the chip holds 8192 of them)

@@ -588,10 +588,7 @@ int balf_topk_select_launch(const int2 *surv, const int *counts, long cap, int B
                             unsigned thr_explicit, int32_t *taken_dev, int cum_budget) {
     const int npow2 = balf::next_pow2(K);
     const size_t smem = (size_t)npow2 * 8 + 256 * 4 + 8 * 4;
-    if (smem > 48 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void *>(topk_select_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-        return BALF_ERR_LAUNCH;
+    if (!balf_allow_dynamic_lds<topk_select_kernel>((int)smem)) return BALF_ERR_LAUNCH;
     BALF_PROF(balf_prof::kTopkSelect, st,
               hipLaunchKernelGGL(topk_select_kernel, dim3(B), dim3(SEL_THREADS), smem, st, surv, counts, cap, K, npow2,
                                  zero_fallback, thr_explicit, idx_dev, score_dev, count_dev, taken_dev, cum_budget));
@@ -608,11 +605,22 @@ extern "C" int balf_window_nms(const float *score_dev, int B, int H, int W, int 
     return launch_nms_tiles(a, B, (hipStream_t)stream);
 }
 
+// [B] survivor counters (their slice is cleared per call) + [B, H*W] (idx, score) survivor slots.  Only slots that receive a
+// survivor are ever touched; H*W is the exact worst case (a constant plateau).
+struct SelectWs { int *counts; size_t counts_bytes; int2 *surv; size_t total; };
+static SelectWs select_layout(int B, int H, int W, void *base = nullptr) {
+    WorkspaceCursor c{static_cast<char *>(base), 0};
+    SelectWs l{};
+    l.counts = c.take<int>((size_t)B * sizeof(int));
+    l.counts_bytes = c.used;
+    l.surv = c.take_exact<int2>((size_t)B * (size_t)H * (size_t)W * sizeof(int2));
+    l.total = c.used;
+    return l;
+}
+
 extern "C" size_t balf_nms_topk_workspace_bytes(int B, int H, int W, int K) {
     if (B <= 0 || H <= 0 || W <= 0 || K <= 0) return 0;
-    // [B] survivor counters (padded to 256 B) + [B, H*W] (idx, score) survivor slots.  Only slots that
-    // receive a survivor are ever touched; H*W is the exact worst case (a constant plateau).
-    return balf_align_up((size_t)B * sizeof(int), 256) + (size_t)B * (size_t)H * (size_t)W * sizeof(int2);
+    return select_layout(B, H, W).total;
 }
 
 namespace {
@@ -626,18 +634,15 @@ int nms_select(const float *prob_dev, int B, int Hp, int Wp, int crop_y, int cro
     if (nms_size < 1 || nms_size > BALF_MAX_NMS_SIZE || K > BALF_MAX_TOPK) return BALF_ERR_ARG;
     if (crop_y < 0 || crop_x < 0 || crop_y + H > Hp || crop_x + W > Wp) return BALF_ERR_SHAPE;
     if ((long)H * W > 0x7fffffffL || (!taken_dev && (long)K > (long)H * W)) return BALF_ERR_SHAPE;
-    if (workspace_bytes < balf_nms_topk_workspace_bytes(B, H, W, K)) return BALF_ERR_WORKSPACE;
+    const SelectWs l = select_layout(B, H, W, workspace_dev);
+    if (workspace_bytes < l.total) return BALF_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-
-    int *counts = reinterpret_cast<int *>(workspace_dev);
-    int2 *surv = reinterpret_cast<int2 *>(reinterpret_cast<char *>(workspace_dev) +
-                                          balf_align_up((size_t)B * sizeof(int), 256));
-    if (balf_fill_u32(counts, 0u, balf_align_up((size_t)B * sizeof(int), 256) / 4, st) != BALF_OK) return BALF_ERR_LAUNCH;
-    NmsArgs a{prob_dev, Hp, Wp, crop_y, crop_x, H, W, border, nms_size, surv, counts, (long)H * W, nullptr};
+    if (balf_fill_u32(l.counts, 0u, l.counts_bytes / 4, st) != BALF_OK) return BALF_ERR_LAUNCH;
+    NmsArgs a{prob_dev, Hp, Wp, crop_y, crop_x, H, W, border, nms_size, l.surv, l.counts, (long)H * W, nullptr};
     int rc = launch_nms_tiles(a, B, st);
     if (rc != BALF_OK) return rc;
 
-    return balf_topk_select_launch(surv, counts, (long)H * W, B, K, /*zero_fallback=*/1, idx_dev, score_dev, count_dev, st,
+    return balf_topk_select_launch(l.surv, l.counts, (long)H * W, B, K, /*zero_fallback=*/1, idx_dev, score_dev, count_dev, st,
                                    thr_explicit, taken_dev, cum_budget);
 }
 }  // namespace

@@ -263,6 +263,14 @@ int image_blocks(int patch) {
 
 bool sizes_ok(int P, int patch) { return P > 0 && P <= kMaxPairs && patch > 0 && patch <= kMaxPatch; }
 
+// the workspace: blk_max [P, image_blocks(patch)], the destination image's maximum per workgroup of the image kernel
+struct SynthWs { int *blk_max; size_t total; };
+SynthWs synth_layout(int P, int patch, void *base = nullptr) {
+    WorkspaceCursor c{static_cast<char *>(base), 0};
+    int *blk_max = c.take<int>((size_t)P * image_blocks(patch) * sizeof(int));
+    return {blk_max, c.used};
+}
+
 }  // namespace
 }  // namespace balf
 
@@ -270,7 +278,7 @@ using namespace balf;
 
 extern "C" size_t balf_synth_pairs_workspace_bytes(int P, int patch) {
     if (!sizes_ok(P, patch)) return 0;
-    return balf_align_up((size_t)P * image_blocks(patch) * sizeof(int), 256);
+    return synth_layout(P, patch).total;
 }
 
 extern "C" int balf_synth_pairs(const unsigned char *packed_dev, size_t packed_bytes, const long long *offsets_dev,
@@ -285,7 +293,8 @@ extern "C" int balf_synth_pairs(const unsigned char *packed_dev, size_t packed_b
         return BALF_ERR_ARG;
     if (P <= 0 || P > kMaxPairs || patch <= 0 || pts_total < 0 || top_k < 0) return BALF_ERR_ARG;
     if (patch > kMaxPatch) return BALF_ERR_SHAPE;
-    if (workspace_bytes < balf_synth_pairs_workspace_bytes(P, patch)) return BALF_ERR_WORKSPACE;
+    const SynthWs ws = synth_layout(P, patch, workspace_dev);
+    if (workspace_bytes < ws.total) return BALF_ERR_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     SynthArgs a{};
     a.packed = packed_dev;
@@ -309,7 +318,7 @@ extern "C" int balf_synth_pairs(const unsigned char *packed_dev, size_t packed_b
     a.heat_src = heat_src_dev;
     a.heat_dst = heat_dst_dev;
     a.dst_max = dst_max_dev;
-    a.blk_max = static_cast<int *>(workspace_dev);
+    a.blk_max = ws.blk_max;
     synth_image_kernel<<<dim3(a.nblk, 2, P), kImgThreads, 0, st>>>(a);
     BALF_LAUNCH_CHECK();
     synth_labels_kernel<<<P, kLblThreads, 0, st>>>(a);

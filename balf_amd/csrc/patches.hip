@@ -119,6 +119,25 @@ int pyramid_level(int h, int w, float scale) {
     return (int)l;
 }
 
+// The pyramid levels below the image, finest first: level l halves level l - 1 while that still holds a patch.  One walk for
+// the size query (base == nullptr) and the launches.  The total is 256 bytes more than the slices, as it always has
+// been (so it is never 0 for valid arguments); the slices themselves start at the workspace's first byte.
+constexpr int kMaxLevels = 32;               // (an int side halves 31 times at most)
+struct Pyramid { int levels; struct { float *out; int h, w; } lv[kMaxLevels]; size_t total; };
+Pyramid pyramid_layout(int B, int H, int W, float scale, void *base = nullptr) {
+    Pyramid p{};
+    const int level = pyramid_level(H, W, scale);
+    WorkspaceCursor c{static_cast<char *>(base), 0};
+    int h = H, w = W;
+    for (int l = 0; l < level && l < kMaxLevels && h >= kPS && w >= kPS; ++l) {
+        h /= 2; w /= 2;
+        p.lv[l] = {c.take<float>((size_t)B * h * w * 4), h, w};
+        p.levels = l + 1;
+    }
+    p.total = 256 + c.used;
+    return p;
+}
+
 }  // namespace
 }  // namespace balf
 
@@ -126,14 +145,7 @@ using namespace balf;
 
 extern "C" size_t balf_extract_patches_batch_workspace_bytes(int B, int H, int W, float scale) {
     if (B <= 0 || H <= 0 || W <= 0 || !(scale > 0.0f)) return 0;
-    const int level = pyramid_level(H, W, scale);
-    size_t bytes = 256;
-    int h = H, w = W;
-    for (int l = 0; l < level && h >= kPS && w >= kPS; ++l) {
-        h /= 2; w /= 2;
-        bytes += balf_align_up((size_t)B * h * w * 4, 256);
-    }
-    return bytes;
+    return pyramid_layout(B, H, W, scale).total;
 }
 
 extern "C" int balf_extract_patches_batch(const unsigned char *gray_dev, int B, int H, int W, const float *xy_dev,
@@ -141,15 +153,14 @@ extern "C" int balf_extract_patches_batch(const unsigned char *gray_dev, int B, 
                                           void *workspace_dev, size_t workspace_bytes, void *stream) {
     if (!gray_dev || !xy_dev || !patches_dev || !workspace_dev || B <= 0 || K <= 0 || !(scale > 0.0f)) return BALF_ERR_ARG;
     if (H < 2 || W < 2 || B > 65535) return BALF_ERR_SHAPE;
-    if (workspace_bytes < balf_extract_patches_batch_workspace_bytes(B, H, W, scale)) return BALF_ERR_WORKSPACE;
+    const Pyramid pyr = pyramid_layout(B, H, W, scale, workspace_dev);
+    if (workspace_bytes < pyr.total) return BALF_ERR_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const int level = pyramid_level(H, W, scale);
     const void *cur = gray_dev;
     int h = H, w = W, made = 0;
-    char *ws = static_cast<char *>(workspace_dev);
-    for (int l = 0; l < level && h >= kPS && w >= kPS; ++l) {
-        const int ho = h / 2, wo = w / 2;
-        float *out = reinterpret_cast<float *>(ws);
+    for (; made < pyr.levels; ++made) {
+        const int ho = pyr.lv[made].h, wo = pyr.lv[made].w;
+        float *out = pyr.lv[made].out;
         const dim3 grid(balf_ceil_div(wo, 16), balf_ceil_div(ho, 16), B);
         if (made == 0)
             BALF_PROF(balf_prof::kPatchPyr, st,
@@ -158,8 +169,7 @@ extern "C" int balf_extract_patches_batch(const unsigned char *gray_dev, int B, 
             BALF_PROF(balf_prof::kPatchPyr, st,
                       (pyrdown_kernel<float><<<grid, 256, 0, st>>>(static_cast<const float *>(cur), h, w, out, ho, wo)));
         BALF_LAUNCH_CHECK();
-        ws += balf_align_up((size_t)B * ho * wo * 4, 256);
-        cur = out; h = ho; w = wo; ++made;
+        cur = out; h = ho; w = wo;
     }
     const float ms0 = (float)((H < W ? H : W) - 1), msl = (float)((h < w ? h : w) - 1);
     SampleArgs a{cur, h, w, xy_dev, patches_dev, count_dev, K, scale / ms0 * msl,

@@ -45,15 +45,24 @@ __global__ void rcab_y_kernel(const float *r, float *y, size_t n) {
     if (i < n) y[i] = r[i] - y[i];
 }
 
+// the checks the three entry points share, in their order, and the forward's plan over a workspace that they only read
+int view_plan(int precision, const void *workspace_dev, size_t workspace_bytes, int B, int Hp, int Wp, Plan *pl) {
+    if (precision != BALF_PREC_FP32 && precision != BALF_PREC_FP16) return BALF_ERR_ARG;
+    if (Hp <= 0 || Wp <= 0 || Hp % 64 || Wp % 64) return BALF_ERR_SHAPE;
+    *pl = make_plan(B, Hp, Wp, const_cast<void *>(workspace_dev));
+    if (workspace_bytes < pl->total) return BALF_ERR_WORKSPACE;
+    return B > pl->mb ? BALF_ERR_ARG : BALF_OK;                  // only the last micro-batch of a forward is resident
+}
+
 // x0[pixel][o] = relu(sum_k x3[pixel][k] * W[o][k] + b[o]) from the resident stage-3 output with the training GEMM; on the split-f16
 // path x3 is de-fragmented into scratch first (pixels * 128 floats)
-int stage4_input(int precision, const char *ws, const Plan &pl, int B, int Hp, int Wp, const float *conv0_w, const float *conv0_b,
+int stage4_input(int precision, const Plan &pl, int B, int Hp, int Wp, const float *conv0_w, const float *conv0_b,
                  float *x0, float *scratch, hipStream_t st) {
     const int C3 = kC[2], C4 = kC[3];
     const size_t pix = (size_t)B * (Hp / 8) * (Wp / 8);
-    const float *x3 = reinterpret_cast<const float *>(ws + pl.off_X[2]);
+    const float *x3 = pl.X[2];
     if (precision == BALF_PREC_FP16) {
-        hipLaunchKernelGGL(view_frag_kernel, dim3((unsigned)((pix * C3 + 255) / 256)), dim3(256), 0, st, ws + pl.off_X[2], (long)pix, C3,
+        hipLaunchKernelGGL(view_frag_kernel, dim3((unsigned)((pix * C3 + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const char *>(pl.X[2]), (long)pix, C3,
                            kFmt32[3] ? 1 : 0, scratch);
         BALF_LAUNCH_CHECK();
         x3 = scratch;
@@ -76,18 +85,14 @@ extern "C" int balf_forward_stage_view(int precision, const void *workspace_dev,
                                        int stage, float *out_dev, void *stream) {
     using namespace balf;
     if (!workspace_dev || !out_dev || B <= 0 || stage < 1 || stage > 4) return BALF_ERR_ARG;
-    if (precision != BALF_PREC_FP32 && precision != BALF_PREC_FP16) return BALF_ERR_ARG;
-    if (Hp <= 0 || Wp <= 0 || Hp % 64 || Wp % 64) return BALF_ERR_SHAPE;
-    const Plan pl = make_plan(B, Hp, Wp);
-    if (workspace_bytes < pl.total) return BALF_ERR_WORKSPACE;
-    if (B > pl.mb) return BALF_ERR_ARG;                          // only the last micro-batch of a forward is resident
-    const char *ws = static_cast<const char *>(workspace_dev);
+    Plan pl;
+    if (const int rc = view_plan(precision, workspace_dev, workspace_bytes, B, Hp, Wp, &pl); rc != BALF_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     const size_t n = balf_forward_stage_view_numel(B, Hp, Wp, stage);
     const int C = kC[stage - 1];
     const unsigned blocks = (unsigned)((n + 255) / 256);
     if (stage < 4) {
-        const char *X = ws + pl.off_X[stage - 1];
+        const char *X = reinterpret_cast<const char *>(pl.X[stage - 1]);
         if (precision == BALF_PREC_FP32) {
             if (hipMemcpyAsync(out_dev, X, n * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return BALF_ERR_LAUNCH;
         } else {
@@ -95,9 +100,8 @@ extern "C" int balf_forward_stage_view(int precision, const void *workspace_dev,
         }
     } else {
         const long per_img = (long)(Hp / 8) * (Wp / 8);
-        hipLaunchKernelGGL(view_x2_kernel, dim3(blocks), dim3(256), 0, st, reinterpret_cast<const float *>(ws + pl.off_T),
-                           reinterpret_cast<const float *>(ws + pl.off_R), reinterpret_cast<const float *>(ws + pl.off_scale),
-                           per_img, (long)n, C, out_dev);
+        hipLaunchKernelGGL(view_x2_kernel, dim3(blocks), dim3(256), 0, st, pl.T, pl.R, pl.scale, per_img, (long)n, C,
+                           out_dev);
     }
     BALF_LAUNCH_CHECK();
     return BALF_OK;
@@ -110,17 +114,13 @@ extern "C" int balf_forward_rcab_inputs(int precision, const void *workspace_dev
                                         const float *conv0_w_dev, const float *conv0_b_dev, float *y_dev, float *r_dev, void *stream) {
     using namespace balf;
     if (!workspace_dev || !conv0_w_dev || !conv0_b_dev || !y_dev || !r_dev || B <= 0) return BALF_ERR_ARG;
-    if (precision != BALF_PREC_FP32 && precision != BALF_PREC_FP16) return BALF_ERR_ARG;
-    if (Hp <= 0 || Wp <= 0 || Hp % 64 || Wp % 64) return BALF_ERR_SHAPE;
-    const Plan pl = make_plan(B, Hp, Wp);
-    if (workspace_bytes < pl.total) return BALF_ERR_WORKSPACE;
-    if (B > pl.mb) return BALF_ERR_ARG;                          // only the last micro-batch of a forward is resident
-    const char *ws = static_cast<const char *>(workspace_dev);
+    Plan pl;
+    if (const int rc = view_plan(precision, workspace_dev, workspace_bytes, B, Hp, Wp, &pl); rc != BALF_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     const size_t n = (size_t)B * (Hp / 8) * (Wp / 8) * kC[3];
-    const int rc = stage4_input(precision, ws, pl, B, Hp, Wp, conv0_w_dev, conv0_b_dev, y_dev, r_dev, st);
+    const int rc = stage4_input(precision, pl, B, Hp, Wp, conv0_w_dev, conv0_b_dev, y_dev, r_dev, st);
     if (rc != BALF_OK) return rc;
-    if (hipMemcpyAsync(r_dev, ws + pl.off_R, n * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return BALF_ERR_LAUNCH;
+    if (hipMemcpyAsync(r_dev, pl.R, n * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return BALF_ERR_LAUNCH;
     hipLaunchKernelGGL(rcab_y_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, r_dev, y_dev, n);
     BALF_LAUNCH_CHECK();
     return BALF_OK;
@@ -132,12 +132,8 @@ extern "C" int balf_forward_gmlp_input(int precision, const void *workspace_dev,
                                        void *stream) {
     using namespace balf;
     if (!workspace_dev || !conv0_w_dev || !conv0_b_dev || !x0_dev || B <= 0) return BALF_ERR_ARG;
-    if (precision != BALF_PREC_FP32 && precision != BALF_PREC_FP16) return BALF_ERR_ARG;
     if (precision == BALF_PREC_FP16 && !scratch_dev) return BALF_ERR_ARG;
-    if (Hp <= 0 || Wp <= 0 || Hp % 64 || Wp % 64) return BALF_ERR_SHAPE;
-    const Plan pl = make_plan(B, Hp, Wp);
-    if (workspace_bytes < pl.total) return BALF_ERR_WORKSPACE;
-    if (B > pl.mb) return BALF_ERR_ARG;                          // only the last micro-batch of a forward is resident
-    return stage4_input(precision, static_cast<const char *>(workspace_dev), pl, B, Hp, Wp, conv0_w_dev, conv0_b_dev, x0_dev, scratch_dev,
-                        (hipStream_t)stream);
+    Plan pl;
+    if (const int rc = view_plan(precision, workspace_dev, workspace_bytes, B, Hp, Wp, &pl); rc != BALF_OK) return rc;
+    return stage4_input(precision, pl, B, Hp, Wp, conv0_w_dev, conv0_b_dev, x0_dev, scratch_dev, (hipStream_t)stream);
 }

@@ -256,9 +256,7 @@ extern "C" int balf_val_points(const float *prob_src_dev, int h_src, int w_src, 
         if (rc != BALF_OK) return rc;
     }
     const size_t smem = (size_t)a.npow2 * 8 + 256 * 4 + (4 + 1 + 16) * 4;
-    if (smem > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(val_select_kernel),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-        return BALF_ERR_LAUNCH;
+    if (!balf_allow_dynamic_lds<val_select_kernel>((int)smem)) return BALF_ERR_LAUNCH;
     val_select_kernel<<<dim3(P, 2), kSelThreads, smem, st>>>(a);
     BALF_LAUNCH_CHECK();
     return BALF_OK;
