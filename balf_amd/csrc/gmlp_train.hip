@@ -7,16 +7,18 @@
 // Kernels:
 //   * gemm_kernel (train_gemm.h) for every product along the channels; GELU is its epilogue EPI_BIAS_N_GELU, which also keeps the
 //     pre-activation, the shortcuts are EPI_BIAS_N_ADD.  The weight gradients go through the slab split and the float64 slab sum.
-//   * LayerNorm: ln_fwd_kernel / ln_bwd_kernel of train_ln.h for the layer's own norm; ln_fwd_s_kernel / ln_bwd_s_kernel here are the
-//     same row-per-wave arithmetic on a 256-channel half of a [N,512] row (a row stride and a column offset), the backward
-//     multiplied by the GELU derivative of the product that made its input, so that dH = dG * gelu'(H) costs no pass of its own.
+//   * LayerNorm: ln_fwd_kernel / ln_bwd_kernel of train_ln.h for all five norms.  The layer's own reads rows of x0 [N,256]
+//     (LN_DX_ADD, or LN_DX_NONE without dx0); the four of the branches read a 256-channel half of a [N,512] row (row stride 512,
+//     the column offset in the pointer), and their backward multiplies by the GELU derivative of the product that made its input
+//     (LN_DX_GELU, LN_DX_ADD_GELU), so that dH = dG * gelu'(H) costs no pass of its own.
 //   * the token mix.  A group's 64 tokens are 64 pixels that no single stride addresses: pixel(token) = base(group) +
 //     (token >> 3) * sy + (token & 7) * sx, with (sy, sx) = (Hc / 8 * Wc, Wc / 8) under the grid map and (Wc, 1) under the block
 //     map.  mix_fwd_kernel / mix_bwd_kernel take a workgroup per group, Wt in LDS, and gather the rows through that map: wave w
 //     owns channels 64 w .. 64 w + 63 of all 64 tokens, a lane loads four consecutive channels of a token's row straight into the
 //     B operands of four MFMA tiles (tile j, column li <-> channel 64 w + 4 li + j), so every activation is read once, by one
 //     lane, as a 16-byte load, and nothing is transposed through memory.  k, the token summed over, ascends.
-//   * column sums in float64 per workgroup of rows (col_sum_kernel, col_sum_s_kernel), added by partial_sum_kernel.
+//   * column sums in float64 per workgroup of rows (bias_grad: col_sum_kernel over 256 or 512 columns of a row of stride 256 or
+//     512), added by partial_sum_kernel.
 // dWt and dbt: each wave of mix_bwd_kernel sums dmix cn^T over its 64 channels in an MFMA chain per group and adds the groups of
 // its workgroup in float64 registers; the 4 * PW wave partials are added by partial_sum_kernel in one fixed order.
 // No floating-point atomics; every order is a function of (B, Hc, Wc) alone.
@@ -88,93 +90,6 @@ Layout make_layout(int B, int Hc, int Wc, char *saved, char *work, size_t *saved
     l.slab = ws.take<float>((size_t)l.px.S * kC2 * kC * sizeof(float));
     if (work_bytes) *work_bytes = ws.used;
     return l;
-}
-
-// ---- LayerNorm on a 256-channel half of a wider row ----------------------------------------------------------------------------
-// ln_fwd_kernel with a row stride: x[p * xs + c]
-__global__ __launch_bounds__(256) void ln_fwd_s_kernel(const float *x, size_t xs, const float *ln_g, const float *ln_b, int N,
-                                                       float *n_out, float *stat) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const gf4 gg = ld4(ln_g + 4 * lane), bb = ld4(ln_b + 4 * lane);
-#pragma unroll
-    for (int i = 0; i < kLnFwdPix / 4; ++i) {
-        const int p = blockIdx.x * kLnFwdPix + 4 * i + wave;   // (uniform in the wave)
-        if (p >= N) break;
-        const gf4 v = ld4(x + (size_t)p * xs + 4 * lane);
-        const float mean = chan_sum(v) * (1.0f / kC);
-        const gf4 d = v - mean;
-        const float var = chan_sum(d * d) * (1.0f / kC);
-        const float rstd = 1.0f / sqrtf(var + kLnEps);
-        const gf4 xh = d * rstd;
-        gf4 o;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = fmaf(xh[j], gg[j], bb[j]);
-        st4(n_out + (size_t)p * kC + 4 * lane, o);
-        if (lane == 0) { stat[2 * (size_t)p] = mean; stat[2 * (size_t)p + 1] = rstd; }
-    }
-}
-
-struct LnBwdSArgs {
-    int N, rows;
-    const float *dn, *stat, *ln_g;          // dn [N,256]
-    const float *x, *g, *h;                 // the LayerNorm's input, the shortcut's gradient (ADD_G), the pre-activation behind x
-    size_t xs, gs, hs, os;                  // their row strides, and out's
-    float *out;
-    double *part_g, *part_b;                // [PC][256] each
-};
-
-// ln_bwd_kernel on strided rows, its result times the GELU derivative:  out = (g + rstd * (u - mean_c u - xhat * mean_c(u * xhat)))
-// * gelu'(h), u = dn * ln_g, and the float64 partials of dln_g = sum dn * xhat, dln_b = sum dn
-template <bool ADD_G>
-__global__ __launch_bounds__(256) void ln_bwd_s_kernel(LnBwdSArgs a) {
-    __shared__ double s_part[2][4][kC];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r0 = blockIdx.x * a.rows, r1 = min(a.N, r0 + a.rows);
-    const gf4 gg = ld4(a.ln_g + 4 * lane);
-    double sg[4] = {0.0, 0.0, 0.0, 0.0}, sb[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int p = r0 + wave; p < r1; p += 4) {
-        const gf4 dn = ld4(a.dn + (size_t)p * kC + 4 * lane), v = ld4(a.x + (size_t)p * a.xs + 4 * lane);
-        const gf4 hv = ld4(a.h + (size_t)p * a.hs + 4 * lane);
-        const float mean = a.stat[2 * (size_t)p], rstd = a.stat[2 * (size_t)p + 1];
-        const gf4 d = v - mean;
-        const gf4 xh = d * rstd;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            sg[j] += (double)dn[j] * (double)xh[j];
-            sb[j] += (double)dn[j];
-        }
-        const gf4 u = dn * gg;
-        const float mu = chan_sum(u) * (1.0f / kC), mux = chan_sum(u * xh) * (1.0f / kC);
-        gf4 o;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = rstd * ((u[j] - mu) - xh[j] * mux);
-        if constexpr (ADD_G) o = ld4(a.g + (size_t)p * a.gs + 4 * lane) + o;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] *= gelu_grad(hv[j]);
-        st4(a.out + (size_t)p * a.os + 4 * lane, o);
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        s_part[0][wave][4 * lane + j] = sg[j];
-        s_part[1][wave][4 * lane + j] = sb[j];
-    }
-    __syncthreads();
-    const int c = threadIdx.x;
-    a.part_g[(size_t)blockIdx.x * kC + c] = ((s_part[0][0][c] + s_part[0][1][c]) + s_part[0][2][c]) + s_part[0][3][c];
-    a.part_b[(size_t)blockIdx.x * kC + c] = ((s_part[1][0][c] + s_part[1][1][c]) + s_part[1][2][c]) + s_part[1][3][c];
-}
-
-// col_sum_kernel on rows of stride xs and gridDim.y * 256 columns: part[block][column]
-__global__ __launch_bounds__(256) void col_sum_s_kernel(const float *x, size_t xs, int N, int rows, double *part) {
-    const int r0 = blockIdx.x * rows, r1 = min(N, r0 + rows), c = blockIdx.y * 256 + threadIdx.x;
-    double s[4] = {0.0, 0.0, 0.0, 0.0};                      // row r goes to chain (r - r0) % 4: four loads in flight
-    int r = r0;
-    for (; r + 4 <= r1; r += 4) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) s[i] += (double)x[(size_t)(r + i) * xs + c];
-    }
-    for (int i = 0; r < r1; ++r, ++i) s[i] += (double)x[(size_t)r * xs + c];
-    part[(size_t)blockIdx.x * (gridDim.y * 256) + c] = (s[0] + s[1]) + (s[2] + s[3]);
 }
 
 // ---- the token mix -------------------------------------------------------------------------------------------------------------
@@ -355,11 +270,11 @@ __global__ __launch_bounds__(256) void mix_bwd_kernel(MixArgs a) {
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------
-int check_sizes(int B, int Hc, int Wc) {
+// check_sizes, and in front of its pixel count the 8 x 8 grid and the 8 x 8 blocks (N is a multiple of 64 behind that rule)
+int check_gmlp_sizes(int B, int Hc, int Wc) {
     if (B < 1 || B > kMaxPairs || Hc < 1 || Wc < 1) return BALF_ERR_ARG;
-    if (Hc % 8 || Wc % 8) return BALF_ERR_SHAPE;            // the 8 x 8 grid and the 8 x 8 blocks
-    if ((long)B * (long)Hc * (long)Wc > (long)kTrainMaxN) return BALF_ERR_SHAPE;
-    return BALF_OK;
+    if (Hc % 8 || Wc % 8) return BALF_ERR_SHAPE;
+    return check_sizes(B, Hc, Wc);
 }
 
 MixArgs mix_args(const Layout &l, bool grid) {
@@ -389,14 +304,14 @@ int check_call(const float *const *params, const void *const *others, int n_othe
 using namespace balf;
 
 extern "C" size_t balf_gmlp_train_workspace_bytes(int B, int Hc, int Wc) {
-    if (check_sizes(B, Hc, Wc) != BALF_OK) return 0;
+    if (check_gmlp_sizes(B, Hc, Wc) != BALF_OK) return 0;
     size_t bytes = 0;
     make_layout(B, Hc, Wc, nullptr, nullptr, nullptr, &bytes);
     return bytes;
 }
 
 extern "C" size_t balf_gmlp_train_saved_bytes(int B, int Hc, int Wc) {
-    if (check_sizes(B, Hc, Wc) != BALF_OK) return 0;
+    if (check_gmlp_sizes(B, Hc, Wc) != BALF_OK) return 0;
     size_t bytes = 0;
     make_layout(B, Hc, Wc, nullptr, nullptr, &bytes, nullptr);
     return bytes;
@@ -405,53 +320,44 @@ extern "C" size_t balf_gmlp_train_saved_bytes(int B, int Hc, int Wc) {
 extern "C" int balf_gmlp_train_forward(const float *x0_dev, const float *const *params, int B, int Hc, int Wc, float *y_dev,
                                        void *saved_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
     const void *ptrs[] = {x0_dev, y_dev, saved_dev, workspace_dev};
-    int rc = check_call(params, ptrs, 4, ptrs, 4);
-    if (rc != BALF_OK) return rc;
-    rc = check_sizes(B, Hc, Wc);
-    if (rc != BALF_OK) return rc;
+    BALF_TRY(check_call(params, ptrs, 4, ptrs, 4));
+    BALF_TRY(check_gmlp_sizes(B, Hc, Wc));
     if (workspace_bytes < balf_gmlp_train_workspace_bytes(B, Hc, Wc)) return BALF_ERR_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const Layout l = make_layout(B, Hc, Wc, static_cast<char *>(saved_dev), static_cast<char *>(workspace_dev), nullptr, nullptr);
     const int N = l.px.N, ln_blocks = balf_ceil_div(N, kLnFwdPix);
     const float *const *P = params;
 
-    ln_fwd_kernel<<<ln_blocks, 256, 0, st>>>(x0_dev, P[0], P[1], N, l.n0, l.stat0);
+    ln_fwd_kernel<<<ln_blocks, 256, 0, st>>>(x0_dev, kC, P[0], P[1], N, l.n0, l.stat0);
     BALF_LAUNCH_CHECK();
-    pixel_gemm<EPI_BIAS_N_GELU, false>(l.n0, kC, kC, P[2], kC2, N, l.g0, kC2, P[3], l.h0, st);      // (u, v) = gelu(n0 W1^T + b1)
-    BALF_LAUNCH_CHECK();
+    BALF_TRY((pixel_gemm<EPI_BIAS_N_GELU, false>(l.n0, kC, kC, P[2], kC2, N, l.g0, kC2, P[3], l.h0, st)));      // (u, v) = gelu(n0 W1^T + b1)
     for (int k = 0; k < 2; ++k) {
         const Branch &b = l.br[k];
         const float *const *Q = P + 4 + kBranchParams * k;
         const float *z = l.g0 + kC * k;                                                              // u or v, row stride 512
-        ln_fwd_s_kernel<<<ln_blocks, 256, 0, st>>>(z, kC2, Q[0], Q[1], N, b.nb, b.statb);
+        ln_fwd_kernel<<<ln_blocks, 256, 0, st>>>(z, kC2, Q[0], Q[1], N, b.nb, b.statb);
         BALF_LAUNCH_CHECK();
-        pixel_gemm<EPI_BIAS_N_GELU, false>(b.nb, kC, kC, Q[2], kC2, N, b.gb, kC2, Q[3], b.hb, st);   // (a, c)
-        BALF_LAUNCH_CHECK();
-        ln_fwd_s_kernel<<<ln_blocks, 256, 0, st>>>(b.gb + kC, kC2, Q[4], Q[5], N, b.cn, b.statg);
+        BALF_TRY((pixel_gemm<EPI_BIAS_N_GELU, false>(b.nb, kC, kC, Q[2], kC2, N, b.gb, kC2, Q[3], b.hb, st)));   // (a, c)
+        ln_fwd_kernel<<<ln_blocks, 256, 0, st>>>(b.gb + kC, kC2, Q[4], Q[5], N, b.cn, b.statg);
         BALF_LAUNCH_CHECK();
         MixArgs m = mix_args(l, k == 0);
         m.wt = Q[6]; m.bt = Q[7]; m.cn = b.cn; m.gb = b.gb; m.mixp1 = b.mixp1; m.gated = b.gated;
         mix_fwd_kernel<<<l.groups, 256, 0, st>>>(m);
         BALF_LAUNCH_CHECK();
-        pixel_gemm<EPI_BIAS_N_ADD, false>(b.gated, kC, kC, Q[8], kC, N, l.cat + kC * k, kC2, Q[9], z, st);   // z' = z + gated Wb2^T + bb2
-        BALF_LAUNCH_CHECK();
+        BALF_TRY((pixel_gemm<EPI_BIAS_N_ADD, false>(b.gated, kC, kC, Q[8], kC, N, l.cat + kC * k, kC2, Q[9], z, st)));   // z' = z + gated Wb2^T + bb2
     }
-    pixel_gemm<EPI_BIAS_N_ADD, false>(l.cat, kC2, kC2, P[24], kC, N, y_dev, kC, P[25], x0_dev, st);  // y = cat W2^T + b2 + x0
-    BALF_LAUNCH_CHECK();
-    return BALF_OK;
+    return pixel_gemm<EPI_BIAS_N_ADD, false>(l.cat, kC2, kC2, P[24], kC, N, y_dev, kC, P[25], x0_dev, st);      // y = cat W2^T + b2 + x0
 }
 
 extern "C" int balf_gmlp_train_backward(const float *dy_dev, const float *x0_dev, const float *const *params, const void *saved_dev,
                                         int B, int Hc, int Wc, float *const *grads, float *dx0_dev, void *workspace_dev,
                                         size_t workspace_bytes, void *stream) {
     const void *ptrs[] = {dy_dev, x0_dev, saved_dev, workspace_dev, dx0_dev};
-    int rc = check_call(params, ptrs, 4, ptrs, 5);
-    if (rc != BALF_OK) return rc;
+    BALF_TRY(check_call(params, ptrs, 4, ptrs, 5));
     if (!grads) return BALF_ERR_ARG;
     for (int i = 0; i < kParams; ++i)
         if (!grads[i]) return BALF_ERR_ARG;
-    rc = check_sizes(B, Hc, Wc);
-    if (rc != BALF_OK) return rc;
+    BALF_TRY(check_gmlp_sizes(B, Hc, Wc));
     if (workspace_bytes < balf_gmlp_train_workspace_bytes(B, Hc, Wc)) return BALF_ERR_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const Layout l = make_layout(B, Hc, Wc, static_cast<char *>(const_cast<void *>(saved_dev)), static_cast<char *>(workspace_dev),
@@ -460,31 +366,23 @@ extern "C" int balf_gmlp_train_backward(const float *dy_dev, const float *x0_dev
     const float *const *P = params;
     float *const *G = grads;
     double *part0 = l.col_part, *part1 = l.col_part + (size_t)l.px.PC * kC2;
+    LnBwdArgs n{};                                                                                   // what the five LayerNorms share
+    n.part_g = part0; n.part_b = part1;
 
     // y = cat W2^T + b2 + x0:  db2 = sum dy,  dW2 = dy^T cat,  dcat = dy W2
-    col_sum_kernel<<<l.px.PC, kC, 0, st>>>(dy_dev, N, l.px.col_rows, part0);
-    BALF_LAUNCH_CHECK();
-    finish_cols(part0, kC, l.px.PC, G[25], st);
-    BALF_LAUNCH_CHECK();
-    weight_grad(dy_dev, kC, kC, l.cat, kC2, kC2, l.px, l.slab, G[24], st);
-    BALF_LAUNCH_CHECK();
-    pixel_gemm<EPI_STORE, true>(dy_dev, kC, kC, P[24], kC2, N, l.dcat, kC2, nullptr, nullptr, st);
-    BALF_LAUNCH_CHECK();
+    BALF_TRY(bias_grad(dy_dev, kC, kC, l.px, part0, G[25], st));
+    BALF_TRY(weight_grad(dy_dev, kC, kC, l.cat, kC2, kC2, l.px, l.slab, G[24], st));
+    BALF_TRY((pixel_gemm<EPI_STORE, true>(dy_dev, kC, kC, P[24], kC2, N, l.dcat, kC2, nullptr, nullptr, st)));
     for (int k = 0; k < 2; ++k) {
         const Branch &b = l.br[k];
         const float *const *Q = P + 4 + kBranchParams * k;
         float *const *D = G + 4 + kBranchParams * k;
         const float *dzo = l.dcat + kC * k;                                                          // the gradient at z', row stride 512
         // z' = z + gated Wb2^T + bb2
-        col_sum_s_kernel<<<dim3(l.px.PC, 1), 256, 0, st>>>(dzo, kC2, N, l.px.col_rows, part0);
-        BALF_LAUNCH_CHECK();
-        finish_cols(part0, kC, l.px.PC, D[9], st);
-        BALF_LAUNCH_CHECK();
-        weight_grad(dzo, kC2, kC, b.gated, kC, kC, l.px, l.slab, D[8], st);
-        BALF_LAUNCH_CHECK();
+        BALF_TRY(bias_grad(dzo, kC2, kC, l.px, part0, D[9], st));
+        BALF_TRY(weight_grad(dzo, kC2, kC, b.gated, kC, kC, l.px, l.slab, D[8], st));
         float *dgated = l.t0, *dcn = l.t1;
-        pixel_gemm<EPI_STORE, true>(dzo, kC2, kC, Q[8], kC, N, dgated, kC, nullptr, nullptr, st);
-        BALF_LAUNCH_CHECK();
+        BALF_TRY((pixel_gemm<EPI_STORE, true>(dzo, kC2, kC, Q[8], kC, N, dgated, kC, nullptr, nullptr, st)));
         // the gate and the token mix: dhb (a's half), dcn, dWt, dbt
         MixArgs m = mix_args(l, k == 0);
         m.wt = Q[6]; m.cn = b.cn; m.gb = b.gb; m.dgated = dgated; m.hb = b.hb; m.mixp1_in = b.mixp1; m.dhb = l.dhb; m.dcn = dcn;
@@ -496,59 +394,27 @@ extern "C" int balf_gmlp_train_backward(const float *dy_dev, const float *x0_dev
         partial_sum_kernel<<<kTok / 4, 256, 0, st>>>(l.mix_part + kTok * kTok, kTok, 4 * l.PW, 1, (size_t)kMixPart, D[7], nullptr);
         BALF_LAUNCH_CHECK();
         // the gating LayerNorm on c: dhb (c's half) = LN'(dcn) * gelu'(hb)
-        LnBwdSArgs s{};
-        s.N = N; s.rows = l.px.col_rows; s.dn = dcn; s.stat = b.statg; s.ln_g = Q[4];
-        s.x = b.gb + kC; s.xs = kC2; s.h = b.hb + kC; s.hs = kC2; s.out = l.dhb + kC; s.os = kC2;
-        s.part_g = part0; s.part_b = part1;
-        ln_bwd_s_kernel<false><<<l.px.PC, 256, 0, st>>>(s);
-        BALF_LAUNCH_CHECK();
-        finish_cols(part0, kC, l.px.PC, D[4], st);
-        BALF_LAUNCH_CHECK();
-        finish_cols(part1, kC, l.px.PC, D[5], st);
-        BALF_LAUNCH_CHECK();
+        n.dn = dcn; n.stat = b.statg; n.ln_g = Q[4];
+        n.x = b.gb + kC; n.xs = kC2; n.h = b.hb + kC; n.hs = kC2; n.out = l.dhb + kC; n.os = kC2;
+        BALF_TRY(ln_backward<LN_DX_GELU>(n, l.px, D[4], D[5], st));
         // hb = nb Wb1^T + bb1
-        col_sum_s_kernel<<<dim3(l.px.PC, 2), 256, 0, st>>>(l.dhb, kC2, N, l.px.col_rows, part0);
-        BALF_LAUNCH_CHECK();
-        finish_cols(part0, kC2, l.px.PC, D[3], st);
-        BALF_LAUNCH_CHECK();
-        weight_grad(l.dhb, kC2, kC2, b.nb, kC, kC, l.px, l.slab, D[2], st);
-        BALF_LAUNCH_CHECK();
+        BALF_TRY(bias_grad(l.dhb, kC2, kC2, l.px, part0, D[3], st));
+        BALF_TRY(weight_grad(l.dhb, kC2, kC2, b.nb, kC, kC, l.px, l.slab, D[2], st));
         float *dnb = l.t0;                                                                           // dgated is spent
-        pixel_gemm<EPI_STORE, true>(l.dhb, kC2, kC2, Q[2], kC, N, dnb, kC, nullptr, nullptr, st);
-        BALF_LAUNCH_CHECK();
+        BALF_TRY((pixel_gemm<EPI_STORE, true>(l.dhb, kC2, kC2, Q[2], kC, N, dnb, kC, nullptr, nullptr, st)));
         // the branch's LayerNorm on z and its shortcut: dh0 (this half) = (dzo + LN'(dnb)) * gelu'(h0)
-        s = LnBwdSArgs{};
-        s.N = N; s.rows = l.px.col_rows; s.dn = dnb; s.stat = b.statb; s.ln_g = Q[0];
-        s.x = l.g0 + kC * k; s.xs = kC2; s.g = dzo; s.gs = kC2; s.h = l.h0 + kC * k; s.hs = kC2; s.out = l.dh0 + kC * k; s.os = kC2;
-        s.part_g = part0; s.part_b = part1;
-        ln_bwd_s_kernel<true><<<l.px.PC, 256, 0, st>>>(s);
-        BALF_LAUNCH_CHECK();
-        finish_cols(part0, kC, l.px.PC, D[0], st);
-        BALF_LAUNCH_CHECK();
-        finish_cols(part1, kC, l.px.PC, D[1], st);
-        BALF_LAUNCH_CHECK();
+        n.dn = dnb; n.stat = b.statb; n.ln_g = Q[0];
+        n.x = l.g0 + kC * k; n.xs = kC2; n.g = dzo; n.gs = kC2; n.h = l.h0 + kC * k; n.hs = kC2; n.out = l.dh0 + kC * k; n.os = kC2;
+        BALF_TRY(ln_backward<LN_DX_ADD_GELU>(n, l.px, D[0], D[1], st));
     }
     // h0 = n0 W1^T + b1
-    col_sum_s_kernel<<<dim3(l.px.PC, 2), 256, 0, st>>>(l.dh0, kC2, N, l.px.col_rows, part0);
-    BALF_LAUNCH_CHECK();
-    finish_cols(part0, kC2, l.px.PC, G[3], st);
-    BALF_LAUNCH_CHECK();
-    weight_grad(l.dh0, kC2, kC2, l.n0, kC, kC, l.px, l.slab, G[2], st);
-    BALF_LAUNCH_CHECK();
+    BALF_TRY(bias_grad(l.dh0, kC2, kC2, l.px, part0, G[3], st));
+    BALF_TRY(weight_grad(l.dh0, kC2, kC2, l.n0, kC, kC, l.px, l.slab, G[2], st));
     float *dn0 = l.t0;
-    pixel_gemm<EPI_STORE, true>(l.dh0, kC2, kC2, P[2], kC, N, dn0, kC, nullptr, nullptr, st);
-    BALF_LAUNCH_CHECK();
+    BALF_TRY((pixel_gemm<EPI_STORE, true>(l.dh0, kC2, kC2, P[2], kC, N, dn0, kC, nullptr, nullptr, st)));
     // the layer's LayerNorm and its shortcut: dx0 = dy + LN'(dn0)
-    LnBwdArgs n{};
-    n.N = N; n.rows = l.px.col_rows; n.dn = dn0; n.y = x0_dev; n.stat = l.stat0; n.ln_g = P[0]; n.g = dy_dev; n.dy = dx0_dev;
-    n.part_g = part0; n.part_b = part1;
-    n.vec_g = true; n.vec_dy = true;
-    if (dx0_dev) ln_bwd_kernel<true><<<l.px.PC, 256, 0, st>>>(n);
-    else ln_bwd_kernel<false><<<l.px.PC, 256, 0, st>>>(n);
-    BALF_LAUNCH_CHECK();
-    finish_cols(part0, kC, l.px.PC, G[0], st);
-    BALF_LAUNCH_CHECK();
-    finish_cols(part1, kC, l.px.PC, G[1], st);
-    BALF_LAUNCH_CHECK();
-    return BALF_OK;
+    n.dn = dn0; n.stat = l.stat0; n.ln_g = P[0];
+    n.x = x0_dev; n.xs = kC; n.g = dy_dev; n.gs = kC; n.h = nullptr; n.out = dx0_dev; n.os = kC;
+    n.vec_g = true; n.vec_out = true;
+    return dx0_dev ? ln_backward<LN_DX_ADD>(n, l.px, G[0], G[1], st) : ln_backward<LN_DX_NONE>(n, l.px, G[0], G[1], st);
 }

@@ -2,8 +2,9 @@
 //   x2 -> down4.conv2 (Linear 256 -> 256) -> ReLU -> detector_head.dense (Linear 256 -> 65) -> BatchNorm2d with BATCH statistics,
 // and its backward from dlogits to the six parameter gradients and dx2.  N = B * Hc * Wc pixels.
 //
-// Two kinds of kernels:
-//   * gemm_kernel (train_gemm.h, shared with rcab_train.hip): ONE LDS-tiled GEMM on v_mfma_f32_16x16x4_f32 (exact fp32 fma chains, k ascending) for all six products.  A
+// Three kinds of kernels:
+//   * gemm_kernel (train_gemm.h, shared with the other training units, as are the argument rule check_sizes and the launch
+//     helpers): ONE LDS-tiled GEMM on v_mfma_f32_16x16x4_f32 (exact fp32 fma chains, k ascending) for all six products.  A
 //     workgroup of four waves owns a 64 x 64 tile of C[m][n] = sum_k A(m,k) * B(k,n), a wave a 32 x 32 quarter (2 x 2 MFMA tiles);
 //     K goes through LDS in steps of 16 with the next step's operands fetched into registers before the MFMAs of this one.  The
 //     operands are addressed by (row stride, k stride), so the same kernel reads x2 [N,256], the weights in PyTorch layout and the
@@ -13,8 +14,9 @@
 //     the workspace, and slab_sum_kernel adds the S slabs in float64 in slice order.
 //   * row kernels over the channel-major [65,N] arrays, a pixel on the lane: the batch statistics (float64 sums of z and z * z),
 //     dbeta / dgamma (float64), dz and its sum, each as per-workgroup partials [65][P] that a wave per channel adds in one fixed
-//     order (lanes strided over the partials, then the butterfly).  No floating-point atomics anywhere; every order is a function
-//     of N alone.
+//     order (lanes strided over the partials, then the butterfly).
+//   * db2, the column sums of the pixel-major dh [N,256]: bias_grad of train_gemm.h (col_sum_kernel, then partial_sum_kernel).
+// No floating-point atomics anywhere; every order is a function of N alone.
 // saved: a = relu(h) [N,256] (h > 0 exactly where a > 0), z channel-major [65,N], and mean / 1/sqrt(var + eps) as float64.
 #include "train_gemm.h"
 
@@ -196,14 +198,6 @@ __global__ __launch_bounds__(256) void normalize_kernel(NormArgs a) {
     }
 }
 
-int check_sizes(int B, int Hc, int Wc) {
-    if (B < 1 || B > kMaxPairs || Hc < 1 || Wc < 1) return BALF_ERR_ARG;
-    const long n = (long)B * (long)Hc * (long)Wc;
-    if (n > (long)kTrainMaxN) return BALF_ERR_SHAPE;
-    if (n < 2) return BALF_ERR_ARG;         // one value per channel has no variance
-    return BALF_OK;
-}
-
 }  // namespace
 }  // namespace balf
 
@@ -241,8 +235,7 @@ extern "C" int balf_head_train_forward(const float *x2_dev, const float *w2_dev,
     const Layout l = make_layout(N, static_cast<char *>(saved_dev), static_cast<char *>(workspace_dev), nullptr, nullptr);
 
     // a[pixel][out] = relu(sum_k x2[pixel][k] * W2[out][k] + b2[out])
-    pixel_gemm<EPI_BIAS_N_RELU, false>(x2_dev, kC, kC, w2_dev, kC, N, l.a, kC, b2_dev, nullptr, st);
-    BALF_LAUNCH_CHECK();
+    BALF_TRY((pixel_gemm<EPI_BIAS_N_RELU, false>(x2_dev, kC, kC, w2_dev, kC, N, l.a, kC, b2_dev, nullptr, st)));
     // zT[c][pixel] = sum_k Wd[c][k] * a[pixel][k] + bd[c]
     GemmArgs g{};
     g.A = wd_dev; g.a_sm = kC; g.a_sk = 1;
@@ -325,18 +318,10 @@ extern "C" int balf_head_train_backward(const float *dlogits_dev, const float *x
     g.C = l.dh; g.c_sm = kC; g.mask = l.a;
     launch_gemm<false, false, false, EPI_RELU_MASK>(g, st);
     BALF_LAUNCH_CHECK();
-    col_sum_kernel<<<l.px.PC, kC, 0, st>>>(l.dh, N, l.px.col_rows, l.b2_part);
-    BALF_LAUNCH_CHECK();
-    finish_cols(l.b2_part, kC, l.px.PC, db2_dev, st);
-    BALF_LAUNCH_CHECK();
+    BALF_TRY(bias_grad(l.dh, kC, kC, l.px, l.b2_part, db2_dev, st));
 
     // dW2[o][k] = sum_pixel dh[pixel][o] * x2[pixel][k], in S slices of the pixels
-    weight_grad(l.dh, kC, kC, x2_dev, kC, kC, l.px, l.slab_w2, dw2_dev, st);
-    BALF_LAUNCH_CHECK();
-    if (dx2_dev) {
-        // dx2[pixel][k] = sum_o dh[pixel][o] * W2[o][k]
-        pixel_gemm<EPI_STORE, true>(l.dh, kC, kC, w2_dev, kC, N, dx2_dev, kC, nullptr, nullptr, st);
-        BALF_LAUNCH_CHECK();
-    }
-    return BALF_OK;
+    BALF_TRY(weight_grad(l.dh, kC, kC, x2_dev, kC, kC, l.px, l.slab_w2, dw2_dev, st));
+    // dx2[pixel][k] = sum_o dh[pixel][o] * W2[o][k]
+    return dx2_dev ? pixel_gemm<EPI_STORE, true>(l.dh, kC, kC, w2_dev, kC, N, dx2_dev, kC, nullptr, nullptr, st) : BALF_OK;
 }

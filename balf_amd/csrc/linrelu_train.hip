@@ -5,9 +5,11 @@
 //
 //   * forward: gemm_kernel (train_gemm.h) with EPI_BIAS_N_RELU, launched as stage4_input of stage_view.hip launches it: the same
 //     MFMA chain, k ascending, and the same epilogue, hence the same bits.
-//   * backward: relu_mask_colsum_kernel, the one kernel of this file, makes gm = y > 0 ? g : 0 (the derivative from the OUTPUT, a
-//     select) and the float64 column sums of gm per workgroup in one pass; partial_sum_kernel adds them to db; dw = gm^T x goes
-//     through the K-sliced GEMM and slab_sum_kernel; dx = gm w is one EPI_STORE GEMM, not launched when dx is not wanted.
+//   * backward: relu_mask_colsum_kernel, the one kernel of this file (its 16-byte accesses are ld4 / st4 of train_gemm.h), makes
+//     gm = y > 0 ? g : 0 (the derivative from the OUTPUT, a select) and the float64 column sums of gm per workgroup in one pass:
+//     R rows in flight and four columns per thread, another shape than chain4_sum's, so it keeps its own loop; finish_cols adds
+//     them to db; dw = gm^T x goes through weight_grad (the K-sliced GEMM and slab_sum_kernel); dx = gm w is one EPI_STORE GEMM,
+//     not launched when dx is not wanted.
 // No floating-point atomics; every order is a function of (N, c_in) alone.
 // workspace: gm [N, c_out] float32, part [P][c_out] float64, slab [S][c_out][c_in] float32.
 #include "train_gemm.h"
@@ -33,9 +35,6 @@ Layout make_layout(int N, int c_in, char *work, size_t *work_bytes) {
     if (work_bytes) *work_bytes = ws.used;
     return l;
 }
-
-__device__ __forceinline__ gf4 ld4(const float *p) { return *reinterpret_cast<const gf4 *>(p); }
-__device__ __forceinline__ void st4(float *p, gf4 v) { *reinterpret_cast<gf4 *>(p) = v; }
 
 // rows [blockIdx.x * rows, ..) of g and y [N,C]: gm = y > 0 ? g : 0, stored, and part[block][c] = the float64 sum of gm's column
 // c over these rows.  A thread owns four consecutive columns (one 16-byte load of g and of y, one store of gm per row) of the rows
@@ -89,10 +88,8 @@ extern "C" int balf_linrelu_train_forward(const float *x_dev, const float *w_dev
     if (!x_dev || !w_dev || !b_dev || !y_dev || !width_ok(c_in)) return BALF_ERR_ARG;
     if (misaligned(x_dev, 15) || misaligned(w_dev, 15) || misaligned(b_dev, 15) || misaligned(y_dev, 15)) return BALF_ERR_ARG;
     if (N < 1 || N > kTrainMaxN) return BALF_ERR_SHAPE;
-    pixel_gemm<EPI_BIAS_N_RELU, false>(x_dev, c_in, c_in, w_dev, 2 * c_in, N, y_dev, 2 * c_in, b_dev, nullptr,
-                                       static_cast<hipStream_t>(stream));
-    BALF_LAUNCH_CHECK();
-    return BALF_OK;
+    return pixel_gemm<EPI_BIAS_N_RELU, false>(x_dev, c_in, c_in, w_dev, 2 * c_in, N, y_dev, 2 * c_in, b_dev, nullptr,
+                                              static_cast<hipStream_t>(stream));
 }
 
 extern "C" int balf_linrelu_train_backward(const float *g_dev, const float *y_dev, const float *x_dev, const float *w_dev, int N, int c_in,
@@ -113,15 +110,9 @@ extern "C" int balf_linrelu_train_backward(const float *g_dev, const float *y_de
     else if (c_out == 128) relu_mask_colsum_kernel<128><<<l.px.PC, 256, 0, st>>>(g_dev, y_dev, N, l.px.col_rows, l.gm, l.part);
     else relu_mask_colsum_kernel<256><<<l.px.PC, 256, 0, st>>>(g_dev, y_dev, N, l.px.col_rows, l.gm, l.part);
     BALF_LAUNCH_CHECK();
-    finish_cols(l.part, c_out, l.px.PC, db_dev, st);
-    BALF_LAUNCH_CHECK();
+    BALF_TRY(finish_cols(l.part, c_out, l.px.PC, db_dev, st));
     // dw[o][k] = fl32(sum_pixel gm[pixel][o] * x[pixel][k]) in S slices of the pixels, the slabs added in float64
-    weight_grad(l.gm, c_out, c_out, x_dev, c_in, c_in, l.px, l.slab, dw_dev, st);
-    BALF_LAUNCH_CHECK();
+    BALF_TRY(weight_grad(l.gm, c_out, c_out, x_dev, c_in, c_in, l.px, l.slab, dw_dev, st));
     // dx[pixel][k] = sum_o gm[pixel][o] * w[o][k]
-    if (dx_dev) {
-        pixel_gemm<EPI_STORE, true>(l.gm, c_out, c_out, w_dev, c_in, N, dx_dev, c_in, nullptr, nullptr, st);
-        BALF_LAUNCH_CHECK();
-    }
-    return BALF_OK;
+    return dx_dev ? pixel_gemm<EPI_STORE, true>(l.gm, c_out, c_out, w_dev, c_in, N, dx_dev, c_in, nullptr, nullptr, st) : BALF_OK;
 }

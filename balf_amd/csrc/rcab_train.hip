@@ -5,10 +5,12 @@
 // Four kinds of kernels:
 //   * gemm_kernel (train_gemm.h, with its launch helpers) for the six 256 x 256 products; dwc1 / dwc2 through the slab split
 //     and the float64 slab sum.
-//   * LayerNorm row kernels (train_ln.h, shared with gmlp_train.hip): a pixel's 256 channels on one wave.
-//   * column kernels, a channel per thread over a block of pixel rows, float64 partial sums per workgroup: over the rows of ONE
-//     image (img_sum_kernel: the SE mean m_i and ds_i = sum g t; the grid is (row blocks of an image, image), so no block ever
-//     holds rows of two images, wherever an image starts), and over all rows (dt_kernel, col_sum_kernel, ln_bwd_kernel).
+//   * LayerNorm row kernels (train_ln.h, shared with gmlp_train.hip): a pixel's 256 channels on one wave; the backward is
+//     LN_DX_ADD (dy = dx2 + LN'(dn), dx2 and dy at any 4-byte alignment) or LN_DX_NONE when dy is not asked for.
+//   * column kernels, a channel per thread over a block of pixel rows, float64 partial sums per workgroup, each a term of its own
+//     inside chain4_sum (train_gemm.h): over the rows of ONE image (img_sum_kernel: the SE mean m_i and ds_i = sum g t; the grid is
+//     (row blocks of an image, image), so no block ever holds rows of two images, wherever an image starts), and over all rows
+//     (dt_kernel; col_sum_kernel through bias_grad; ln_bwd_kernel, which has its own row walk).
 //   * the squeeze-excite arithmetic in float64: se_fwd_kernel / se_bwd_kernel, a workgroup per image, and se_wgrad_kernel, a
 //     thread per element of dws0 / dws2 / dbs0 / dbs2 that walks the images in image order.
 // No floating-point atomics; every order is a function of (B, Hc, Wc) alone.
@@ -77,18 +79,10 @@ __global__ __launch_bounds__(kC) void img_sum_kernel(const float *x, const float
     const int img = blockIdx.y;
     const int o0 = blockIdx.x * rows, o1 = min(hw, o0 + rows);
     const size_t base = (size_t)img * (size_t)hw;
-    double s[4] = {0.0, 0.0, 0.0, 0.0};                      // row o goes to chain (o - o0) % 4: four loads in flight
-    auto term = [&](int o) {
+    part[((size_t)img * gridDim.x + blockIdx.x) * kC + threadIdx.x] = chain4_sum(o0, o1, [&](int o) {
         const size_t at = (base + o) * kC + threadIdx.x;
         return PROD ? (double)x[at] * (double)w[at] : (double)x[at];
-    };
-    int o = o0;
-    for (; o + 4 <= o1; o += 4) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) s[i] += term(o + i);
-    }
-    for (int i = 0; o < o1; ++o, ++i) s[i] += term(o);
-    part[((size_t)img * gridDim.x + blockIdx.x) * kC + threadIdx.x] = (s[0] + s[1]) + (s[2] + s[3]);
+    });
 }
 
 struct SeArgs {
@@ -207,28 +201,12 @@ __global__ __launch_bounds__(256) void scale_add_kernel(const float *t, const fl
 __global__ __launch_bounds__(kC) void dt_kernel(const float *g, const float *sf, const float *dmh, int N, int hw, int rows, float *dt,
                                                 double *part) {
     const int r0 = blockIdx.x * rows, r1 = min(N, r0 + rows), c = threadIdx.x;
-    double s[4] = {0.0, 0.0, 0.0, 0.0};                      // row r goes to chain (r - r0) % 4
-    auto one = [&](int r) {
+    part[(size_t)blockIdx.x * kC + c] = chain4_sum(r0, r1, [&](int r) {
         const size_t at = (size_t)r * kC + c, im = (size_t)(r / hw) * kC + c;
         const float v = fmaf(g[at], sf[im], dmh[im]);
         dt[at] = v;
         return (double)v;
-    };
-    int r = r0;
-    for (; r + 4 <= r1; r += 4) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) s[i] += one(r + i);
-    }
-    for (int i = 0; r < r1; ++r, ++i) s[i] += one(r);
-    part[(size_t)blockIdx.x * kC + c] = (s[0] + s[1]) + (s[2] + s[3]);
-}
-
-int check_sizes(int B, int Hc, int Wc) {
-    if (B < 1 || B > kMaxPairs || Hc < 1 || Wc < 1) return BALF_ERR_ARG;
-    const long n = (long)B * (long)Hc * (long)Wc;
-    if (n > (long)kTrainMaxN) return BALF_ERR_SHAPE;
-    if (n < 2) return BALF_ERR_ARG;         // the limits of the head, whose input this block produces
-    return BALF_OK;
+    });
 }
 
 }  // namespace
@@ -269,12 +247,10 @@ extern "C" int balf_rcab_train_forward(const float *y_dev, const float *r_dev, c
     const int hw = Hc * Wc, N = B * hw;
     const Layout l = make_layout(B, hw, static_cast<char *>(saved_dev), static_cast<char *>(workspace_dev), nullptr, nullptr);
 
-    ln_fwd_kernel<<<balf_ceil_div(N, kLnFwdPix), 256, 0, st>>>(y_dev, ln_g_dev, ln_b_dev, N, l.n, l.stat);
+    ln_fwd_kernel<<<balf_ceil_div(N, kLnFwdPix), 256, 0, st>>>(y_dev, kC, ln_g_dev, ln_b_dev, N, l.n, l.stat);
     BALF_LAUNCH_CHECK();
-    pixel_gemm<EPI_BIAS_N_LRELU, false>(l.n, kC, kC, wc1_dev, kC, N, l.a, kC, bc1_dev, nullptr, st);   // a = lrelu(n wc1^T + bc1)
-    BALF_LAUNCH_CHECK();
-    pixel_gemm<EPI_BIAS_N, false>(l.a, kC, kC, wc2_dev, kC, N, l.t, kC, bc2_dev, nullptr, st);         // t = a wc2^T + bc2
-    BALF_LAUNCH_CHECK();
+    BALF_TRY((pixel_gemm<EPI_BIAS_N_LRELU, false>(l.n, kC, kC, wc1_dev, kC, N, l.a, kC, bc1_dev, nullptr, st)));   // a = lrelu(n wc1^T + bc1)
+    BALF_TRY((pixel_gemm<EPI_BIAS_N, false>(l.a, kC, kC, wc2_dev, kC, N, l.t, kC, bc2_dev, nullptr, st)));         // t = a wc2^T + bc2
     img_sum_kernel<false><<<dim3(l.PI, B), kC, 0, st>>>(l.t, nullptr, hw, l.img_rows, l.img_part);
     BALF_LAUNCH_CHECK();
     SeArgs s{};
@@ -325,33 +301,18 @@ extern "C" int balf_rcab_train_backward(const float *dx2_dev, const float *y_dev
     // dt = g s_i + dm_i / hw, dbc2 = sum dt, dwc2 = dt^T a
     dt_kernel<<<l.px.PC, kC, 0, st>>>(dx2_dev, l.sf, l.dmh, N, hw, l.px.col_rows, l.dt, part0);
     BALF_LAUNCH_CHECK();
-    finish_cols(part0, kC, l.px.PC, dbc2_dev, st);
-    BALF_LAUNCH_CHECK();
-    weight_grad(l.dt, kC, kC, l.a, kC, kC, l.px, l.slab, dwc2_dev, st);
-    BALF_LAUNCH_CHECK();
+    BALF_TRY(finish_cols(part0, kC, l.px.PC, dbc2_dev, st));
+    BALF_TRY(weight_grad(l.dt, kC, kC, l.a, kC, kC, l.px, l.slab, dwc2_dev, st));
     // dh = (dt wc2) * (a > 0 ? 1 : 0.2), dbc1 = sum dh, dwc1 = dh^T n
-    pixel_gemm<EPI_LRELU_MASK, true>(l.dt, kC, kC, wc2_dev, kC, N, l.dh, kC, nullptr, l.a, st);
-    BALF_LAUNCH_CHECK();
-    col_sum_kernel<<<l.px.PC, kC, 0, st>>>(l.dh, N, l.px.col_rows, part0);
-    BALF_LAUNCH_CHECK();
-    finish_cols(part0, kC, l.px.PC, dbc1_dev, st);
-    BALF_LAUNCH_CHECK();
-    weight_grad(l.dh, kC, kC, l.n, kC, kC, l.px, l.slab, dwc1_dev, st);
-    BALF_LAUNCH_CHECK();
-    // dn = dh wc1 (over dt, which nobody reads any more), then the LayerNorm: dln_g, dln_b and, if asked for, dy
+    BALF_TRY((pixel_gemm<EPI_LRELU_MASK, true>(l.dt, kC, kC, wc2_dev, kC, N, l.dh, kC, nullptr, l.a, st)));
+    BALF_TRY(bias_grad(l.dh, kC, kC, l.px, part0, dbc1_dev, st));
+    BALF_TRY(weight_grad(l.dh, kC, kC, l.n, kC, kC, l.px, l.slab, dwc1_dev, st));
+    // dn = dh wc1 (over dt, which nobody reads any more), then the LayerNorm: dln_g, dln_b and, if asked for, dy = dx2 + LN'(dn)
     float *dn = l.dt;
-    pixel_gemm<EPI_STORE, true>(l.dh, kC, kC, wc1_dev, kC, N, dn, kC, nullptr, nullptr, st);
-    BALF_LAUNCH_CHECK();
+    BALF_TRY((pixel_gemm<EPI_STORE, true>(l.dh, kC, kC, wc1_dev, kC, N, dn, kC, nullptr, nullptr, st)));
     LnBwdArgs b{};
-    b.N = N; b.rows = l.px.col_rows; b.dn = dn; b.y = y_dev; b.stat = l.stat; b.ln_g = ln_g_dev; b.g = dx2_dev; b.dy = dy_dev;
+    b.dn = dn; b.stat = l.stat; b.ln_g = ln_g_dev; b.x = y_dev; b.xs = kC; b.g = dx2_dev; b.gs = kC; b.out = dy_dev; b.os = kC;
     b.part_g = part0; b.part_b = part1;
-    b.vec_g = !misaligned(dx2_dev, 15); b.vec_dy = !misaligned(dy_dev, 15);
-    if (dy_dev) ln_bwd_kernel<true><<<l.px.PC, 256, 0, st>>>(b);
-    else ln_bwd_kernel<false><<<l.px.PC, 256, 0, st>>>(b);
-    BALF_LAUNCH_CHECK();
-    finish_cols(part0, kC, l.px.PC, dln_g_dev, st);
-    BALF_LAUNCH_CHECK();
-    finish_cols(part1, kC, l.px.PC, dln_b_dev, st);
-    BALF_LAUNCH_CHECK();
-    return BALF_OK;
+    b.vec_g = !misaligned(dx2_dev, 15); b.vec_out = !misaligned(dy_dev, 15);
+    return dy_dev ? ln_backward<LN_DX_ADD>(b, l.px, dln_g_dev, dln_b_dev, st) : ln_backward<LN_DX_NONE>(b, l.px, dln_g_dev, dln_b_dev, st);
 }

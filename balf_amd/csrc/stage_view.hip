@@ -67,9 +67,7 @@ int stage4_input(int precision, const Plan &pl, int B, int Hp, int Wp, const flo
         BALF_LAUNCH_CHECK();
         x3 = scratch;
     }
-    pixel_gemm<EPI_BIAS_N_RELU, false>(x3, C3, C3, conv0_w, C4, (int)pix, x0, C4, conv0_b, nullptr, st);
-    BALF_LAUNCH_CHECK();
-    return BALF_OK;
+    return pixel_gemm<EPI_BIAS_N_RELU, false>(x3, C3, C3, conv0_w, C4, (int)pix, x0, C4, conv0_b, nullptr, st);
 }
 
 }  // namespace

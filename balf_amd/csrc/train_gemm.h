@@ -6,10 +6,15 @@
 //     by (row stride, k stride); whatever lies outside M, Nn or the K range is never loaded and enters the tile as 0, and a
 //     16-row MFMA tile wholly outside is skipped.  A weight gradient sums over the pixels: its K range is cut into S slices
 //     (rows_per_slice(N)), slice s writes slab s of the workspace, and slab_sum_kernel adds the S slabs in float64 in slice order.
-//   * the float64 sums over pixels: col_sum_kernel (per-workgroup partials of the columns of a [N,256] matrix) and
-//     partial_sum_kernel (a wave per output adds the partials in one fixed order: lanes strided, then the butterfly).
-//   * the host side of both: PixelSlices, the slice geometry of N pixels that every unit's Layout holds, and the launch helpers
-//     pixel_gemm / weight_grad / finish_cols, which fill a GemmArgs for the products along the channels of pixel-major matrices.
+//   * the float64 sums over pixels: chain4_sum, the ONE spelling of a thread's sum over a block of rows (four chains, row r on
+//     chain (r - r0) % 4), which col_sum_kernel (per-workgroup partials of the columns of a strided matrix, 256 columns per grid y)
+//     and the RCAB's img_sum_kernel / dt_kernel call with their own terms, and partial_sum_kernel (a wave per output adds the
+//     partials in one fixed order: lanes strided, then the butterfly).
+//   * ld4 / st4, the 16-byte accesses of four consecutive channels, with the overloads that fall back to four 4-byte accesses.
+//   * the host side: PixelSlices, the slice geometry of N pixels that every unit's Layout holds; check_sizes, the limits of
+//     (B, Hc, Wc); and the launch helpers pixel_gemm / weight_grad / finish_cols / bias_grad, which fill a GemmArgs for the
+//     products along the channels of pixel-major matrices and launch the column sums.  Every helper checks each of its launches
+//     and returns BALF_OK or BALF_ERR_LAUNCH; a caller passes that on with BALF_TRY.
 // An epilogue is a template value: a new one adds an instantiation and leaves the code of the others as it was.
 #pragma once
 #include "block_ops.h"
@@ -24,7 +29,34 @@ constexpr int kTile = 64, kTK = 16, kPitch = kTile + 4;
 constexpr int kMaxSlices = 64;              // slabs of a weight gradient
 constexpr int kTrainMaxN = 1 << 24;         // pixels: up to 2^32 elements in a [N,256] matrix, indexed in size_t
 
+// pass on the status of a check or of a launch helper unless it is BALF_OK
+#define BALF_TRY(call)                            \
+    do {                                          \
+        const int balf_try_rc = (call);           \
+        if (balf_try_rc != BALF_OK)               \
+            return balf_try_rc;                   \
+    } while (0)
+
 bool misaligned(const void *p, unsigned mask) { return ((uintptr_t)p & mask) != 0; }
+
+// B images of Hc x Wc cells, N = B * Hc * Wc pixels: the limits of the head, and of the RCAB, whose output is the head's input
+int check_sizes(int B, int Hc, int Wc) {
+    if (B < 1 || B > kMaxPairs || Hc < 1 || Wc < 1) return BALF_ERR_ARG;
+    const long n = (long)B * (long)Hc * (long)Wc;
+    if (n > (long)kTrainMaxN) return BALF_ERR_SHAPE;
+    if (n < 2) return BALF_ERR_ARG;         // one value per channel has no variance
+    return BALF_OK;
+}
+
+__device__ __forceinline__ gf4 ld4(const float *p) { return *reinterpret_cast<const gf4 *>(p); }
+__device__ __forceinline__ void st4(float *p, gf4 v) { *reinterpret_cast<gf4 *>(p) = v; }
+// (vec, uniform: the array is 16-byte aligned; else four 4-byte accesses)
+__device__ __forceinline__ gf4 ld4(const float *p, bool vec) { return vec ? ld4(p) : gf4{p[0], p[1], p[2], p[3]}; }
+__device__ __forceinline__ void st4(float *p, gf4 v, bool vec) {
+    if (vec) { st4(p, v); return; }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) p[j] = v[j];
+}
 
 // rows (pixels) per K slice of dW2 / dWd: 256, or the multiple of 256 that keeps the slices at kMaxSlices
 int rows_per_slice(int N) {
@@ -188,24 +220,36 @@ __global__ __launch_bounds__(256) void partial_sum_kernel(const double *part, in
     }
 }
 
-// float64 column sums of rows [blockIdx.x * rows, ...) of a [N,256] matrix, a column per thread
-__global__ __launch_bounds__(kTrainC) void col_sum_kernel(const float *x, int N, int rows, double *part) {
-    const int r0 = blockIdx.x * rows, r1 = min(N, r0 + rows);
-    double s[4] = {0.0, 0.0, 0.0, 0.0};                      // row r goes to chain (r - r0) % 4: four loads in flight
+// where row r >= 0 of a matrix of row stride s begins, in elements: one 32 x 32 -> 64-bit product, which a row loop waits for
+// before it can issue the row's load (a stride held in 64 bits costs three products and their sums)
+__device__ __forceinline__ size_t row_at(int r, unsigned s) { return (size_t)(unsigned)r * s; }
+
+// the float64 sum of term(r) over rows [r0, r1): row r goes to chain (r - r0) % 4, four rows (loads) in flight, and the chains are
+// added as (s0 + s1) + (s2 + s3)
+template <typename Term>
+__device__ __forceinline__ double chain4_sum(int r0, int r1, Term term) {
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
     int r = r0;
     for (; r + 4 <= r1; r += 4) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) s[i] += (double)x[(size_t)(r + i) * kTrainC + threadIdx.x];
+        for (int i = 0; i < 4; ++i) s[i] += term(r + i);
     }
-    for (int i = 0; r < r1; ++r, ++i) s[i] += (double)x[(size_t)r * kTrainC + threadIdx.x];
-    part[(size_t)blockIdx.x * kTrainC + threadIdx.x] = (s[0] + s[1]) + (s[2] + s[3]);
+    for (int i = 0; r < r1; ++r, ++i) s[i] += term(r);
+    return (s[0] + s[1]) + (s[2] + s[3]);
+}
+
+// float64 column sums of rows [blockIdx.x * rows, ...) of a matrix of row stride xs and gridDim.y * 256 columns, a column per
+// thread: part[block][column]
+__global__ __launch_bounds__(256) void col_sum_kernel(const float *x, unsigned xs, int N, int rows, double *part) {
+    const int r0 = blockIdx.x * rows, r1 = min(N, r0 + rows), c = blockIdx.y * 256 + threadIdx.x;
+    part[(size_t)blockIdx.x * (gridDim.y * 256) + c] = chain4_sum(r0, r1, [&](int r) { return (double)x[row_at(r, xs) + c]; });
 }
 
 // ---- the launches along the channels -----------------------------------------------------------------------------------------
 // C[pixel][n] = epilogue(sum_k A[pixel * lda + k] * W(k, n)), n < Nn, k < K: TRANSPOSED = false reads W[n][k] (x W^T), true reads
 // W[k][n] (x W)
 template <int EPI, bool TRANSPOSED>
-void pixel_gemm(const float *A, size_t lda, int K, const float *W, int Nn, int N, float *C, size_t ldc, const float *bias,
+int pixel_gemm(const float *A, size_t lda, int K, const float *W, int Nn, int N, float *C, size_t ldc, const float *bias,
                 const float *mask, hipStream_t st) {
     GemmArgs g{};
     g.A = A; g.a_sm = lda; g.a_sk = 1;
@@ -213,13 +257,14 @@ void pixel_gemm(const float *A, size_t lda, int K, const float *W, int Nn, int N
     g.M = N; g.Nn = Nn; g.K = K; g.k_rows = K;
     g.C = C; g.c_sm = ldc; g.bias = bias; g.mask = mask;
     launch_gemm<true, !TRANSPOSED, false, EPI>(g, st);
+    BALF_LAUNCH_CHECK();
+    return BALF_OK;
 }
 
 // out[o][k] = fl32(sum_pixel D[pixel * ldd + o] * X[pixel * ldx + k]), o < M, k < Nn, in p.S slices of the pixels through slab
-// [p.S][M * Nn], the slabs added in float64.  Two launches: the caller's launch check after it covers both, hipGetLastError
-// keeps an error until it is read.  (A template only so that a unit that never calls it instantiates no GEMM for it.)
+// [p.S][M * Nn], the slabs added in float64.  (A template only so that a unit that never calls it instantiates no GEMM for it.)
 template <typename = void>
-void weight_grad(const float *D, size_t ldd, int M, const float *X, size_t ldx, int Nn, const PixelSlices &p, float *slab, float *out,
+int weight_grad(const float *D, size_t ldd, int M, const float *X, size_t ldx, int Nn, const PixelSlices &p, float *slab, float *out,
                  hipStream_t st) {
     GemmArgs g{};
     g.A = D; g.a_sm = 1; g.a_sk = ldd;
@@ -227,12 +272,24 @@ void weight_grad(const float *D, size_t ldd, int M, const float *X, size_t ldx, 
     g.M = M; g.Nn = Nn; g.K = p.N; g.k_rows = p.rows;
     g.C = slab; g.c_sm = Nn; g.c_sz = (size_t)M * Nn;
     launch_gemm<false, false, false, EPI_STORE>(g, st);
+    BALF_LAUNCH_CHECK();
     slab_sum_kernel<<<M * Nn / 256, 256, 0, st>>>(slab, p.S, M * Nn, out);
+    BALF_LAUNCH_CHECK();
+    return BALF_OK;
 }
 
 // out[c] = fl32(sum over the P float64 partials part[p][c] of column c), c < cols
-void finish_cols(const double *part, int cols, int P, float *out, hipStream_t st) {
+int finish_cols(const double *part, int cols, int P, float *out, hipStream_t st) {
     partial_sum_kernel<<<cols / 4, 256, 0, st>>>(part, cols, P, 1, (size_t)cols, out, nullptr);
+    BALF_LAUNCH_CHECK();
+    return BALF_OK;
+}
+
+// a bias gradient: out[c] = fl32(sum over the p.N rows of x[row * xs + c]), c < cols (256 or 512), through part [p.PC][cols]
+int bias_grad(const float *x, unsigned xs, int cols, const PixelSlices &p, double *part, float *out, hipStream_t st) {
+    col_sum_kernel<<<dim3(p.PC, cols / 256), 256, 0, st>>>(x, xs, p.N, p.col_rows, part);
+    BALF_LAUNCH_CHECK();
+    return finish_cols(part, cols, p.PC, out, st);
 }
 
 }  // namespace
