@@ -493,8 +493,11 @@ int balf_resize_crop_u8(const unsigned char *packed_dev, size_t packed_bytes, co
  *                      device function): X = M0 x + M1 y + M2 etc. in float64 without fused operations, 32 / W (0 for W = 0),
  *                      clamped to the int range, rounded half to even; tap = value >> 5, fractions fx, fy = value & 31.
  *                      Integer weights (32-fx)(32-fy)32, fx(32-fy)32, (32-fx)fy 32, fx fy 32 (sum 32768); a tap outside the
- *                      source image contributes 0; byte = (sum + 16384) >> 15; then / 255 as above.  A singular inv_h gives an
- *                      all-zero patch.
+ *                      source image contributes 0; byte = (sum + 16384) >> 15; then / 255 as above.  At a pixel where W is
+ *                      exactly 0 both coordinates are 0: the tap is source pixel (0, 0).  A singular inv_h (the determinant
+ *                      of the closed form is exactly 0, e.g. a zero row) gives an all-zero patch and dst_max = 0; the pair's
+ *                      source patch and both heat maps are computed as for any other pair (the label warp divides by its
+ *                      own float32 denominator, below), and the other pairs of the call are not affected.
  *   dst_max            the largest byte of the destination patch (0: an all-black patch).  The reference redraws a homography
  *                      whose WHOLE warped image is black (COCO.py:77); that image is never formed here, nothing is redrawn, and
  *                      the caller gets this value instead.
@@ -506,7 +509,8 @@ int balf_resize_crop_u8(const unsigned char *packed_dev, size_t packed_bytes, co
  *   dest. heat map     apply_homography_to_source_labels_torch as it returns (:200-219; its bilinear labels are discarded by
  *                      the reference and not computed): (xi, yi) warped with inv_h NARROWED TO float32 in float32 arithmetic
  *                      without fused operations, x' = ((h0 xi + h1 yi) + h2) / ((h6 xi + h7 yi) + h8); kept where 0 <= x' <=
- *                      w - 1 and 0 <= y' <= h - 1 of the FULL image; rounded half to even; 1.0 where the rounded point lies
+ *                      w - 1 and 0 <= y' <= h - 1 of the FULL image (both ends included; a denominator of exactly 0 gives an
+ *                      infinity or a NaN, which is dropped here); rounded half to even; 1.0 where the rounded point lies
  *                      inside the destination window, 0 elsewhere.
  * The heat maps are zeroed by the call itself.  An image that does not lie inside packed_bytes gives all-zero outputs; a window
  * that leaves its image is read clamped (source) / evaluated where it lies (destination); both report dst_max = -1 (the

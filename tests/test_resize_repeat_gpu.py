@@ -171,14 +171,17 @@ def test_c_abi_stays_inside_its_buffers(g):
 
 
 # ---- 3. the resize -------------------------------------------------------------------------------------------------------
-RESIZE_SIZES = ((480, 640), (300, 700), (700, 300), (100, 120), (333, 517), (125, 175), (241, 320), (240, 325), (50, 25))
+# (the last two: one-pixel-thin sources, a single tap on one axis)
+RESIZE_SIZES = ((480, 640), (300, 700), (700, 300), (100, 120), (333, 517), (125, 175), (241, 320), (240, 325), (50, 25), (1, 37),
+                (41, 1))
 
 
 @pytest.mark.parametrize("color", [False, True])
-@pytest.mark.parametrize("target", [(240, 320), (5, 2)])
+@pytest.mark.parametrize("target", [(240, 320), (5, 2), (67, 130), (1, 65)])
 def test_resize_equals_the_integer_restatement(color, target):
     """Sizes that crop in x, in y, that need upscaling, odd sizes (125 x 175 at scale 0.02 -> 2.5 and 3.5, 50 x 25 at 0.1 -> 2.5:
-    np.round goes to even) and odd differences; images of different sizes in ONE call; integer arithmetic: array_equal."""
+    np.round goes to even) and odd differences; images of different sizes in ONE call; integer arithmetic: array_equal.
+    Targets of whole 64 x 4 tiles, of one partial tile, of whole and partial tiles on both axes (67 x 130), of a single row."""
     rng = np.random.default_rng(8)
     images = []
     for i, (h, w) in enumerate(RESIZE_SIZES):
