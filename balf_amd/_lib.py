@@ -19,6 +19,7 @@ PYR_SRC_U8, PYR_SRC_F32, PYR_SRC_LEVEL = 0, 1, 2                   # include/bal
 PYR_MAX_RADIUS, MAX_PYRAMID_LEVELS = 8, 32
 VAL_LEG_GREEDY, VAL_LEG_WINDOW = 0, 1                              # include/balf_hip.h: balf_val_points
 STATUS_SCORE, STATUS_RANGE, STATUS_SE, STATUS_WORDS = 0, 1, 2, 4      # include/balf_hip.h: balf_forward_status
+UNIT_RCAB, UNIT_GMLP, UNIT_POOL = 0, 1, 2                          # include/balf_hip.h: balf_train_unit_sizes
 OPTIM_MAX_TENSORS = 64                                             # include/balf_hip.h: balf_adam_step / balf_sgd_step
 
 # name -> (restype, argtypes); kept in step with include/balf_hip.h (tests/test_abi.py checks)
@@ -100,15 +101,22 @@ PROTOTYPES = {
     "balf_rcab_train_saved_bytes": (_sz, [_i, _i, _i]),
     "balf_rcab_train_forward": (_i, [_fp] * 12 + [_i, _i, _i, _fp, _vp, _vp, _sz, _vp]),
     "balf_rcab_train_backward": (_i, [_fp] * 7 + [_vp, _i, _i, _i] + [_fp] * 11 + [_vp, _sz, _vp]),
+    "balf_rcab_train_forward_c": (_i, [_fp] * 12 + [_i, _i, _i, _i, _fp, _vp, _vp, _sz, _vp]),
+    "balf_rcab_train_backward_c": (_i, [_fp] * 7 + [_vp, _i, _i, _i, _i] + [_fp] * 11 + [_vp, _sz, _vp]),
     "balf_forward_rcab_inputs": (_i, [_i, _vp, _sz, _i, _i, _i, _fp, _fp, _fp, _fp, _vp]),
     "balf_gmlp_train_workspace_bytes": (_sz, [_i, _i, _i]),
     "balf_gmlp_train_saved_bytes": (_sz, [_i, _i, _i]),
     "balf_gmlp_train_forward": (_i, [_fp, C.POINTER(_vp), _i, _i, _i, _fp, _vp, _vp, _sz, _vp]),
     "balf_gmlp_train_backward": (_i, [_fp, _fp, C.POINTER(_vp), _vp, _i, _i, _i, C.POINTER(_vp), _fp, _vp, _sz, _vp]),
+    "balf_gmlp_train_forward_c": (_i, [_fp, C.POINTER(_vp), _i, _i, _i, _i, _fp, _vp, _vp, _sz, _vp]),
+    "balf_gmlp_train_backward_c": (_i, [_fp, _fp, C.POINTER(_vp), _vp, _i, _i, _i, _i, C.POINTER(_vp), _fp, _vp, _sz, _vp]),
     "balf_forward_gmlp_input": (_i, [_i, _vp, _sz, _i, _i, _i, _fp, _fp, _fp, _fp, _vp]),
     "balf_linrelu_train_workspace_bytes": (_sz, [_i, _i]),
     "balf_linrelu_train_forward": (_i, [_fp, _fp, _fp, _i, _i, _fp, _vp]),
     "balf_linrelu_train_backward": (_i, [_fp, _fp, _fp, _fp, _i, _i, _fp, _fp, _fp, _vp, _sz, _vp]),
+    "balf_pool_train_forward": (_i, [_fp, _i, _i, _i, _i, _fp, _vp, _vp]),
+    "balf_pool_train_backward": (_i, [_fp, _vp, _i, _i, _i, _i, _fp, _vp]),
+    "balf_train_unit_sizes": (_i, [_i, _i, _i, _i, _i, C.POINTER(_sz), C.POINTER(_sz)]),
     "balf_optim_chunk_elems": (_i, []),
     "balf_adam_step": (_i, [_i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(C.c_int64), C.c_double,
                            C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64, _vp]),

@@ -1,8 +1,11 @@
-// balf_gmlp_train_forward / balf_gmlp_train_backward (include/balf_hip.h): stage 4's ResidualSplitHeadMultiAxisGmlpLayer in
-// training form,  x0 -> LayerNorm -> dense1 (256 -> 512) -> GELU -> halves (u, v) -> the grid branch on u, the block branch on v
-// -> dense2 (512 -> 256) + x0 = y,  and its backward from dy to the 26 parameter gradients and dx0 (DESIGN.md 7n).
+// balf_gmlp_train_forward_c / balf_gmlp_train_backward_c (include/balf_hip.h): a Down stage's ResidualSplitHeadMultiAxisGmlpLayer
+// in training form at C channels, C = 256 (stage 4) or 128 (stage 3) a template value of every kernel and of the Layout; the text
+// below writes the widths of C = 256, and 256 / 512 read C / 2C throughout.
+// x0 -> LayerNorm -> dense1 (256 -> 512) -> GELU -> halves (u, v) -> the grid branch on u, the block branch on v
+// -> dense2 (512 -> 256) + x0 = y,  and its backward from dy to the 26 parameter gradients and dx0 (DESIGN.md 7n, 7x).
 // N = B * Hc * Wc pixels.  A branch on z [N,256]:  LayerNorm -> dense1 (256 -> 512) -> GELU -> halves (a, c) -> LayerNorm of c ->
 // the 64 x 64 product along the TOKEN axis -> gate a * (mix + 1) -> dense2 (256 -> 256) + z.
+// The C = 256 instantiation is the code that served stage 4 alone: the same operations in the same order.
 //
 // Kernels:
 //   * gemm_kernel (train_gemm.h) for every product along the channels; GELU is its epilogue EPI_BIAS_N_GELU, which also keeps the
@@ -20,14 +23,14 @@
 //   * column sums in float64 per workgroup of rows (bias_grad: col_sum_kernel over 256 or 512 columns of a row of stride 256 or
 //     512), added by partial_sum_kernel.
 // dWt and dbt: each wave of mix_bwd_kernel sums dmix cn^T over its 64 channels in an MFMA chain per group and adds the groups of
-// its workgroup in float64 registers; the 4 * PW wave partials are added by partial_sum_kernel in one fixed order.
+// its workgroup in float64 registers; the (C / 64) * PW wave partials (a workgroup has C / 64 waves, one per 64 channels: C
+// threads) are added by partial_sum_kernel in one fixed order.
 // No floating-point atomics; every order is a function of (B, Hc, Wc) alone.
 #include "train_ln.h"
 
 namespace balf {
 namespace {
 
-constexpr int kC = 256, kC2 = 512;          // channels; the width of the two dense1 outputs and of the concatenation
 constexpr int kTok = 64;                    // tokens of a group: the 8 x 8 grid, the 8 x 8 block
 constexpr int kParams = 26;
 constexpr int kBranchParams = 10;           // norm.{w,b} dense1.{w,b} gating norm.{w,b} gating dense.{w,b} dense2.{w,b}
@@ -47,13 +50,15 @@ struct Layout {
     Branch br[2];
     // workspace
     double *col_part;                       // [2][PC][512]
-    double *mix_part;                       // [4 PW][kMixPart]
+    double *mix_part;                       // [(C / 64) PW][kMixPart]
     float *dcat, *dh0, *dhb;                // [N,512] each
     float *t0, *t1;                         // [N,256]: dgated, then dnb, then dn0; dcn
     float *slab;                            // [S][512 * 256]
 };
 
+template <int kC>
 Layout make_layout(int B, int Hc, int Wc, char *saved, char *work, size_t *saved_bytes, size_t *work_bytes) {
+    constexpr int kC2 = 2 * kC;             // the width of the two dense1 outputs and of the concatenation
     Layout l{};
     l.B = B; l.Hc = Hc; l.Wc = Wc;
     const int N = B * Hc * Wc;
@@ -81,7 +86,7 @@ Layout make_layout(int B, int Hc, int Wc, char *saved, char *work, size_t *saved
     if (saved_bytes) *saved_bytes = sv.used;
     WorkspaceCursor ws{work, 0};
     l.col_part = ws.take<double>((size_t)2 * l.px.PC * kC2 * sizeof(double));
-    l.mix_part = ws.take<double>((size_t)4 * l.PW * kMixPart * sizeof(double));
+    l.mix_part = ws.take<double>((size_t)(kC / 64) * l.PW * kMixPart * sizeof(double));
     l.dcat = ws.take<float>(a2);
     l.dh0 = ws.take<float>(a2);
     l.dhb = ws.take<float>(a2);
@@ -101,7 +106,7 @@ struct MixArgs {
     float *mixp1, *gated;                   // forward: mix + 1, a * (mix + 1)  [N,256]
     const float *dgated, *hb, *mixp1_in;    // backward
     float *dhb, *dcn;                       // dhb [N,512], its lower half written here; dcn [N,256]
-    double *part;                           // [4 * PW][kMixPart]
+    double *part;                           // [(C / 64) * PW][kMixPart]
 };
 
 __device__ __forceinline__ size_t group_base(const MixArgs &a, int g) {
@@ -115,9 +120,9 @@ __device__ __forceinline__ size_t token_pixel(const MixArgs &a, size_t base, int
 typedef float (*MixTile)[kMixPitch];
 
 // TRANSPOSE: sW[q][p] = Wt[p][q] (forward: the MFMA's A operand is (m = p, k = q)); else sW[p][q] (backward: (m = q, k = p))
-template <bool TRANSPOSE>
+template <int kC, bool TRANSPOSE>
 __device__ __forceinline__ void load_wt(const float *wt, MixTile sW) {
-    for (int e = threadIdx.x; e < kTok * kTok; e += 256) {
+    for (int e = threadIdx.x; e < kTok * kTok; e += kC) {   // (a workgroup of kC threads)
         const int p = e >> 6, q = e & 63;
         if (TRANSPOSE) sW[q][p] = wt[e];
         else sW[p][q] = wt[e];
@@ -132,11 +137,13 @@ __device__ __forceinline__ void zero_acc(gf4 (&acc)[4][4]) {
 }
 
 // a workgroup per group: mix[p][ch] = sum_q Wt[p][q] cn[q][ch] + bt[p], q ascending; mixp1 = mix + 1; gated = a * mixp1
-__global__ __launch_bounds__(256) void mix_fwd_kernel(MixArgs a) {
+template <int kC>
+__global__ __launch_bounds__(kC) void mix_fwd_kernel(MixArgs a) {
+    constexpr int kC2 = 2 * kC;
     __shared__ float sW[kTok][kMixPitch];
     __shared__ float sB[kTok];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4, li = lane & 15;
-    load_wt<true>(a.wt, sW);
+    load_wt<kC, true>(a.wt, sW);
     if (threadIdx.x < kTok) sB[threadIdx.x] = a.bt[threadIdx.x];
     __syncthreads();
     const size_t base = group_base(a, blockIdx.x);
@@ -179,10 +186,12 @@ __global__ __launch_bounds__(256) void mix_fwd_kernel(MixArgs a) {
 // dcn[q][ch] = sum_p Wt[p][q] dmix[p][ch], p ascending;  then, over the wave's own 64 channels, dWt[p][q] += sum_ch dmix[p][ch]
 // cn[q][ch] (lane quarter k of step s takes channel 16 k + s of the 64: four 16-byte loads cover the sixteen steps) and dbt[p] +=
 // sum_ch dmix[p][ch].  The groups of the workgroup are added in float64 registers, in group order.
-__global__ __launch_bounds__(256) void mix_bwd_kernel(MixArgs a) {
+template <int kC>
+__global__ __launch_bounds__(kC) void mix_bwd_kernel(MixArgs a) {
+    constexpr int kC2 = 2 * kC;
     __shared__ float sW[kTok][kMixPitch];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane >> 4, li = lane & 15;
-    load_wt<false>(a.wt, sW);
+    load_wt<kC, false>(a.wt, sW);
     __syncthreads();
     const int ch = 64 * wave + 4 * li;
     double wacc[4][4][4], bsum[4];
@@ -255,7 +264,7 @@ __global__ __launch_bounds__(256) void mix_bwd_kernel(MixArgs a) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) wacc[i][j][r] += (double)acc[i][j][r];
     }
-    double *out = a.part + ((size_t)blockIdx.x * 4 + wave) * kMixPart;
+    double *out = a.part + ((size_t)blockIdx.x * (kC / 64) + wave) * kMixPart;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
 #pragma unroll
@@ -298,69 +307,57 @@ int check_call(const float *const *params, const void *const *others, int n_othe
     return BALF_OK;
 }
 
-}  // namespace
-}  // namespace balf
-
-using namespace balf;
-
-extern "C" size_t balf_gmlp_train_workspace_bytes(int B, int Hc, int Wc) {
-    if (check_gmlp_sizes(B, Hc, Wc) != BALF_OK) return 0;
-    size_t bytes = 0;
-    make_layout(B, Hc, Wc, nullptr, nullptr, nullptr, &bytes);
-    return bytes;
+template <int kC>
+size_t layout_bytes(int B, int Hc, int Wc, bool saved) {
+    size_t sv = 0, ws = 0;
+    make_layout<kC>(B, Hc, Wc, nullptr, nullptr, &sv, &ws);
+    return saved ? sv : ws;
 }
 
-extern "C" size_t balf_gmlp_train_saved_bytes(int B, int Hc, int Wc) {
-    if (check_gmlp_sizes(B, Hc, Wc) != BALF_OK) return 0;
-    size_t bytes = 0;
-    make_layout(B, Hc, Wc, nullptr, nullptr, &bytes, nullptr);
-    return bytes;
-}
-
-extern "C" int balf_gmlp_train_forward(const float *x0_dev, const float *const *params, int B, int Hc, int Wc, float *y_dev,
-                                       void *saved_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
+template <int kC>
+int gmlp_forward(const float *x0_dev, const float *const *params, int B, int Hc, int Wc, float *y_dev, void *saved_dev,
+                 void *workspace_dev, size_t workspace_bytes, void *stream) {
+    constexpr int kC2 = 2 * kC;
     const void *ptrs[] = {x0_dev, y_dev, saved_dev, workspace_dev};
     BALF_TRY(check_call(params, ptrs, 4, ptrs, 4));
     BALF_TRY(check_gmlp_sizes(B, Hc, Wc));
-    if (workspace_bytes < balf_gmlp_train_workspace_bytes(B, Hc, Wc)) return BALF_ERR_WORKSPACE;
+    if (workspace_bytes < layout_bytes<kC>(B, Hc, Wc, false)) return BALF_ERR_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const Layout l = make_layout(B, Hc, Wc, static_cast<char *>(saved_dev), static_cast<char *>(workspace_dev), nullptr, nullptr);
-    const int N = l.px.N, ln_blocks = balf_ceil_div(N, kLnFwdPix);
+    const Layout l = make_layout<kC>(B, Hc, Wc, static_cast<char *>(saved_dev), static_cast<char *>(workspace_dev), nullptr, nullptr);
+    const int N = l.px.N;
     const float *const *P = params;
 
-    ln_fwd_kernel<<<ln_blocks, 256, 0, st>>>(x0_dev, kC, P[0], P[1], N, l.n0, l.stat0);
-    BALF_LAUNCH_CHECK();
+    BALF_TRY(ln_forward<kC>(x0_dev, kC, P[0], P[1], N, l.n0, l.stat0, st));
     BALF_TRY((pixel_gemm<EPI_BIAS_N_GELU, false>(l.n0, kC, kC, P[2], kC2, N, l.g0, kC2, P[3], l.h0, st)));      // (u, v) = gelu(n0 W1^T + b1)
     for (int k = 0; k < 2; ++k) {
         const Branch &b = l.br[k];
         const float *const *Q = P + 4 + kBranchParams * k;
         const float *z = l.g0 + kC * k;                                                              // u or v, row stride 512
-        ln_fwd_kernel<<<ln_blocks, 256, 0, st>>>(z, kC2, Q[0], Q[1], N, b.nb, b.statb);
-        BALF_LAUNCH_CHECK();
+        BALF_TRY(ln_forward<kC>(z, kC2, Q[0], Q[1], N, b.nb, b.statb, st));
         BALF_TRY((pixel_gemm<EPI_BIAS_N_GELU, false>(b.nb, kC, kC, Q[2], kC2, N, b.gb, kC2, Q[3], b.hb, st)));   // (a, c)
-        ln_fwd_kernel<<<ln_blocks, 256, 0, st>>>(b.gb + kC, kC2, Q[4], Q[5], N, b.cn, b.statg);
-        BALF_LAUNCH_CHECK();
+        BALF_TRY(ln_forward<kC>(b.gb + kC, kC2, Q[4], Q[5], N, b.cn, b.statg, st));
         MixArgs m = mix_args(l, k == 0);
         m.wt = Q[6]; m.bt = Q[7]; m.cn = b.cn; m.gb = b.gb; m.mixp1 = b.mixp1; m.gated = b.gated;
-        mix_fwd_kernel<<<l.groups, 256, 0, st>>>(m);
+        mix_fwd_kernel<kC><<<l.groups, kC, 0, st>>>(m);
         BALF_LAUNCH_CHECK();
         BALF_TRY((pixel_gemm<EPI_BIAS_N_ADD, false>(b.gated, kC, kC, Q[8], kC, N, l.cat + kC * k, kC2, Q[9], z, st)));   // z' = z + gated Wb2^T + bb2
     }
     return pixel_gemm<EPI_BIAS_N_ADD, false>(l.cat, kC2, kC2, P[24], kC, N, y_dev, kC, P[25], x0_dev, st);      // y = cat W2^T + b2 + x0
 }
 
-extern "C" int balf_gmlp_train_backward(const float *dy_dev, const float *x0_dev, const float *const *params, const void *saved_dev,
-                                        int B, int Hc, int Wc, float *const *grads, float *dx0_dev, void *workspace_dev,
-                                        size_t workspace_bytes, void *stream) {
+template <int kC>
+int gmlp_backward(const float *dy_dev, const float *x0_dev, const float *const *params, const void *saved_dev, int B, int Hc, int Wc,
+                  float *const *grads, float *dx0_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
+    constexpr int kC2 = 2 * kC;
     const void *ptrs[] = {dy_dev, x0_dev, saved_dev, workspace_dev, dx0_dev};
     BALF_TRY(check_call(params, ptrs, 4, ptrs, 5));
     if (!grads) return BALF_ERR_ARG;
     for (int i = 0; i < kParams; ++i)
         if (!grads[i]) return BALF_ERR_ARG;
     BALF_TRY(check_gmlp_sizes(B, Hc, Wc));
-    if (workspace_bytes < balf_gmlp_train_workspace_bytes(B, Hc, Wc)) return BALF_ERR_WORKSPACE;
+    if (workspace_bytes < layout_bytes<kC>(B, Hc, Wc, false)) return BALF_ERR_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const Layout l = make_layout(B, Hc, Wc, static_cast<char *>(const_cast<void *>(saved_dev)), static_cast<char *>(workspace_dev),
+    const Layout l = make_layout<kC>(B, Hc, Wc, static_cast<char *>(const_cast<void *>(saved_dev)), static_cast<char *>(workspace_dev),
                                  nullptr, nullptr);
     const int N = l.px.N;
     const float *const *P = params;
@@ -387,16 +384,16 @@ extern "C" int balf_gmlp_train_backward(const float *dy_dev, const float *x0_dev
         MixArgs m = mix_args(l, k == 0);
         m.wt = Q[6]; m.cn = b.cn; m.gb = b.gb; m.dgated = dgated; m.hb = b.hb; m.mixp1_in = b.mixp1; m.dhb = l.dhb; m.dcn = dcn;
         m.part = l.mix_part;
-        mix_bwd_kernel<<<l.PW, 256, 0, st>>>(m);
+        mix_bwd_kernel<kC><<<l.PW, kC, 0, st>>>(m);
         BALF_LAUNCH_CHECK();
-        partial_sum_kernel<<<kTok * kTok / 4, 256, 0, st>>>(l.mix_part, kTok * kTok, 4 * l.PW, 1, (size_t)kMixPart, D[6], nullptr);
+        partial_sum_kernel<<<kTok * kTok / 4, 256, 0, st>>>(l.mix_part, kTok * kTok, (kC / 64) * l.PW, 1, (size_t)kMixPart, D[6], nullptr);
         BALF_LAUNCH_CHECK();
-        partial_sum_kernel<<<kTok / 4, 256, 0, st>>>(l.mix_part + kTok * kTok, kTok, 4 * l.PW, 1, (size_t)kMixPart, D[7], nullptr);
+        partial_sum_kernel<<<kTok / 4, 256, 0, st>>>(l.mix_part + kTok * kTok, kTok, (kC / 64) * l.PW, 1, (size_t)kMixPart, D[7], nullptr);
         BALF_LAUNCH_CHECK();
         // the gating LayerNorm on c: dhb (c's half) = LN'(dcn) * gelu'(hb)
         n.dn = dcn; n.stat = b.statg; n.ln_g = Q[4];
         n.x = b.gb + kC; n.xs = kC2; n.h = b.hb + kC; n.hs = kC2; n.out = l.dhb + kC; n.os = kC2;
-        BALF_TRY(ln_backward<LN_DX_GELU>(n, l.px, D[4], D[5], st));
+        BALF_TRY((ln_backward<kC, LN_DX_GELU>(n, l.px, D[4], D[5], st)));
         // hb = nb Wb1^T + bb1
         BALF_TRY(bias_grad(l.dhb, kC2, kC2, l.px, part0, D[3], st));
         BALF_TRY(weight_grad(l.dhb, kC2, kC2, b.nb, kC, kC, l.px, l.slab, D[2], st));
@@ -405,7 +402,7 @@ extern "C" int balf_gmlp_train_backward(const float *dy_dev, const float *x0_dev
         // the branch's LayerNorm on z and its shortcut: dh0 (this half) = (dzo + LN'(dnb)) * gelu'(h0)
         n.dn = dnb; n.stat = b.statb; n.ln_g = Q[0];
         n.x = l.g0 + kC * k; n.xs = kC2; n.g = dzo; n.gs = kC2; n.h = l.h0 + kC * k; n.hs = kC2; n.out = l.dh0 + kC * k; n.os = kC2;
-        BALF_TRY(ln_backward<LN_DX_ADD_GELU>(n, l.px, D[0], D[1], st));
+        BALF_TRY((ln_backward<kC, LN_DX_ADD_GELU>(n, l.px, D[0], D[1], st)));
     }
     // h0 = n0 W1^T + b1
     BALF_TRY(bias_grad(l.dh0, kC2, kC2, l.px, part0, G[3], st));
@@ -416,5 +413,55 @@ extern "C" int balf_gmlp_train_backward(const float *dy_dev, const float *x0_dev
     n.dn = dn0; n.stat = l.stat0; n.ln_g = P[0];
     n.x = x0_dev; n.xs = kC; n.g = dy_dev; n.gs = kC; n.h = nullptr; n.out = dx0_dev; n.os = kC;
     n.vec_g = true; n.vec_out = true;
-    return dx0_dev ? ln_backward<LN_DX_ADD>(n, l.px, G[0], G[1], st) : ln_backward<LN_DX_NONE>(n, l.px, G[0], G[1], st);
+    return dx0_dev ? ln_backward<kC, LN_DX_ADD>(n, l.px, G[0], G[1], st) : ln_backward<kC, LN_DX_NONE>(n, l.px, G[0], G[1], st);
+}
+
+}  // namespace
+
+// the unit's two sizes for balf_train_unit_sizes (train_sizes.hip): the code of the size check, and the outputs only with BALF_OK
+int gmlp_train_sizes(int C, int B, int Hc, int Wc, size_t *workspace_bytes, size_t *saved_bytes) {
+    if (C != 128 && C != 256) return BALF_ERR_SHAPE;
+    BALF_TRY(check_gmlp_sizes(B, Hc, Wc));
+    *workspace_bytes = C == 128 ? layout_bytes<128>(B, Hc, Wc, false) : layout_bytes<256>(B, Hc, Wc, false);
+    *saved_bytes = C == 128 ? layout_bytes<128>(B, Hc, Wc, true) : layout_bytes<256>(B, Hc, Wc, true);
+    return BALF_OK;
+}
+
+}  // namespace balf
+
+using namespace balf;
+
+extern "C" size_t balf_gmlp_train_workspace_bytes(int B, int Hc, int Wc) {
+    return check_gmlp_sizes(B, Hc, Wc) == BALF_OK ? layout_bytes<256>(B, Hc, Wc, false) : 0;
+}
+
+extern "C" size_t balf_gmlp_train_saved_bytes(int B, int Hc, int Wc) {
+    return check_gmlp_sizes(B, Hc, Wc) == BALF_OK ? layout_bytes<256>(B, Hc, Wc, true) : 0;
+}
+
+extern "C" int balf_gmlp_train_forward_c(const float *x0_dev, const float *const *params, int B, int Hc, int Wc, int C, float *y_dev,
+                                         void *saved_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
+    if (C != 128 && C != 256) return BALF_ERR_SHAPE;
+    return (C == 128 ? gmlp_forward<128> : gmlp_forward<256>)(x0_dev, params, B, Hc, Wc, y_dev, saved_dev, workspace_dev, workspace_bytes,
+                                                              stream);
+}
+
+extern "C" int balf_gmlp_train_backward_c(const float *dy_dev, const float *x0_dev, const float *const *params, const void *saved_dev,
+                                          int B, int Hc, int Wc, int C, float *const *grads, float *dx0_dev, void *workspace_dev,
+                                          size_t workspace_bytes, void *stream) {
+    if (C != 128 && C != 256) return BALF_ERR_SHAPE;
+    return (C == 128 ? gmlp_backward<128> : gmlp_backward<256>)(dy_dev, x0_dev, params, saved_dev, B, Hc, Wc, grads, dx0_dev, workspace_dev,
+                                                                workspace_bytes, stream);
+}
+
+extern "C" int balf_gmlp_train_forward(const float *x0_dev, const float *const *params, int B, int Hc, int Wc, float *y_dev,
+                                       void *saved_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
+    return balf_gmlp_train_forward_c(x0_dev, params, B, Hc, Wc, 256, y_dev, saved_dev, workspace_dev, workspace_bytes, stream);
+}
+
+extern "C" int balf_gmlp_train_backward(const float *dy_dev, const float *x0_dev, const float *const *params, const void *saved_dev,
+                                        int B, int Hc, int Wc, float *const *grads, float *dx0_dev, void *workspace_dev,
+                                        size_t workspace_bytes, void *stream) {
+    return balf_gmlp_train_backward_c(dy_dev, x0_dev, params, saved_dev, B, Hc, Wc, 256, grads, dx0_dev, workspace_dev, workspace_bytes,
+                                      stream);
 }

@@ -24,7 +24,6 @@ namespace {
 
 typedef float gf4 __attribute__((ext_vector_type(4)));
 
-constexpr int kTrainC = 256;                // the channel count of every [N,256] matrix here
 constexpr int kTile = 64, kTK = 16, kPitch = kTile + 4;
 constexpr int kMaxSlices = 64;              // slabs of a weight gradient
 constexpr int kTrainMaxN = 1 << 24;         // pixels: up to 2^32 elements in a [N,256] matrix, indexed in size_t
@@ -238,11 +237,12 @@ __device__ __forceinline__ double chain4_sum(int r0, int r1, Term term) {
     return (s[0] + s[1]) + (s[2] + s[3]);
 }
 
-// float64 column sums of rows [blockIdx.x * rows, ...) of a matrix of row stride xs and gridDim.y * 256 columns, a column per
-// thread: part[block][column]
-__global__ __launch_bounds__(256) void col_sum_kernel(const float *x, unsigned xs, int N, int rows, double *part) {
+// float64 column sums of rows [blockIdx.x * rows, ...) of a matrix of row stride xs and cols columns (256 per grid y; 128: half a
+// workgroup idles), a column per thread: part[block][column]
+__global__ __launch_bounds__(256) void col_sum_kernel(const float *x, unsigned xs, int N, int rows, int cols, double *part) {
     const int r0 = blockIdx.x * rows, r1 = min(N, r0 + rows), c = blockIdx.y * 256 + threadIdx.x;
-    part[(size_t)blockIdx.x * (gridDim.y * 256) + c] = chain4_sum(r0, r1, [&](int r) { return (double)x[row_at(r, xs) + c]; });
+    if (c >= cols) return;
+    part[(size_t)blockIdx.x * cols + c] = chain4_sum(r0, r1, [&](int r) { return (double)x[row_at(r, xs) + c]; });
 }
 
 // ---- the launches along the channels -----------------------------------------------------------------------------------------
@@ -285,9 +285,9 @@ int finish_cols(const double *part, int cols, int P, float *out, hipStream_t st)
     return BALF_OK;
 }
 
-// a bias gradient: out[c] = fl32(sum over the p.N rows of x[row * xs + c]), c < cols (256 or 512), through part [p.PC][cols]
+// a bias gradient: out[c] = fl32(sum over the p.N rows of x[row * xs + c]), c < cols (128, 256 or 512), through part [p.PC][cols]
 int bias_grad(const float *x, unsigned xs, int cols, const PixelSlices &p, double *part, float *out, hipStream_t st) {
-    col_sum_kernel<<<dim3(p.PC, cols / 256), 256, 0, st>>>(x, xs, p.N, p.col_rows, part);
+    col_sum_kernel<<<dim3(p.PC, balf_ceil_div(cols, 256)), 256, 0, st>>>(x, xs, p.N, p.col_rows, cols, part);
     BALF_LAUNCH_CHECK();
     return finish_cols(part, cols, p.PC, out, st);
 }

@@ -250,7 +250,11 @@ class MLP_MA_DECODER(nn.Module):
         return self._forward("f32", (b, h, w), x.contiguous().float(), b, h, w, want_logits)
 
     def encode(self, x: torch.Tensor, chunk=None, level: str = "x2"):
-        """``level="stage3"``: the whole of stage 4 earlier -- ``x3``, the stage-3 output and input of ``down4.conv.0``,
+        """``level="stage2"``: the whole of stages 3 and 4 earlier -- the stage-2 output and input of ``down3.conv.0``,
+        [B,H/4,W/4,64] float32 NHWC, what ``model.stage3_train.TrainableStage3`` trains on (balf_forward_stage_view, stage 2),
+        chunked and guarded exactly as ``"stage3"``.
+
+        ``level="stage3"``: the whole of stage 4 earlier -- ``x3``, the stage-3 output and input of ``down4.conv.0``,
         [B,H/8,W/8,128] float32 NHWC, what ``model.stage4_train.TrainableStage4`` trains on (balf_forward_stage_view, stage 3:
         a copy on the fp32 path, de-fragmented on the split-f16 path -- the x3 that levels "rcab" and "gmlp" compute x0 from).
 
@@ -279,14 +283,15 @@ class MLP_MA_DECODER(nn.Module):
             raise ValueError(f"H and W must be multiples of 64 (pad with mod_padding_symmetric), got {h}x{w}")
         if b < 1:
             raise ValueError("encode: an empty batch")
-        if level not in ("x2", "rcab", "gmlp", "stage3"):
-            raise ValueError(f"encode: level must be 'x2', 'rcab', 'gmlp' or 'stage3', got {level!r}")
+        if level not in ("x2", "rcab", "gmlp", "stage3", "stage2"):
+            raise ValueError(f"encode: level must be 'x2', 'rcab', 'gmlp', 'stage3' or 'stage2', got {level!r}")
         x = x.contiguous().float()
         l = lib()
         mb = l.balf_forward_micro_batch(b, h, w)
         chunk = mb if chunk is None else max(1, min(int(chunk), mb))
-        stage = 3 if level == "stage3" else 4
-        out = torch.empty((b, h // 8, w // 8, 128 if stage == 3 else 256), dtype=torch.float32, device=x.device)
+        stage = {"stage2": 2, "stage3": 3}.get(level, 4)
+        cells = 4 if stage == 2 else 8                          # the stage's map is H / cells x W / cells
+        out = torch.empty((b, h // cells, w // cells, {2: 64, 3: 128, 4: 256}[stage]), dtype=torch.float32, device=x.device)
         if level == "rcab":
             r = torch.empty_like(out)
         if level in ("rcab", "gmlp"):

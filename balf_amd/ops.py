@@ -666,6 +666,30 @@ RCAB_PARAMS = ("ln_g", "ln_b", "wc1", "bc1", "wc2", "bc2", "ws0", "bs0", "ws2", 
 _RCAB_PARAM_SHAPES = {"ln_g": (256,), "ln_b": (256,), "wc1": (256, 256), "bc1": (256,), "wc2": (256, 256), "bc2": (256,),
                       "ws0": (64, 256), "bs0": (64,), "ws2": (256, 64), "bs2": (256,)}
 _RCAB_BACKWARD_READS = ("ln_g", "wc1", "wc2", "ws0", "ws2")
+TRAIN_WIDTHS = {256: 4, 128: 3}           # channels of the RCAB and the gated-MLP layer in training form -> the Down stage
+
+
+def _train_width(channels: int, what: str) -> int:
+    if channels not in TRAIN_WIDTHS:
+        raise BalfHipError(f"{what}: channels must be one of {sorted(TRAIN_WIDTHS)}, got {channels!r}")
+    return channels
+
+
+def rcab_param_shapes(channels: int = 256) -> dict:
+    """The shapes of the ten ``RCAB_PARAMS`` of the channel-attention block at ``channels`` (256: stage 4's, 128: stage 3's)."""
+    c = _train_width(channels, "rcab_param_shapes")
+    if c == 256:
+        return _RCAB_PARAM_SHAPES
+    return {"ln_g": (c,), "ln_b": (c,), "wc1": (c, c), "bc1": (c,), "wc2": (c, c), "bc2": (c,), "ws0": (c // 4, c), "bs0": (c // 4,),
+            "ws2": (c, c // 4), "bs2": (c,)}
+
+
+def train_unit_sizes(unit: int, channels: int, b: int, h: int, w: int) -> Tuple[int, int]:
+    """(workspace bytes, saved bytes) of a training unit (_lib.UNIT_RCAB / UNIT_GMLP / UNIT_POOL) at ``channels`` on ``b`` maps of
+    ``h x w``, the map the unit receives: balf_train_unit_sizes in include/balf_hip.h."""
+    ws, sv = C.c_size_t(0), C.c_size_t(0)
+    _lib.check(lib().balf_train_unit_sizes(unit, channels, b, h, w, C.byref(ws), C.byref(sv)), "balf_train_unit_sizes")
+    return ws.value, sv.value
 
 
 class RcabTrainForward(NamedTuple):
@@ -687,11 +711,12 @@ class RcabTrainBackward(NamedTuple):
     dy: Optional[torch.Tensor]                # [B,Hc,Wc,256]
 
 
-def _rcab_train_checks(y, named, aligned=()):
+def _rcab_train_checks(y, named, aligned=(), channels=256):
     """``named``: (tensor or None, name, shape) triples, y first; ``aligned``: the names whose storage must start on 16 bytes (the
     LayerNorm kernels move four channels at a time) (_check_tensors).  -> (B, Hc, Wc)."""
-    if y.dim() != 4 or y.shape[3] != 256:
-        raise BalfHipError(f"y must be [B,Hc,Wc,256] (the input of stage 4's RCAB, NHWC), got {tuple(y.shape)}")
+    if y.dim() != 4 or y.shape[3] != channels:
+        raise BalfHipError(f"y must be [B,Hc,Wc,{channels}] (the input of stage {TRAIN_WIDTHS[channels]}'s RCAB, NHWC), "
+                           f"got {tuple(y.shape)}")
     b, hc, wc, _ = y.shape
     if not 1 <= b <= 65535 or hc < 1 or wc < 1 or not 2 <= b * hc * wc <= 1 << 24:
         raise BalfHipError(f"rcab_train: 1 <= B <= 65535 and 2 <= B * Hc * Wc <= 2^24, got {tuple(y.shape)}")
@@ -699,44 +724,48 @@ def _rcab_train_checks(y, named, aligned=()):
     return b, hc, wc
 
 
-def rcab_train_forward(y: torch.Tensor, r: torch.Tensor, params, saved=None) -> RcabTrainForward:
+def rcab_train_forward(y: torch.Tensor, r: torch.Tensor, params, saved=None, *, channels: int = 256) -> RcabTrainForward:
     """Stage 4's channel-attention block on ``y`` [B,Hc,Wc,256] with ``r`` = y + the long shortcut (``rcab_inputs`` /
     ``MLP_MA_DECODER.encode(level="rcab")`` give both): LayerNorm, conv1, LeakyReLU, conv2, the squeeze-excite scale, ``x2 = t * s +
     r`` (balf_rcab_train_forward in include/balf_hip.h).  ``params``: the ten tensors in ``RCAB_PARAMS`` order, float32 and
-    contiguous on y's GPU.  ``saved``: a uint8 block to reuse (at least balf_rcab_train_saved_bytes), else allocated."""
+    contiguous on y's GPU.  ``saved``: a uint8 block to reuse (at least balf_rcab_train_saved_bytes), else allocated.
+    ``channels``: the block's width, 256 (stage 4) or 128 (stage 3: balf_rcab_train_forward_c); it is stated, never taken from
+    ``y``, and every width above reads ``channels`` for 256 and ``channels // 4`` for 64."""
+    shapes = rcab_param_shapes(channels)
     params = tuple(params)
     if len(params) != len(RCAB_PARAMS):
         raise BalfHipError(f"rcab_train_forward takes the ten parameters {RCAB_PARAMS}, got {len(params)}")
-    named = ((y, "y", None), (r, "r", tuple(y.shape))) + tuple((t, k, _RCAB_PARAM_SHAPES[k]) for t, k in zip(params, RCAB_PARAMS))
-    b, hc, wc = _rcab_train_checks(y, named + ((saved, "saved", None),), aligned=("y", "r", "ln_g", "ln_b"))
+    named = ((y, "y", None), (r, "r", tuple(y.shape))) + tuple((t, k, shapes[k]) for t, k in zip(params, RCAB_PARAMS))
+    b, hc, wc = _rcab_train_checks(y, named + ((saved, "saved", None),), aligned=("y", "r", "ln_g", "ln_b"), channels=channels)
     dev = y.device
-    l = lib()
-    saved = _saved_block(saved, l.balf_rcab_train_saved_bytes(b, hc, wc), dev, True)
+    ws_bytes, saved_bytes = train_unit_sizes(_lib.UNIT_RCAB, channels, b, hc, wc)
+    saved = _saved_block(saved, saved_bytes, dev, True)
     x2 = torch.empty_like(y)
-    ws = _workspace("rcab_train", dev, l.balf_rcab_train_workspace_bytes(b, hc, wc))
-    launch("balf_rcab_train_forward", dev, y, r, *params, b, hc, wc, x2, saved, Workspace(ws))
+    ws = _workspace("rcab_train", dev, ws_bytes)
+    launch("balf_rcab_train_forward_c", dev, y, r, *params, b, hc, wc, channels, x2, saved, Workspace(ws))
     return RcabTrainForward(x2, saved)
 
 
 def rcab_train_backward(dx2: torch.Tensor, y: torch.Tensor, ln_g: torch.Tensor, wc1: torch.Tensor, wc2: torch.Tensor,
-                        ws0: torch.Tensor, ws2: torch.Tensor, saved: torch.Tensor, want_dy=False) -> RcabTrainBackward:
+                        ws0: torch.Tensor, ws2: torch.Tensor, saved: torch.Tensor, want_dy=False, *,
+                        channels: int = 256) -> RcabTrainBackward:
     """The backward of ``rcab_train_forward`` (balf_rcab_train_backward): ``dx2`` [B,Hc,Wc,256] (``head_train_backward`` writes
     it) and the ``saved`` block of that forward -> the ten parameter gradients and, with ``want_dy``, the gradient at the block's
-    input (``want_dy`` may be a contiguous float32 tensor of y's shape to write into)."""
-    s = _RCAB_PARAM_SHAPES
+    input (``want_dy`` may be a contiguous float32 tensor of y's shape to write into).  ``channels`` as in the forward."""
+    s = rcab_param_shapes(channels)
     dy = want_dy if isinstance(want_dy, torch.Tensor) else None
     shape = tuple(y.shape)
     named = ((y, "y", None), (dx2, "dx2", shape), (ln_g, "ln_g", s["ln_g"]), (wc1, "wc1", s["wc1"]), (wc2, "wc2", s["wc2"]),
              (ws0, "ws0", s["ws0"]), (ws2, "ws2", s["ws2"]), (saved, "saved", None), (dy, "dy", shape))
-    b, hc, wc = _rcab_train_checks(y, named, aligned=("y", "ln_g"))
+    b, hc, wc = _rcab_train_checks(y, named, aligned=("y", "ln_g"), channels=channels)
     dev = y.device
-    l = lib()
-    _saved_block(saved, l.balf_rcab_train_saved_bytes(b, hc, wc), dev, True, "rcab_train_forward")
+    ws_bytes, saved_bytes = train_unit_sizes(_lib.UNIT_RCAB, channels, b, hc, wc)
+    _saved_block(saved, saved_bytes, dev, True, "rcab_train_forward")
     if dy is None and want_dy:
         dy = torch.empty_like(y)
     out = [torch.empty(s[k], dtype=torch.float32, device=dev) for k in RCAB_PARAMS]
-    ws = _workspace("rcab_train", dev, l.balf_rcab_train_workspace_bytes(b, hc, wc))
-    launch("balf_rcab_train_backward", dev, dx2, y, ln_g, wc1, wc2, ws0, ws2, saved, b, hc, wc, *out, dy, Workspace(ws))
+    ws = _workspace("rcab_train", dev, ws_bytes)
+    launch("balf_rcab_train_backward_c", dev, dx2, y, ln_g, wc1, wc2, ws0, ws2, saved, b, hc, wc, channels, *out, dy, Workspace(ws))
     return RcabTrainBackward(*out, dy)
 
 
@@ -763,6 +792,16 @@ GMLP_PARAMS = (("norm.weight", "norm.bias", "dense1.weight", "dense1.bias")
 _GMLP_PARAM_SHAPES = dict(zip(GMLP_PARAMS, ((256,), (256,), (512, 256), (512,)) + 2 * _GMLP_BRANCH_SHAPES + ((256, 512), (256,))))
 
 
+def gmlp_param_shapes(channels: int = 256) -> dict:
+    """The shapes of the 26 ``GMLP_PARAMS`` of the gated-MLP layer at ``channels`` (256: stage 4's, 128: stage 3's); the token
+    matrices stay [64,64]."""
+    c = _train_width(channels, "gmlp_param_shapes")
+    if c == 256:
+        return _GMLP_PARAM_SHAPES
+    branch = ((c,), (c,), (2 * c, c), (2 * c,), (c,), (c,), (64, 64), (64,), (c, c), (c,))
+    return dict(zip(GMLP_PARAMS, ((c,), (c,), (2 * c, c), (2 * c,)) + 2 * branch + ((c, 2 * c), (c,))))
+
+
 class GmlpTrainForward(NamedTuple):
     y: torch.Tensor                           # [B,Hc,Wc,256] float32: the input of stage 4's RCAB
     saved: torch.Tensor                       # opaque uint8 block for gmlp_train_backward
@@ -773,18 +812,20 @@ class GmlpTrainBackward(NamedTuple):
     dx0: Optional[torch.Tensor]               # [B,Hc,Wc,256]
 
 
-def _gmlp_train_checks(x0, params, others):
+def _gmlp_train_checks(x0, params, others, channels=256):
     """``others``: (tensor or None, name, shape) triples behind x0 and the parameters.  Every tensor but ``saved`` is float32,
     contiguous and starts on a 16-byte boundary of its storage (_check_tensors).  -> (B, Hc, Wc, params)."""
-    if x0.dim() != 4 or x0.shape[3] != 256:
-        raise BalfHipError(f"x0 must be [B,Hc,Wc,256] (the input of stage 4's gMLP layer, NHWC), got {tuple(x0.shape)}")
+    shapes = gmlp_param_shapes(channels)
+    if x0.dim() != 4 or x0.shape[3] != channels:
+        raise BalfHipError(f"x0 must be [B,Hc,Wc,{channels}] (the input of stage {TRAIN_WIDTHS[channels]}'s gMLP layer, NHWC), "
+                           f"got {tuple(x0.shape)}")
     b, hc, wc, _ = x0.shape
     if not 1 <= b <= 65535 or hc < 1 or wc < 1 or hc % 8 or wc % 8 or b * hc * wc > 1 << 24:
         raise BalfHipError(f"gmlp_train: 1 <= B <= 65535, Hc and Wc multiples of 8 and B * Hc * Wc <= 2^24, got {tuple(x0.shape)}")
     params = tuple(params)
     if len(params) != len(GMLP_PARAMS):
         raise BalfHipError(f"gmlp_train takes the {len(GMLP_PARAMS)} parameters of ops.GMLP_PARAMS, got {len(params)}")
-    named = ((x0, "x0", None),) + tuple((t, k, _GMLP_PARAM_SHAPES[k]) for t, k in zip(params, GMLP_PARAMS)) + tuple(others)
+    named = ((x0, "x0", None),) + tuple((t, k, shapes[k]) for t, k in zip(params, GMLP_PARAMS)) + tuple(others)
     _check_tensors(named, "x0", aligned=True, strict_saved=True)
     return b, hc, wc, params
 
@@ -793,35 +834,39 @@ def _pointer_array(tensors):
     return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
 
 
-def gmlp_train_forward(x0: torch.Tensor, params, saved=None) -> GmlpTrainForward:
+def gmlp_train_forward(x0: torch.Tensor, params, saved=None, *, channels: int = 256) -> GmlpTrainForward:
     """Stage 4's multi-axis gated-MLP layer on ``x0`` [B,Hc,Wc,256] (``MLP_MA_DECODER.encode(level="gmlp")`` gives it):
     balf_gmlp_train_forward in include/balf_hip.h.  ``params``: the 26 tensors in ``GMLP_PARAMS`` order, float32 and contiguous on
-    x0's GPU.  ``saved``: a uint8 block to reuse (at least balf_gmlp_train_saved_bytes), else allocated."""
-    b, hc, wc, params = _gmlp_train_checks(x0, params, ((saved, "saved", None),))
+    x0's GPU.  ``saved``: a uint8 block to reuse (at least balf_gmlp_train_saved_bytes), else allocated.  ``channels``: the
+    layer's width, 256 (stage 4) or 128 (stage 3: balf_gmlp_train_forward_c); stated, never taken from ``x0``."""
+    b, hc, wc, params = _gmlp_train_checks(x0, params, ((saved, "saved", None),), channels)
     dev = x0.device
-    l = lib()
-    saved = _saved_block(saved, l.balf_gmlp_train_saved_bytes(b, hc, wc), dev, True)
+    ws_bytes, saved_bytes = train_unit_sizes(_lib.UNIT_GMLP, channels, b, hc, wc)
+    saved = _saved_block(saved, saved_bytes, dev, True)
     y = torch.empty_like(x0)
-    ws = _workspace("gmlp_train", dev, l.balf_gmlp_train_workspace_bytes(b, hc, wc))
-    launch("balf_gmlp_train_forward", dev, x0, _pointer_array(params), b, hc, wc, y, saved, Workspace(ws))
+    ws = _workspace("gmlp_train", dev, ws_bytes)
+    launch("balf_gmlp_train_forward_c", dev, x0, _pointer_array(params), b, hc, wc, channels, y, saved, Workspace(ws))
     return GmlpTrainForward(y, saved)
 
 
-def gmlp_train_backward(dy: torch.Tensor, x0: torch.Tensor, params, saved: torch.Tensor, want_dx0=False) -> GmlpTrainBackward:
+def gmlp_train_backward(dy: torch.Tensor, x0: torch.Tensor, params, saved: torch.Tensor, want_dx0=False, *,
+                        channels: int = 256) -> GmlpTrainBackward:
     """The backward of ``gmlp_train_forward`` (balf_gmlp_train_backward): ``dy`` [B,Hc,Wc,256] (``rcab_train_backward`` writes it)
     and the ``saved`` block of that forward -> the 26 parameter gradients and, with ``want_dx0``, the gradient at the layer's input
-    through the layer (``want_dx0`` may be a contiguous float32 tensor of x0's shape to write into)."""
+    through the layer (``want_dx0`` may be a contiguous float32 tensor of x0's shape to write into).  ``channels`` as in the
+    forward."""
     dx0 = want_dx0 if isinstance(want_dx0, torch.Tensor) else None
     shape = tuple(x0.shape)
-    b, hc, wc, params = _gmlp_train_checks(x0, params, ((dy, "dy", shape), (saved, "saved", None), (dx0, "dx0", shape)))
+    b, hc, wc, params = _gmlp_train_checks(x0, params, ((dy, "dy", shape), (saved, "saved", None), (dx0, "dx0", shape)), channels)
     dev = x0.device
-    l = lib()
-    _saved_block(saved, l.balf_gmlp_train_saved_bytes(b, hc, wc), dev, True, "gmlp_train_forward")
+    ws_bytes, saved_bytes = train_unit_sizes(_lib.UNIT_GMLP, channels, b, hc, wc)
+    _saved_block(saved, saved_bytes, dev, True, "gmlp_train_forward")
     if dx0 is None and want_dx0:
         dx0 = torch.empty_like(x0)
-    out = tuple(torch.empty(_GMLP_PARAM_SHAPES[k], dtype=torch.float32, device=dev) for k in GMLP_PARAMS)
-    ws = _workspace("gmlp_train", dev, l.balf_gmlp_train_workspace_bytes(b, hc, wc))
-    launch("balf_gmlp_train_backward", dev, dy, x0, _pointer_array(params), saved, b, hc, wc, _pointer_array(out), dx0,
+    shapes = gmlp_param_shapes(channels)
+    out = tuple(torch.empty(shapes[k], dtype=torch.float32, device=dev) for k in GMLP_PARAMS)
+    ws = _workspace("gmlp_train", dev, ws_bytes)
+    launch("balf_gmlp_train_backward_c", dev, dy, x0, _pointer_array(params), saved, b, hc, wc, channels, _pointer_array(out), dx0,
            Workspace(ws))
     return GmlpTrainBackward(out, dx0)
 
@@ -837,6 +882,52 @@ def gmlp_input(precision: int, workspace: torch.Tensor, b: int, hp: int, wp: int
     if precision == _lib.PREC_FP16:
         scratch = _workspace("gmlp_input", dev, x0.numel() // 2 * 4)
     launch("balf_forward_gmlp_input", dev, precision, Workspace(workspace), b, hp, wp, conv0_w, conv0_b, x0, scratch)
+
+
+class PoolTrainForward(NamedTuple):
+    out: torch.Tensor                         # [B,H/2,W/2,C] float32
+    which: torch.Tensor                       # [B,H/2,W/2,C] uint8: the raster position 0..3 of the chosen element in its window
+
+
+def _pool_train_checks(anchor, name, named, scale):
+    """``anchor`` [B,h,w,C] is ``x`` (the input map, ``scale`` 1) or ``g`` (the pooled map, ``scale`` 2).  -> (B, h, w, C)."""
+    if anchor.dim() != 4 or anchor.shape[3] % 4 or not 4 <= anchor.shape[3] <= 256:
+        raise BalfHipError(f"{name} must be [B,H,W,C] (NHWC) with C a multiple of 4 up to 256, got {tuple(anchor.shape)}")
+    b, h, w, c = anchor.shape
+    if not 1 <= b <= 65535 or h < 1 or w < 1:
+        raise BalfHipError(f"pool_train: 1 <= B <= 65535 and H, W >= 1, got {tuple(anchor.shape)}")
+    if scale == 1 and (h % 2 or w % 2):
+        raise BalfHipError(f"pool_train: H and W of the input map must be even, got {tuple(anchor.shape)}")
+    if b * h * w * scale * scale > 1 << 24:
+        raise BalfHipError(f"pool_train: B * H * W <= 2^24 on the input map, got {tuple(anchor.shape)}")
+    _check_metadata(tuple(t for t in named if t[1] != "which"), aligned=True)
+    for t, k, shape in named:
+        if k == "which" and (t.dtype != torch.uint8 or tuple(t.shape) != tuple(shape) or not t.is_contiguous()
+                             or t.storage_offset() % 16):
+            raise BalfHipError(f"which must be the contiguous uint8 {list(shape)} tensor that pool_train_forward returned")
+    _check_devices(tuple(t[:2] for t in named), name, anchor.device)
+    return b, h, w, c
+
+
+def pool_train_forward(x: torch.Tensor) -> PoolTrainForward:
+    """The 2 x 2 max-pool that ends a Down stage on ``x`` [B,H,W,C] float32 NHWC, H and W even, C a multiple of 4 up to 256
+    (balf_pool_train_forward in include/balf_hip.h): torch's CPU ``max_pool2d`` rule, and ``which`` for the backward."""
+    b, h, w, c = _pool_train_checks(x, "x", ((x, "x", None),), 1)
+    dev = x.device
+    out = torch.empty((b, h // 2, w // 2, c), dtype=torch.float32, device=dev)
+    which = torch.empty(train_unit_sizes(_lib.UNIT_POOL, c, b, h, w)[1], dtype=torch.uint8, device=dev).view(out.shape)
+    launch("balf_pool_train_forward", dev, x, b, h, w, c, out, which)
+    return PoolTrainForward(out, which)
+
+
+def pool_train_backward(g: torch.Tensor, which: torch.Tensor) -> torch.Tensor:
+    """The backward of ``pool_train_forward`` (balf_pool_train_backward): ``g`` [B,H/2,W/2,C] and that forward's ``which`` ->
+    ``dx`` [B,H,W,C], every element written: g at the recorded position, +0 at the other three."""
+    b, ho, wo, c = _pool_train_checks(g, "g", ((g, "g", None), (which, "which", tuple(g.shape))), 2)
+    dev = g.device
+    dx = torch.empty((b, 2 * ho, 2 * wo, c), dtype=torch.float32, device=dev)
+    launch("balf_pool_train_backward", dev, g, which, b, 2 * ho, 2 * wo, c, dx)
+    return dx
 
 
 LINRELU_PARAMS = ("weight", "bias")       # of the Linear c_in -> 2 c_in in front of a ReLU (down4.conv.0 at c_in = 128)

@@ -235,8 +235,9 @@ def _guarded_features(model, encode_chunk):
 def train_head(dataloader, model, head, optimizer, device, grid_size=8, chunk_batches=16, noise=None) -> float:
     """One epoch of the reference's training step (train_utils.py:104-124) for the trainable tail alone: ``model``'s encoder is
     frozen and runs on the forward kernels (``model.encode``), ``head`` (``model.head_train.TrainableHead``, or one of
-    ``model.tail_train.TrainableTail``, ``model.mixer_train.TrainableMixerTail`` and ``model.stage4_train.TrainableStage4`` -- all
-    of stage 4 --, whose ``encode_level`` attribute selects ``model.encode(x, level=...)``) runs forward in
+    ``model.tail_train.TrainableTail``, ``model.mixer_train.TrainableMixerTail``, ``model.stage4_train.TrainableStage4`` -- all
+    of stage 4 -- and ``model.stage3_train.TrainableStage3`` -- stages 3 and 4 --, whose ``encode_level`` attribute selects
+    ``model.encode(x, level=...)``) runs forward in
     training mode and backward on the library, ``optimizer`` (any ``torch.optim.Optimizer`` over ``head.parameters()``; the intended
     one is ``balf_amd.optim.FusedAdam``, one launch per step, which ``build_optimizer`` returns) steps once per loader batch.
     ``dataloader`` yields the reference's 6-tuples ``(images_src, images_dst, heatmap_src, heatmap_dst, h_src_2_dst,

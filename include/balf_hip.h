@@ -656,6 +656,20 @@ int balf_rcab_train_backward(const float *dx2_dev, const float *y_dev, const flo
                              int Wc, float *dln_g_dev, float *dln_b_dev, float *dwc1_dev, float *dbc1_dev, float *dwc2_dev,
                              float *dbc2_dev, float *dws0_dev, float *dbs0_dev, float *dws2_dev, float *dbs2_dev, float *dy_dev,
                              void *workspace_dev, size_t workspace_bytes, void *stream);
+/* The same block at C channels, C = 256 (stage 4; what the two functions above call) or 128 (stage 3's, under
+ * down3.residual_channel_attention_block.); any other C gives BALF_ERR_SHAPE.  Read C for 256 and C / 4 for 64 in everything
+ * above.  At C = 128 a LayerNorm row is a half-wave, two pixels per wave, the butterfly 16..1 inside the half-wave; the column
+ * kernels run C threads per workgroup.  The sizes of saved_dev and workspace_dev at C come from balf_train_unit_sizes. */
+int balf_rcab_train_forward_c(const float *y_dev, const float *r_dev, const float *ln_g_dev, const float *ln_b_dev,
+                              const float *wc1_dev, const float *bc1_dev, const float *wc2_dev, const float *bc2_dev,
+                              const float *ws0_dev, const float *bs0_dev, const float *ws2_dev, const float *bs2_dev, int B, int Hc,
+                              int Wc, int C, float *x2_dev, void *saved_dev, void *workspace_dev, size_t workspace_bytes,
+                              void *stream);
+int balf_rcab_train_backward_c(const float *dx2_dev, const float *y_dev, const float *ln_g_dev, const float *wc1_dev,
+                               const float *wc2_dev, const float *ws0_dev, const float *ws2_dev, const void *saved_dev, int B, int Hc,
+                               int Wc, int C, float *dln_g_dev, float *dln_b_dev, float *dwc1_dev, float *dbc1_dev, float *dwc2_dev,
+                               float *dbc2_dev, float *dws0_dev, float *dbs0_dev, float *dws2_dev, float *dbs2_dev, float *dy_dev,
+                               void *workspace_dev, size_t workspace_bytes, void *stream);
 /* After a forward whose last micro-batch of B images is resident in workspace_dev (the rules and error codes of
  * balf_forward_stage_view): r_dev [B,Hp/8,Wp/8,256] = the forward's own y + x0, copied; x0 = relu(x3 W^T + b) computed again from
  * the resident stage-3 output (view 3, de-fragmented on the split-f16 path) with the training GEMM and conv0_w_dev [256,128],
@@ -715,6 +729,16 @@ int balf_gmlp_train_forward(const float *x0_dev, const float *const *params, int
 int balf_gmlp_train_backward(const float *dy_dev, const float *x0_dev, const float *const *params, const void *saved_dev, int B,
                              int Hc, int Wc, float *const *grads, float *dx0_dev, void *workspace_dev, size_t workspace_bytes,
                              void *stream);
+/* The same layer at C channels, C = 256 (stage 4; what the two functions above call) or 128 (stage 3's, under
+ * down3.residual_split_head_multi_axis_gmlp_layer.); any other C gives BALF_ERR_SHAPE.  Read C for 256 and 2C for 512 in
+ * everything above; the token matrices stay [64,64].  At C = 128 the token-mix kernels run two waves per group (wave w owns
+ * channels 64 w .. 64 w + 63 as before), so dWt / dbt have 2 wave partials per workgroup instead of 4, added in the same fixed
+ * order.  The sizes of saved_dev and workspace_dev at C come from balf_train_unit_sizes. */
+int balf_gmlp_train_forward_c(const float *x0_dev, const float *const *params, int B, int Hc, int Wc, int C, float *y_dev,
+                              void *saved_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+int balf_gmlp_train_backward_c(const float *dy_dev, const float *x0_dev, const float *const *params, const void *saved_dev, int B,
+                               int Hc, int Wc, int C, float *const *grads, float *dx0_dev, void *workspace_dev,
+                               size_t workspace_bytes, void *stream);
 /* After a forward whose last micro-batch of B images is resident in workspace_dev (the rules and error codes of
  * balf_forward_stage_view): x0_dev [B,Hp/8,Wp/8,256] = relu(x3 W^T + b), computed from the resident stage-3 output with the
  * training GEMM exactly as balf_forward_rcab_inputs computes it (the same bits).  scratch_dev: B * Hp/8 * Wp/8 * 128 floats for the
@@ -746,6 +770,34 @@ int balf_linrelu_train_forward(const float *x_dev, const float *w_dev, const flo
 int balf_linrelu_train_backward(const float *g_dev, const float *y_dev, const float *x_dev, const float *w_dev, int N, int c_in,
                                 float *dw_dev, float *db_dev, float *dx_dev, void *workspace_dev, size_t workspace_bytes,
                                 void *stream);
+
+/* ---- the 2 x 2 max-pool that ends a Down stage, in training form ------------------------------------------------
+ * x_dev [B,H,W,C] float32 NHWC -> out_dev [B,H/2,W/2,C] and which_dev [B,H/2,W/2,C] uint8: the raster position 0..3 of the chosen
+ * element in its 2 x 2 window, (0,0), (0,1), (1,0), (1,1).  H x W is the INPUT map.
+ *   forward    the rule of torch's CPU max_pool2d: the window is scanned in raster order and a value replaces the current one when
+ *              it is greater or is NaN, so the first maximum wins, of +0 / -0 the first, of several NaN the last.  out has the
+ *              chosen element's bits.
+ *   backward   g_dev [B,H/2,W/2,C] and which_dev -> dx_dev [B,H,W,C]: g at the recorded position and +0.0f at the other three.
+ *              EVERY element of dx is written (no memset is needed, none is made); nothing but g and which is read.
+ * A thread handles four consecutive channels of an output pixel with 16-byte accesses (which: 4 bytes).  Nothing is summed, no
+ * atomics, no workspace.  Stream-ordered, nothing synchronised, allocated or read back, capturable.  Launches: 1 each.
+ * Limits: 1 <= B <= 65535, H, W >= 1 (BALF_ERR_ARG); H and W even, C a multiple of 4 in 4..256, B * H * W <= 2^24
+ * (BALF_ERR_SHAPE); no NULL pointer, every pointer 16-byte aligned (BALF_ERR_ARG). */
+int balf_pool_train_forward(const float *x_dev, int B, int H, int W, int C, float *out_dev, unsigned char *which_dev, void *stream);
+int balf_pool_train_backward(const float *g_dev, const unsigned char *which_dev, int B, int H, int W, int C, float *dx_dev,
+                             void *stream);
+
+/* ---- the buffer sizes of the training units that take their channel width ------------------------------------
+ * *workspace_bytes and *saved_bytes of unit at width C on B images whose map, as the unit receives it, is Hc x Wc.
+ *   BALF_UNIT_RCAB  balf_rcab_train_*_c, C = 128 or 256; at 256 what balf_rcab_train_workspace_bytes / _saved_bytes return
+ *   BALF_UNIT_GMLP  balf_gmlp_train_*_c, C = 128 or 256; at 256 what balf_gmlp_train_workspace_bytes / _saved_bytes return
+ *   BALF_UNIT_POOL  balf_pool_train_*: Hc x Wc is the pool's INPUT map; saved is which, B * Hc/2 * Wc/2 * C bytes; workspace is 0
+ * Returns BALF_OK, or the code that the unit's entry points give for these sizes (a C the unit does not take: BALF_ERR_SHAPE);
+ * an unknown unit or a NULL output: BALF_ERR_ARG.  The two outputs are written only with BALF_OK. */
+#define BALF_UNIT_RCAB 0
+#define BALF_UNIT_GMLP 1
+#define BALF_UNIT_POOL 2
+int balf_train_unit_sizes(int unit, int C, int B, int Hc, int Wc, size_t *workspace_bytes, size_t *saved_bytes);
 
 /* ---- the optimiser step over many tensors in one launch ---------------------------------------------------------
  * balf_adam_step: one step of torch.optim.Adam (amsgrad=False, maximize=False, L2 weight decay) on n float32 tensors.  p, g, m, v
