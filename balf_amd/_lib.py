@@ -90,6 +90,9 @@ PROTOTYPES = {
     "balf_synth_pairs_workspace_bytes": (_sz, [_i, _i]),
     "balf_synth_pairs": (_i, [_vp, _sz, _vp, _vp, _i, _vp, _vp, _vp, _fp, _i, _vp, _i, _i, _fp, _fp, _fp, _fp, _vp, _vp, _sz,
                              _vp]),
+    "balf_photometric_u8": (_i, [_vp, _sz, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp]),
+    "balf_synth_train_pairs": (_i, [_vp, _sz, _vp, _vp, _i, _vp, _vp, _vp, _fp, _i, _vp, _i, _i, _fp, _fp, _fp, _fp, _vp, _vp, _sz,
+                                   _vp, _vp, _vp]),
     "balf_detector_loss_workspace_bytes": (_sz, [_i, _i, _i]),
     "balf_detector_loss": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _fp, _fp, _vp, _fp, _vp, _sz, _vp]),
     "balf_head_train_workspace_bytes": (_sz, [C.c_long]),

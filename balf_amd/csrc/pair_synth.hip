@@ -23,6 +23,21 @@
 //                          inside the destination window (apply_homography_to_source_labels_torch as it returns, :200-219).
 //                          Every store is 1.0f: duplicates need no atomics and no order.  The workgroup maxima of the image
 //                          kernel are reduced to dst_max (max is exact: no order dependence).
+//   balf_synth_train_pairs   the TRAINING task's pairs (COCO.py:70-75, task == 'train'): the same two launches, the image kernel
+//     in its training form (synth_image_kernel<true>): the destination patch is the warp of bgr_photometric_to_rgb(image), and
+//     the distorted image is never formed: each of the four taps of an output pixel is distorted, all three channels, before
+//     the integer interpolation; a tap outside the image contributes 0 (the reference pads the DISTORTED image with zeros).
+//     Side-1 workgroups build the pair's PhotoTables in LDS (3 KiB) before the barrier they already have.
+//   balf_photometric_u8      bgr_distorsion (dataset_utils.py:81-121) of whole packed images with given parameters: one launch,
+//     photometric_kernel     grid (blocks, B), 256 threads, four pixels (12 bytes, three dwords where the image is 4-byte aligned)
+//                            per thread and step of a grid-stride loop.
+//   photo_distort            the ONE distortion function of both kernels.  The value maps that depend on the pair's float64
+//                            parameters (brightness + first contrast, saturation, hue, second contrast) and OpenCV's sdiv /
+//                            hdiv tables are 256-entry LDS tables (PhotoTables, one entry per thread: the float64 work happens
+//                            there and nowhere else); per pixel the rest is integer arithmetic and the float32 HSV -> BGR of
+//                            OpenCV's scalar 8-bit code, fp contraction off.  Every table index is a byte read from a table or
+//                            from the image, so no index leaves its table whatever bits the parameters hold.
+//                            The two conversions are DEFINED by that scalar code (include/balf_hip.h); cv2 parity is UNPINNED.
 // This follows OpenCV's 8-bit INTER_LINEAR remap as documented; parity with cv2 itself is UNPINNED (checked against the
 // tests' integer restatement of the same algorithm only), like the masks (common_mask.h) and the resize (resize_repeat.hip).
 // fp contraction is OFF wherever a float expression is compared against the reference (the label warp; common_mask.h).
@@ -52,14 +67,96 @@ struct SynthArgs {
     float *heat_src, *heat_dst;             // [P, 1, patch, patch]
     int *dst_max;                           // [P]
     int *blk_max;                           // [P, nblk] workspace
+    const double *photo;                    // [P, 5] (delta_b, alpha1, sat, hue, alpha2); balf_synth_train_pairs only, else null
+    const int *perm;                        // [P] row of kPerms; null with photo
 };
 
 constexpr int kFarAway = 1 << 24;
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
+// ---- the photometric distortion of the training task (dataset_utils.py:76-121) ----------------------------------------------
+constexpr int kNumPerms = 6;
+// the reference's perms, row r in bits 6r .. 6r + 5, two bits per entry: out_bgr[k] = bgr[perms[r][k]]
+constexpr unsigned long long perm_row(int a, int b, int c) { return (unsigned long long)(a | (b << 2) | (c << 4)); }
+constexpr unsigned long long kPerms = perm_row(0, 1, 2) | perm_row(0, 2, 1) << 6 | perm_row(1, 0, 2) << 12 | perm_row(1, 2, 0) << 18 |
+                                      perm_row(2, 0, 1) << 24 | perm_row(2, 1, 0) << 30;
+constexpr int kPhotoThreads = 256;          // one table entry per thread: both kernels that distort run 256 threads
+
+struct PhotoTables {
+    int sdiv[256], hdiv[256];               // OpenCV's RGB2HSV_b tables, hrange 180, hsv_shift 12
+    unsigned char pre[256], sat[256], hue[256], post[256];      // steps 1, 3, 4 and 6 of include/balf_hip.h as byte -> byte maps
+};
+
+__device__ __forceinline__ double clamp255(double x) {           // check_margins: two comparisons, a NaN passes
+    x = x > 255.0 ? 255.0 : x;
+    return x < 0.0 ? 0.0 : x;
+}
+
+// entry i of every table from prm = (delta_b, alpha1, sat, hue, alpha2); the caller's barrier publishes them
+__device__ __forceinline__ void photo_build(PhotoTables &t, const double *prm, int i) {
+#pragma clang fp contract(off)
+    const double x = (double)i;
+    t.sdiv[i] = i ? (int)rint((double)(255 << 12) / x) : 0;
+    t.hdiv[i] = i ? (int)rint((double)(180 << 12) / (6.0 * x)) : 0;
+    t.pre[i] = (unsigned char)(int)clamp255(clamp255(x + prm[0]) * prm[1]);
+    t.sat[i] = (unsigned char)(int)clamp255(x * prm[2]);
+    double h = x + prm[3];
+    h = h > 360.0 ? h - 360.0 : h;
+    h = h < 0.0 ? h + 360.0 : h;
+    t.hue[i] = (unsigned char)((int)h & 255);                    // astype(np.uint8) of 324..359: 68..103, as the reference
+    t.post[i] = (unsigned char)(int)clamp255(x * prm[4]);
+}
+
+__device__ __forceinline__ int sel3(int i, int v0, int v1, int v2) { return i == 0 ? v0 : (i == 1 ? v1 : v2); }
+
+// rint(x * 255.f) saturated to a byte (saturate_cast<uchar>: half to even)
+__device__ __forceinline__ int to_u8(float x) {
+#pragma clang fp contract(off)
+    const float y = __builtin_rintf(x * 255.0f);
+    return y < 0.0f ? 0 : (y > 255.0f ? 255 : (int)y);
+}
+
+// one pixel through steps 1-7; perm_bits = the six bits of the pair's row of kPerms
+__device__ __forceinline__ void photo_distort(const PhotoTables &t, unsigned perm_bits, int &b, int &g, int &r) {
+#pragma clang fp contract(off)
+    b = t.pre[b];
+    g = t.pre[g];
+    r = t.pre[r];
+    // RGB2HSV_b
+    int v = b > g ? b : g, vmin = b < g ? b : g;
+    v = r > v ? r : v;
+    vmin = r < vmin ? r : vmin;
+    const int diff = v - vmin;
+    const int s0 = (diff * t.sdiv[v] + (1 << 11)) >> 12;
+    const int h0 = v == r ? g - b : (v == g ? b - r + 2 * diff : r - g + 4 * diff);
+    int hq = (h0 * t.hdiv[diff] + (1 << 11)) >> 12;
+    hq += hq < 0 ? 180 : 0;
+    const int S = t.sat[s0 & 255], H = t.hue[hq & 255];          // (s0 <= 255 and 0 <= hq < 180 already: the masks cost nothing)
+    // HSV2RGB_b: OpenCV's float32 path
+    const float s = (float)S * (1.0f / 255.0f), vv = (float)v * (1.0f / 255.0f);
+    float fb = vv, fg = vv, fr = vv;
+    if (S != 0) {
+        float hh = (float)H * (6.0f / 180.0f);
+        hh = hh >= 6.0f ? hh - 6.0f : hh;                         // (H <= 255: hh < 9, once is enough)
+        int sector = (int)hh;                                    // floor: hh >= 0
+        const float f = hh - (float)sector;
+        sector = sector > 5 ? 5 : sector;
+        const float tab1 = vv * (1.0f - s), tab2 = vv * (1.0f - s * f), tab3 = vv * (1.0f - s * (1.0f - f));
+        // sector_data: {1,3,0}, {1,0,2}, {3,0,1}, {0,2,1}, {0,1,3}, {2,1,0} -> (b, g, r)
+        fb = sector == 0 || sector == 1 ? tab1 : (sector == 2 ? tab3 : (sector == 5 ? tab2 : vv));
+        fg = sector == 0 ? tab3 : (sector == 1 || sector == 2 ? vv : (sector == 3 ? tab2 : tab1));
+        fr = sector == 0 || sector == 5 ? vv : (sector == 1 ? tab2 : (sector == 4 ? tab3 : tab1));
+    }
+    const int pb = t.post[to_u8(fb)], pg = t.post[to_u8(fg)], pr = t.post[to_u8(fr)];
+    b = sel3(perm_bits & 3, pb, pg, pr);
+    g = sel3((perm_bits >> 2) & 3, pb, pg, pr);
+    r = sel3((perm_bits >> 4) & 3, pb, pg, pr);
+}
+
 struct PairGeom {
-    bool img_ok, win_ok;                    // the image lies inside the packed buffer; both windows lie inside the image
+    bool img_ok, win_ok;                    // the image lies inside the packed buffer; both windows lie inside the image (and, in
+                                            // the training form, perm names a row of kPerms): the pair is synthesised as asked
     int h, w, top[2], left[2];
     const unsigned char *img;
 };
@@ -81,6 +178,7 @@ __device__ __forceinline__ PairGeom pair_geom(const SynthArgs &a, int p) {
         g.top[s] = clampi(g.top[s], -kFarAway, kFarAway);        // (a window far outside: no overflow in top + row below)
         g.left[s] = clampi(g.left[s], -kFarAway, kFarAway);
     }
+    if (a.perm) g.win_ok = g.win_ok && (unsigned)a.perm[p] < (unsigned)kNumPerms;
     return g;
 }
 
@@ -98,14 +196,45 @@ __device__ __forceinline__ void store_px(float *out, const float (&v)[kImgPx], i
     }
 }
 
+template <bool kTrain> struct PhotoLds {};                       // the tables take LDS in the training form only
+template <> struct PhotoLds<true> { PhotoTables t; };
+
+// the three channels of the pixel at (y, x) as the training task sees them, in the packed image's R, G, B order: distorted
+// (the packed images are RGB: blue is px[2]), all 0 outside the image -- NOT the distortion of a black pixel
+__device__ __forceinline__ void tap_photo(const PairGeom &g, const PhotoTables &t, unsigned perm_bits, int y, int x, int (&v)[3]) {
+    v[0] = v[1] = v[2] = 0;
+    if (y >= 0 && y < g.h && x >= 0 && x < g.w) {
+        const unsigned char *px = g.img + ((long)y * g.w + x) * 3;
+        int b = px[2], gr = px[1], r = px[0];
+        photo_distort(t, perm_bits, b, gr, r);
+        v[0] = r;
+        v[1] = gr;
+        v[2] = b;
+    }
+}
+
+// kTrain: the destination side warps the photometrically distorted image (balf_synth_train_pairs); everything else is shared
+template <bool kTrain>
 __global__ __launch_bounds__(kImgThreads) void synth_image_kernel(SynthArgs a) {
+    static_assert(kImgThreads == kPhotoThreads, "one table entry per thread");
     __shared__ float s_norm[256];
     __shared__ double s_m[9];
     __shared__ int s_inv_ok;
     __shared__ int s_red[kImgThreads / 64];
+    __shared__ PhotoLds<kTrain> s_photo;
     const int p = blockIdx.z, side = blockIdx.y, tid = threadIdx.x;
     s_norm[tid] = (float)((double)tid / 255.0);                  // (kImgThreads == 256: one entry per thread)
     const PairGeom g = pair_geom(a, p);
+    unsigned perm_bits = 0;
+    bool perm_ok = true;
+    if constexpr (kTrain) {
+        if (side == 1) {
+            photo_build(s_photo.t, a.photo + 5 * (long)p, tid);
+            const int pm = a.perm[p];
+            perm_ok = (unsigned)pm < (unsigned)kNumPerms;
+            perm_bits = perm_ok ? (unsigned)(kPerms >> (6 * pm)) & 63u : 0u;
+        }
+    }
     if (side == 1 && tid == 0) {
         double ih[9], m[9];
         for (int k = 0; k < 9; ++k) ih[k] = a.inv_h[9 * (long)p + k];
@@ -131,7 +260,7 @@ __global__ __launch_bounds__(kImgThreads) void synth_image_kernel(SynthArgs a) {
                 v8[1][j] = px[1];
                 v8[2][j] = px[2];
             }
-        } else if (g.img_ok && s_inv_ok) {
+        } else if (g.img_ok && s_inv_ok && perm_ok) {
             const int y = g.top[1] + row;
             for (int j = 0; j < n; ++j) {
                 int sx, sy, fx, fy;
@@ -139,11 +268,24 @@ __global__ __launch_bounds__(kImgThreads) void synth_image_kernel(SynthArgs a) {
                 const int w00 = (32 - fx) * (32 - fy) * 32, w01 = fx * (32 - fy) * 32, w10 = (32 - fx) * fy * 32,
                           w11 = fx * fy * 32;
                 // (a tap more than one pixel outside has all four reads refused by tap_u8; sx + 1 cannot overflow: |sx| < 2^26)
-                for (int c = 0; c < 3; ++c) {
-                    const int sum = tap_u8(g, sy, sx, c) * w00 + tap_u8(g, sy, sx + 1, c) * w01 + tap_u8(g, sy + 1, sx, c) * w10 +
-                                    tap_u8(g, sy + 1, sx + 1, c) * w11;
-                    v8[c][j] = (sum + 16384) >> 15;
-                    vmax = v8[c][j] > vmax ? v8[c][j] : vmax;
+                if constexpr (kTrain) {
+                    int t00[3], t01[3], t10[3], t11[3];
+                    tap_photo(g, s_photo.t, perm_bits, sy, sx, t00);
+                    tap_photo(g, s_photo.t, perm_bits, sy, sx + 1, t01);
+                    tap_photo(g, s_photo.t, perm_bits, sy + 1, sx, t10);
+                    tap_photo(g, s_photo.t, perm_bits, sy + 1, sx + 1, t11);
+                    for (int c = 0; c < 3; ++c) {
+                        const int sum = t00[c] * w00 + t01[c] * w01 + t10[c] * w10 + t11[c] * w11;
+                        v8[c][j] = (sum + 16384) >> 15;
+                        vmax = v8[c][j] > vmax ? v8[c][j] : vmax;
+                    }
+                } else {
+                    for (int c = 0; c < 3; ++c) {
+                        const int sum = tap_u8(g, sy, sx, c) * w00 + tap_u8(g, sy, sx + 1, c) * w01 +
+                                        tap_u8(g, sy + 1, sx, c) * w10 + tap_u8(g, sy + 1, sx + 1, c) * w11;
+                        v8[c][j] = (sum + 16384) >> 15;
+                        vmax = v8[c][j] > vmax ? v8[c][j] : vmax;
+                    }
                 }
             }
         }
@@ -271,22 +413,76 @@ SynthWs synth_layout(int P, int patch, void *base = nullptr) {
     return {blk_max, c.used};
 }
 
-}  // namespace
-}  // namespace balf
+// ---- balf_photometric_u8: whole images --------------------------------------------------------------------------------------
+constexpr int kPhotoPx = 4;                 // pixels per thread and step: 12 bytes, three dwords
+constexpr int kPhotoMaxBlocks = 4096;
 
-using namespace balf;
+struct PhotoArgs {
+    const unsigned char *packed;
+    size_t packed_bytes;
+    const long long *offsets;               // [B]
+    const int *sizes;                       // [B, 2] (h, w)
+    const double *params;                   // [B, 5]
+    const int *perm;                        // [B]
+    int blue_idx;                           // 0: the pixels are B, G, R; 2: R, G, B
+    unsigned char *out;
+};
 
-extern "C" size_t balf_synth_pairs_workspace_bytes(int P, int patch) {
-    if (!sizes_ok(P, patch)) return 0;
-    return synth_layout(P, patch).total;
+__global__ __launch_bounds__(kPhotoThreads) void photometric_kernel(PhotoArgs a) {
+    __shared__ PhotoTables s_t;
+    const int b = blockIdx.y, tid = threadIdx.x;
+    photo_build(s_t, a.params + 5 * (long)b, tid);
+    __syncthreads();
+    const int h = a.sizes[2 * b], w = a.sizes[2 * b + 1];
+    const long long off = a.offsets[b];
+    // (h * w <= 2^62: the product by 3 is formed only once it is known to be small)
+    if (h <= 0 || w <= 0 || off < 0 || (unsigned long long)off > a.packed_bytes) return;
+    const unsigned long long npx = (unsigned long long)h * (unsigned long long)w;
+    if (npx > (a.packed_bytes - (unsigned long long)off) / 3) return;                 // the image leaves the buffer: not written
+    const int pm = a.perm[b];
+    const bool perm_ok = (unsigned)pm < (unsigned)kNumPerms;
+    const unsigned perm_bits = perm_ok ? (unsigned)(kPerms >> (6 * pm)) & 63u : 0u;
+    const unsigned char *in = a.packed + off;
+    unsigned char *out = a.out + off;
+    const bool dwords = (((uintptr_t)in | (uintptr_t)out) & 3u) == 0;
+    const int bi = a.blue_idx;
+    const unsigned long long groups = (npx + kPhotoPx - 1) / kPhotoPx;
+    for (unsigned long long q = (unsigned long long)blockIdx.x * kPhotoThreads + tid; q < groups;
+         q += (unsigned long long)gridDim.x * kPhotoThreads) {
+        const unsigned long long px0 = q * kPhotoPx;
+        const int n = npx - px0 < (unsigned long long)kPhotoPx ? (int)(npx - px0) : kPhotoPx;
+        const bool whole = dwords && n == kPhotoPx;
+        unsigned char v[3 * kPhotoPx] = {};
+        if (whole) {
+            const uint3 d = *reinterpret_cast<const uint3 *>(in + 3 * px0);          // 12-byte groups of a 4-byte aligned image
+            const unsigned dw[3] = {d.x, d.y, d.z};
+            for (int k = 0; k < 3 * kPhotoPx; ++k) v[k] = (unsigned char)(dw[k >> 2] >> (8 * (k & 3)));
+        } else {
+            for (int k = 0; k < 3 * n; ++k) v[k] = in[3 * px0 + k];
+        }
+        for (int j = 0; j < kPhotoPx; ++j) {
+            int cb = v[3 * j + bi], cg = v[3 * j + 1], cr = v[3 * j + 2 - bi];
+            photo_distort(s_t, perm_bits, cb, cg, cr);
+            v[3 * j + bi] = (unsigned char)(perm_ok ? cb : 0);                        // a perm outside the table: a black image
+            v[3 * j + 1] = (unsigned char)(perm_ok ? cg : 0);
+            v[3 * j + 2 - bi] = (unsigned char)(perm_ok ? cr : 0);
+        }
+        if (whole) {
+            unsigned dw[3] = {0u, 0u, 0u};
+            for (int k = 0; k < 3 * kPhotoPx; ++k) dw[k >> 2] |= (unsigned)v[k] << (8 * (k & 3));
+            *reinterpret_cast<uint3 *>(out + 3 * px0) = make_uint3(dw[0], dw[1], dw[2]);
+        } else {
+            for (int k = 0; k < 3 * n; ++k) out[3 * px0 + k] = v[k];
+        }
+    }
 }
 
-extern "C" int balf_synth_pairs(const unsigned char *packed_dev, size_t packed_bytes, const long long *offsets_dev,
-                                const int32_t *sizes_dev, int P, const double *inv_h_dev, const int32_t *win_src_dev,
-                                const int32_t *win_dst_dev, const float *pts_dev, int pts_total, const int32_t *pts_offsets_dev,
-                                int top_k, int patch, float *img_src_dev, float *img_dst_dev, float *heat_src_dev,
-                                float *heat_dst_dev, int32_t *dst_max_dev, void *workspace_dev, size_t workspace_bytes,
-                                void *stream) {
+// both pair entries: photo_dev / perm_dev null = the validation task
+int synth_pairs_launch(const unsigned char *packed_dev, size_t packed_bytes, const long long *offsets_dev, const int32_t *sizes_dev,
+                       int P, const double *inv_h_dev, const int32_t *win_src_dev, const int32_t *win_dst_dev, const float *pts_dev,
+                       int pts_total, const int32_t *pts_offsets_dev, int top_k, int patch, float *img_src_dev, float *img_dst_dev,
+                       float *heat_src_dev, float *heat_dst_dev, int32_t *dst_max_dev, void *workspace_dev, size_t workspace_bytes,
+                       const double *photo_dev, const int32_t *perm_dev, void *stream) {
     // (no label rows at all, pts_total == 0, may come with a null pts_dev: an empty tensor has none)
     if (!packed_dev || !offsets_dev || !sizes_dev || !inv_h_dev || !win_src_dev || !win_dst_dev || (!pts_dev && pts_total != 0) ||
         !pts_offsets_dev || !img_src_dev || !img_dst_dev || !heat_src_dev || !heat_dst_dev || !dst_max_dev || !workspace_dev)
@@ -319,9 +515,62 @@ extern "C" int balf_synth_pairs(const unsigned char *packed_dev, size_t packed_b
     a.heat_dst = heat_dst_dev;
     a.dst_max = dst_max_dev;
     a.blk_max = ws.blk_max;
-    synth_image_kernel<<<dim3(a.nblk, 2, P), kImgThreads, 0, st>>>(a);
+    a.photo = photo_dev;
+    a.perm = perm_dev;
+    if (photo_dev)
+        synth_image_kernel<true><<<dim3(a.nblk, 2, P), kImgThreads, 0, st>>>(a);
+    else
+        synth_image_kernel<false><<<dim3(a.nblk, 2, P), kImgThreads, 0, st>>>(a);
     BALF_LAUNCH_CHECK();
     synth_labels_kernel<<<P, kLblThreads, 0, st>>>(a);
+    BALF_LAUNCH_CHECK();
+    return BALF_OK;
+}
+
+}  // namespace
+}  // namespace balf
+
+using namespace balf;
+
+extern "C" size_t balf_synth_pairs_workspace_bytes(int P, int patch) {
+    if (!sizes_ok(P, patch)) return 0;
+    return synth_layout(P, patch).total;
+}
+
+extern "C" int balf_synth_pairs(const unsigned char *packed_dev, size_t packed_bytes, const long long *offsets_dev,
+                                const int32_t *sizes_dev, int P, const double *inv_h_dev, const int32_t *win_src_dev,
+                                const int32_t *win_dst_dev, const float *pts_dev, int pts_total, const int32_t *pts_offsets_dev,
+                                int top_k, int patch, float *img_src_dev, float *img_dst_dev, float *heat_src_dev,
+                                float *heat_dst_dev, int32_t *dst_max_dev, void *workspace_dev, size_t workspace_bytes,
+                                void *stream) {
+    return synth_pairs_launch(packed_dev, packed_bytes, offsets_dev, sizes_dev, P, inv_h_dev, win_src_dev, win_dst_dev, pts_dev,
+                              pts_total, pts_offsets_dev, top_k, patch, img_src_dev, img_dst_dev, heat_src_dev, heat_dst_dev,
+                              dst_max_dev, workspace_dev, workspace_bytes, nullptr, nullptr, stream);
+}
+
+extern "C" int balf_synth_train_pairs(const unsigned char *packed_dev, size_t packed_bytes, const long long *offsets_dev,
+                                      const int32_t *sizes_dev, int P, const double *inv_h_dev, const int32_t *win_src_dev,
+                                      const int32_t *win_dst_dev, const float *pts_dev, int pts_total,
+                                      const int32_t *pts_offsets_dev, int top_k, int patch, float *img_src_dev, float *img_dst_dev,
+                                      float *heat_src_dev, float *heat_dst_dev, int32_t *dst_max_dev, void *workspace_dev,
+                                      size_t workspace_bytes, const double *params_dev, const int32_t *perm_dev, void *stream) {
+    if (!params_dev || !perm_dev) return BALF_ERR_ARG;
+    return synth_pairs_launch(packed_dev, packed_bytes, offsets_dev, sizes_dev, P, inv_h_dev, win_src_dev, win_dst_dev, pts_dev,
+                              pts_total, pts_offsets_dev, top_k, patch, img_src_dev, img_dst_dev, heat_src_dev, heat_dst_dev,
+                              dst_max_dev, workspace_dev, workspace_bytes, params_dev, perm_dev, stream);
+}
+
+extern "C" int balf_photometric_u8(const unsigned char *packed_dev, size_t packed_bytes, const long long *offsets_dev,
+                                   const int32_t *sizes_dev, int B, const double *params_dev, const int32_t *perm_dev, int blue_idx,
+                                   unsigned char *out_dev, void *stream) {
+    if (!packed_dev || !offsets_dev || !sizes_dev || !params_dev || !perm_dev || !out_dev) return BALF_ERR_ARG;
+    if (B <= 0 || B > kMaxPairs || (blue_idx != 0 && blue_idx != 2)) return BALF_ERR_ARG;
+    PhotoArgs a{packed_dev, packed_bytes, offsets_dev, sizes_dev, params_dev, perm_dev, blue_idx, out_dev};
+    // the sizes live on the device: twice the blocks an image of the average size needs, the grid-stride loop takes the rest
+    const size_t per_block = (size_t)3 * kPhotoPx * kPhotoThreads;
+    size_t blocks = 2 * ((packed_bytes / (size_t)B + per_block) / per_block);
+    blocks = blocks > (size_t)kPhotoMaxBlocks ? (size_t)kPhotoMaxBlocks : blocks;
+    photometric_kernel<<<dim3((unsigned)blocks, B), kPhotoThreads, 0, static_cast<hipStream_t>(stream)>>>(a);
     BALF_LAUNCH_CHECK();
     return BALF_OK;
 }

@@ -9,6 +9,12 @@ crops, heat maps) is ``balf_synth_pairs`` (datasets/synthetic_pairs.py).  The tw
 written out (``getRotationMatrix2D`` in closed form, ``getPerspectiveTransform`` as the 8 x 8 float64 solve); their last
 bits against a cv2 build are UNPINNED.
 
+The photometric distortion of the TRAINING task (reference :10-12, :76-134): ``sample_photometric`` draws ``bgr_distorsion``'s
+random numbers on the host, in its order and with its quirks, and ``balf_photometric_u8`` (whole images: ``bgr_distorsion``,
+``bgr_photometric_to_rgb``) or ``balf_synth_train_pairs`` (only the destination window, datasets/synthetic_pairs.py) applies
+them.  The two cv2 colour conversions are defined in include/balf_hip.h by OpenCV's scalar 8-bit code; parity with a cv2 build
+is UNPINNED.
+
 PARITY of the resize is UNPINNED: the reference resizes with ``cv2.resize`` and crops with imgaug, neither of which is
 available where this library is built.  The 8-bit arithmetic is defined in include/balf_hip.h after OpenCV's documented
 INTER_LINEAR scheme and has not been checked against a cv2 build."""
@@ -78,6 +84,72 @@ def ratio_preserving_resize(img, target_size):
     img = np.asarray(img)
     out = ratio_preserving_resize_batch([img], target_size)[0].cpu().numpy()
     return out[..., None] if img.ndim == 3 and img.shape[2] == 1 else out
+
+
+# ---- the training task's photometric distortion -----------------------------------------------------------------------------
+perms = ((0, 1, 2), (0, 2, 1),
+         (1, 0, 2), (1, 2, 0),
+         (2, 0, 1), (2, 1, 0))
+PHOTOMETRIC_NEUTRAL = (0.0, 1.0, 1.0, 0.0, 1.0)
+
+
+def sample_photometric(rng=None, lower=.5, upper=1.5, delta=18.0, delta_brigtness=36):
+    """The random numbers of one ``bgr_distorsion`` call (reference :81-121), from ``np.random`` or the ``RandomState`` passed
+    as ``rng``, in the reference's order: a coin before every step, its value only when the coin fell.  -> dict ``params``
+    float64 [5] = (delta_b, alpha1, sat, hue, alpha2) and ``perm`` (a row of ``perms``); a step that did not fire has its
+    neutral value (``PHOTOMETRIC_NEUTRAL``, perm 0), which makes it the identity bit for bit.  The reference's quirks are
+    kept: the brightness branch OVERWRITES ``delta``, so the hue is then drawn from ``uniform(-brightness, brightness)``; the
+    second contrast gain is drawn only when the first was."""
+    rng = np.random if rng is None else rng
+    delta_b = 0.0
+    if rng.randint(2):
+        delta = rng.uniform(-delta_brigtness, delta_brigtness)
+        delta_b = delta
+    contrast = rng.randint(2)
+    alpha1 = rng.uniform(lower, upper) if contrast else 1.0
+    sat = rng.uniform(lower, upper) if rng.randint(2) else 1.0
+    hue = rng.uniform(-delta, delta) if rng.randint(2) else 0.0
+    alpha2 = rng.uniform(lower, upper) if contrast else 1.0
+    perm = int(rng.randint(len(perms))) if rng.randint(2) else 0
+    return {"params": np.array([delta_b, alpha1, sat, hue, alpha2], dtype=np.float64), "perm": perm}
+
+
+def photometric_u8(image, photometric, blue_idx=0):
+    """One uint8 ``[H,W,3]`` NumPy image through ``balf_photometric_u8`` with a ``sample_photometric`` result -> NumPy."""
+    image = np.ascontiguousarray(image)
+    if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3 or image.size == 0:
+        raise ValueError(f"image must be a non-empty uint8 [H,W,3] array, got {image.dtype} {image.shape}")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    out = ops.photometric_u8(torch.from_numpy(image.reshape(-1)).to(dev), torch.zeros(1, dtype=torch.int64, device=dev),
+                             torch.tensor([image.shape[:2]], dtype=torch.int32, device=dev),
+                             torch.from_numpy(np.asarray(photometric["params"], np.float64).reshape(1, 5)).to(dev),
+                             torch.tensor([photometric["perm"]], dtype=torch.int32, device=dev), blue_idx)
+    return out.cpu().numpy().reshape(image.shape)
+
+
+def bgr_distorsion(image, lower=0.5, upper=1.5, delta=18.0, delta_brigtness=36):
+    """The reference's signature: a uint8 BGR ``[H,W,3]`` NumPy image -> its random photometric distortion (NumPy, uint8),
+    the draws from ``np.random`` (``sample_photometric``), the pixels on the GPU."""
+    return photometric_u8(image, sample_photometric(None, lower, upper, delta, delta_brigtness))
+
+
+def bgr_photometric_to_rgb(im_bgr):
+    """Reference :76-79: ``bgr_distorsion``, then the channels reversed."""
+    img_rgb = np.ascontiguousarray(bgr_distorsion(im_bgr)[:, :, ::-1])
+    return img_rgb.reshape(img_rgb.shape[0], img_rgb.shape[1], 3)
+
+
+def check_margins(img, axis=-1):
+    """Reference :123-130: clamp a float image (``axis`` -1) or one of its channels to [0, 255], in place; returns it."""
+    view = img if axis == -1 else img[:, :, axis]
+    view[view > 255.0] = 255.0
+    view[view < 0.0] = 0.0
+    return img
+
+
+def swap_channels(image, swaps):
+    """Reference :132-134: the channels of ``image`` in the order ``swaps``."""
+    return image[:, :, swaps]
 
 
 # ---- synthetic-homography pairs: the host side ------------------------------------------------------------------------------
@@ -181,12 +253,15 @@ def compose_pair_homographies(h, point_src, point_dst, patch_size):
     return h_src_2_dst, h_dst_2_src
 
 
-def sample_pair_geometry(shape, hom_config, patch_size, rng=None, max_draws=10000):
+def sample_pair_geometry(shape, hom_config, patch_size, rng=None, max_draws=10000, photometric_rng=None):
     """The random part of one pair of the reference's loader (COCO.py:53-142) for an image of ``shape`` (h, w[, c]): draw a
     homography, the source window, map its centre with ``inv_h``; a destination window that leaves the image redraws the pair
     FROM THE HOMOGRAPHY ON, as the reference's loop does.  -> dict: ``inv_h`` float64 [3,3] (what ``cv2.warpPerspective`` is
     handed), ``win_src`` / ``win_dst`` (top row, left column) ints, ``h_src_2_dst`` / ``h_dst_2_src`` float32 [3,3].
-    Not reproduced: the reference also redraws a homography whose whole warped image is black (see SyntheticPairs)."""
+    Not reproduced: the reference also redraws a homography whose whole warped image is black (see SyntheticPairs).
+    ``photometric_rng`` (a ``np.random.RandomState``) selects the training task: EVERY homography draw of the loop is followed
+    by one ``sample_photometric(photometric_rng)`` -- the reference distorts inside its loop, so a redraw consumes a set -- and
+    the accepted draw's set is returned under ``"photometric"``.  Without it nothing changes: the same draws, the same dict."""
     rng = random if rng is None else rng
     half = patch_size / 2
     if shape[0] < patch_size or shape[1] < patch_size:
@@ -195,6 +270,7 @@ def sample_pair_geometry(shape, hom_config, patch_size, rng=None, max_draws=1000
         h = generate_homography(shape, hom_config, rng)
         inv_h = np.linalg.inv(h)
         inv_h = inv_h / inv_h[2, 2]
+        photometric = None if photometric_rng is None else sample_photometric(photometric_rng)
         point_src = get_window_point(shape, patch_size, rng=rng)
         point_dst = inv_h.dot([point_src[1], point_src[0], 1.0])
         point_dst = [point_dst[1] / point_dst[2], point_dst[0] / point_dst[2]]
@@ -207,5 +283,8 @@ def sample_pair_geometry(shape, hom_config, patch_size, rng=None, max_draws=1000
         if any(int(c + half) - int(c - half) != patch_size for c in point_dst):     # the reference's final shape check
             continue
         h_src_2_dst, h_dst_2_src = compose_pair_homographies(h, point_src, point_dst, patch_size)
-        return {"inv_h": inv_h, "win_src": win_src, "win_dst": win_dst, "h_src_2_dst": h_src_2_dst, "h_dst_2_src": h_dst_2_src}
+        out = {"inv_h": inv_h, "win_src": win_src, "win_dst": win_dst, "h_src_2_dst": h_src_2_dst, "h_dst_2_src": h_dst_2_src}
+        if photometric is not None:
+            out["photometric"] = photometric
+        return out
     raise RuntimeError(f"no destination window inside the image in {max_draws} draws: {hom_config} on {tuple(shape[:2])}")

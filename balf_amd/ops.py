@@ -430,7 +430,7 @@ def resize_crop_u8(packed: torch.Tensor, offsets: torch.Tensor, sizes: torch.Ten
     return out
 
 
-# ---- synthetic-homography image pairs of the validation task (datasets/synthetic_pairs.py drives this) ----------------------
+# ---- synthetic-homography image pairs of the validation and the training task (datasets/synthetic_pairs.py drives this) ----
 def synth_pairs(packed: torch.Tensor, offsets: torch.Tensor, sizes: torch.Tensor, inv_h: torch.Tensor, win_src: torch.Tensor,
                 win_dst: torch.Tensor, pts: torch.Tensor, pts_offsets: torch.Tensor, top_k: int, patch: int, out=None):
     """The image patches and heat maps of P synthetic-homography pairs in one call (balf_synth_pairs in include/balf_hip.h):
@@ -440,6 +440,54 @@ def synth_pairs(packed: torch.Tensor, offsets: torch.Tensor, sizes: torch.Tensor
     ``pts_offsets`` [P+1] int32; everything on the GPU.  Returns (img_src [P,3,patch,patch], img_dst [P,3,patch,patch],
     heat_src [P,1,patch,patch], heat_dst [P,1,patch,patch] float32, dst_max [P] int32); ``out`` = such a 5-tuple to write into
     instead of allocating.  Nothing is read back: a window that leaves its image shows as ``dst_max == -1``."""
+    return _synth_pairs("balf_synth_pairs", packed, offsets, sizes, inv_h, win_src, win_dst, pts, pts_offsets, top_k, patch, out, ())
+
+
+def synth_train_pairs(packed: torch.Tensor, offsets: torch.Tensor, sizes: torch.Tensor, inv_h: torch.Tensor, win_src: torch.Tensor,
+                      win_dst: torch.Tensor, pts: torch.Tensor, pts_offsets: torch.Tensor, top_k: int, patch: int,
+                      params: torch.Tensor, perm: torch.Tensor, out=None):
+    """:func:`synth_pairs` for the TRAINING task (balf_synth_train_pairs in include/balf_hip.h): the destination patch is the
+    warp of the photometrically distorted image, ``params`` [P,5] float64 (delta_b, alpha1, sat, hue, alpha2) and ``perm`` [P]
+    int32 per pair (``datasets.dataset_utils.sample_photometric``), on the GPU.  Everything else as there; a ``perm`` outside
+    0..5 shows as an all-zero destination patch and ``dst_max == -1``."""
+    return _synth_pairs("balf_synth_train_pairs", packed, offsets, sizes, inv_h, win_src, win_dst, pts, pts_offsets, top_k, patch,
+                        out, (params, perm))
+
+
+def _check_photometric(params, perm, n, dev):
+    _check_layouts(((params, "params", ((n, 5),), torch.float64), (perm, "perm", ((n,),), torch.int32)), dev)
+
+
+def photometric_u8(packed: torch.Tensor, offsets: torch.Tensor, sizes: torch.Tensor, params: torch.Tensor, perm: torch.Tensor,
+                   blue_idx: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The reference's ``bgr_distorsion`` with given parameters on B whole images in one launch (balf_photometric_u8 in
+    include/balf_hip.h): ``packed`` the uint8 3-channel interleaved images back to back (1-D), ``offsets`` [B] int64, ``sizes``
+    [B,2] int32 (h, w), ``params`` [B,5] float64 (delta_b, alpha1, sat, hue, alpha2), ``perm`` [B] int32, all on the GPU;
+    ``blue_idx`` 0 for B, G, R pixels, 2 for R, G, B.  -> a uint8 tensor laid out as ``packed`` (``out``, which may be
+    ``packed`` itself, or a new one, zeroed: an image outside ``packed`` is not written)."""
+    for t, name in ((packed, "packed"), (offsets, "offsets"), (sizes, "sizes")):
+        require_gpu_tensor(t, name)
+    b = offsets.shape[0] if offsets.dim() == 1 else 0
+    if packed.dtype != torch.uint8 or packed.dim() != 1 or offsets.dtype != torch.int64 or b == 0 or \
+            sizes.dtype != torch.int32 or tuple(sizes.shape) != (b, 2):
+        raise BalfHipError("packed must be a 1-D uint8 tensor, offsets [B] int64 and sizes [B,2] int32 with B > 0")
+    dev = packed.device
+    _check_photometric(params, perm, b, dev)
+    if blue_idx not in (0, 2):
+        raise ValueError(f"blue_idx must be 0 (BGR) or 2 (RGB), got {blue_idx}")
+    if out is None:
+        out = torch.zeros_like(packed)
+    else:
+        require_gpu_tensor(out, "out")
+        if out.dtype != torch.uint8 or out.shape != packed.shape or out.device != dev:
+            raise BalfHipError(f"out must be a uint8 tensor of {tuple(packed.shape)} on {dev}")
+    launch("balf_photometric_u8", dev, packed, packed.numel(), offsets, sizes, b, params, perm, int(blue_idx), out)
+    return out
+
+
+def _synth_pairs(entry, packed, offsets, sizes, inv_h, win_src, win_dst, pts, pts_offsets, top_k, patch, out, photometric):
+    """The body of :func:`synth_pairs` and :func:`synth_train_pairs`: ``entry`` the library's, ``photometric`` = () or
+    (params, perm), which follow the workspace in the argument list."""
     for t, name in ((packed, "packed"), (offsets, "offsets"), (sizes, "sizes"), (inv_h, "inv_h"), (win_src, "win_src"),
                     (win_dst, "win_dst"), (pts, "pts"), (pts_offsets, "pts_offsets")):
         require_gpu_tensor(t, name)
@@ -452,6 +500,8 @@ def synth_pairs(packed: torch.Tensor, offsets: torch.Tensor, sizes: torch.Tensor
                     (win_dst, "win_dst", ((p, 2),), torch.int32), (pts_offsets, "pts_offsets", ((p + 1,),), torch.int32)), dev)
     if pts.dtype != torch.float32 or pts.dim() != 2 or pts.shape[1] != 3 or pts.device != dev:
         raise BalfHipError(f"pts must be an [N,3] float32 tensor on {dev}")
+    if photometric:
+        _check_photometric(*photometric, p, dev)
     top_k, patch = int(top_k), int(patch)
     if top_k < 0:
         raise ValueError(f"top_k must be >= 0 (0 keeps every row), got {top_k}")
@@ -459,7 +509,7 @@ def synth_pairs(packed: torch.Tensor, offsets: torch.Tensor, sizes: torch.Tensor
         raise ValueError(f"patch must be positive, got {patch}")
     nbytes = lib().balf_synth_pairs_workspace_bytes(p, patch)
     if nbytes == 0:
-        raise BalfHipError(f"balf_synth_pairs: unsupported sizes P={p}, patch={patch}")
+        raise BalfHipError(f"{entry}: unsupported sizes P={p}, patch={patch}")
     shapes = ((p, 3, patch, patch), (p, 3, patch, patch), (p, 1, patch, patch), (p, 1, patch, patch), (p,))
     if out is None:
         out = tuple(torch.empty(s, dtype=torch.int32 if len(s) == 1 else torch.float32, device=dev) for s in shapes)
@@ -471,8 +521,8 @@ def synth_pairs(packed: torch.Tensor, offsets: torch.Tensor, sizes: torch.Tensor
             if tuple(t.shape) != s or t.dtype != (torch.int32 if len(s) == 1 else torch.float32) or t.device != dev:
                 raise BalfHipError(f"out tensors must be {shapes} (float32, dst_max int32) on {dev}")
     ws = _workspace("synth_pairs", dev, nbytes)
-    launch("balf_synth_pairs", dev, packed, packed.numel(), offsets, sizes, p, inv_h, win_src, win_dst,
-           pts if pts.shape[0] else None, pts.shape[0], pts_offsets, top_k, patch, *out, Workspace(ws))
+    launch(entry, dev, packed, packed.numel(), offsets, sizes, p, inv_h, win_src, win_dst,
+           pts if pts.shape[0] else None, pts.shape[0], pts_offsets, top_k, patch, *out, Workspace(ws), *photometric)
     return tuple(out)
 
 

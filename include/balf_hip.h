@@ -524,6 +524,58 @@ int balf_synth_pairs(const unsigned char *packed_dev, size_t packed_bytes, const
                      int top_k, int patch, float *img_src_dev, float *img_dst_dev, float *heat_src_dev, float *heat_dst_dev,
                      int32_t *dst_max_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
 
+/* ---- the training task's pairs: photometric distortion (balf/datasets/dataset_utils.py:76-134, COCO.py:70-75) -------------
+ * The reference's training loader warps bgr_photometric_to_rgb(src_BGR), not the image itself.  The random draws stay on the
+ * host (balf_amd/datasets/dataset_utils.py: sample_photometric); per image / pair the device takes params [5] float64 =
+ * (delta_b, alpha1, sat, hue, alpha2) and perm int32, a row of the reference's perms table ((0,1,2), (0,2,1), (1,0,2), (1,2,0),
+ * (2,0,1), (2,1,0)).  A branch of bgr_distorsion that did not fire is its neutral value -- delta_b = 0, alpha = 1, sat = 1,
+ * hue = 0, perm = 0 --, which makes the step the identity bit for bit, so there are no flags.
+ * The two colour conversions are DEFINED here by OpenCV's scalar 8-bit code (RGB2HSV_b with hrange 180, HSV2RGB_b through its
+ * float32 path); parity with a cv2 build is UNPINNED (no cv2 where this library is built), as for the warp and
+ * the resize.  Per pixel, from bytes (b, g, r):
+ *   1  x = (double)byte + delta_b, clamped to [0, 255] (x > 255 -> 255, then x < 0 -> 0); x *= alpha1, clamped; truncated.
+ *   2  v = max, vmin = min, diff = v - vmin; sdiv[i] = rint((255 << 12) / (double)i), hdiv[i] = rint((180 << 12) / (6.0 * i)),
+ *      sdiv[0] = hdiv[0] = 0; S = (diff * sdiv[v] + 2048) >> 12; h = (v == r) ? g - b : (v == g) ? b - r + 2 diff : r - g +
+ *      4 diff (in this order when channels tie); H = (h * hdiv[diff] + 2048) >> 12 (arithmetic shift, int32), H += 180 if H < 0.
+ *   3  S = trunc(clamp((double)S * sat)).
+ *   4  x = (double)H + hue; x -= 360 if x > 360; x += 360 if x < 0; the byte is (int32)x & 255.  This is what the reference's
+ *      astype(np.uint8) gives on x86-64: 324..359 become 68..103, a hue jump the reference really makes; it is reproduced.
+ *   5  s = S * (1.f / 255.f), vv = V * (1.f / 255.f) in float32 without fused operations.  S == 0: b = g = r = vv.  Otherwise
+ *      hh = H * (6.f / 180.f), hh -= 6.f if hh >= 6.f, sector = floor(hh), f = hh - sector, tab = {vv, vv (1 - s),
+ *      vv (1 - s f), vv (1 - s (1 - f))}, (b, g, r) = tab[{1,3,0}, {1,0,2}, {3,0,1}, {0,2,1}, {0,1,3}, {2,1,0}][sector]; the byte
+ *      is rint(x * 255.f) (half to even) saturated to [0, 255].
+ *   6  x = (double)byte * alpha2, clamped, truncated.
+ *   7  out_bgr[k] = bgr[perms[perm][k]].
+ * Finite parameters are the contract; whatever bits they hold, every table index is a byte, so no read leaves its table.
+ *
+ * balf_photometric_u8: steps 1-7 on B whole 3-channel interleaved uint8 images, one launch, no workspace, stream-ordered,
+ * capturable.  The images are packed as balf_resize_crop_u8 takes them (offsets_dev [B] int64, sizes_dev [B,2] int32 (h, w));
+ * out_dev has the layout and the offsets of packed_dev (it may BE packed_dev).  params_dev [B,5] float64, perm_dev [B] int32.
+ * blue_idx 0: the pixels are B, G, R; 2: R, G, B (b = px[blue_idx], r = px[2 - blue_idx]); the output keeps the input's order.
+ * An image that does not lie inside packed_bytes is not written; a perm outside 0..5 writes a black image.
+ * 1 <= B <= 65535, blue_idx in {0, 2} (BALF_ERR_ARG).
+ *
+ * balf_synth_train_pairs: balf_synth_pairs for the training task: the same arguments, then params_dev [P,5] and perm_dev [P];
+ * the same workspace (balf_synth_pairs_workspace_bytes), limits and errors, and the same outputs except the destination patch
+ * and dst_max.  The packed images are RGB, as for balf_synth_pairs, and the destination patch is the warp of
+ * bgr_photometric_to_rgb(image) -- the distortion reads blue from px[2] and writes in the input's order, blue_idx = 2 above.
+ * The distorted image is never formed: each of the four taps of an output pixel is distorted, all three channels, before the
+ * integer interpolation.  A tap outside the image contributes 0, NOT the distortion of a black pixel: the reference pads the
+ * already distorted image with zeros.  The source patch is the undistorted image; dst_max is the largest byte of the
+ * distorted, warped patch.  A perm outside 0..5 gives an all-zero destination patch and dst_max = -1; the pair's other
+ * outputs and the other pairs of the call are as for any pair.  The destination patch, both heat maps and dst_max equal, bit
+ * for bit, those of balf_photometric_u8 (blue_idx 2) followed by balf_synth_pairs on its output (whose SOURCE patch is cut from
+ * the distorted image, which is not the training task's). */
+int balf_photometric_u8(const unsigned char *packed_dev, size_t packed_bytes, const long long *offsets_dev,
+                        const int32_t *sizes_dev, int B, const double *params_dev, const int32_t *perm_dev, int blue_idx,
+                        unsigned char *out_dev, void *stream);
+int balf_synth_train_pairs(const unsigned char *packed_dev, size_t packed_bytes, const long long *offsets_dev,
+                           const int32_t *sizes_dev, int P, const double *inv_h_dev, const int32_t *win_src_dev,
+                           const int32_t *win_dst_dev, const float *pts_dev, int pts_total, const int32_t *pts_offsets_dev,
+                           int top_k, int patch, float *img_src_dev, float *img_dst_dev, float *heat_src_dev,
+                           float *heat_dst_dev, int32_t *dst_max_dev, void *workspace_dev, size_t workspace_bytes,
+                           const double *params_dev, const int32_t *perm_dev, void *stream);
+
 /* ---- detector (anchor) loss: labels, masked cross-entropy and its gradient (balf/loss/loss_function.py:7-26) ------------
  * balf_detector_loss: the reference's detector_loss for grid_size 8 (the 65-channel head, the only one arch.py supports; the
  * reference's train_model passes grid_size=16, which its own 65-channel head cannot satisfy), stream-ordered, nothing read
