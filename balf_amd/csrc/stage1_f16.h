@@ -69,6 +69,23 @@ enum S1Par { kS1pConv0B = 0, kS1pQ1B = 32, kS1pD1B = 64, kS1pGlnG = 128, kS1pGln
 #define BALF_S1_NW2 12
 #endif
 template <int MODE> constexpr int s1_waves() { return MODE == 0 ? BALF_S1_NW0 : MODE == 1 ? BALF_S1_NW1 : BALF_S1_NW2; }   // 2 / 2 / 3 waves per SIMD
+// Work split between the two waves of a SIMD.  Waves w and w + NW / 2 share a SIMD, and its vector issue goes to the older wave
+// first: with one group per wave and round, wave w needed 11.4 k clocks per group and wave w + 4 14.2 k (grid; block 15.0 k
+// against 19.3 k), so the lower half was done after three quarters of the launch and the upper half finished alone, one wave
+// per SIMD ("Two waves of a SIMD do not run at one speed").  BALF_S1_SHAREm: the lower half of the waves of the
+// MODE-m kernel takes the first SHARE / 1000 of the groups, the upper half the rest, each half in the XCD-aware order; 0: every
+// wave takes one group per round.  Which wave computes a group changes no bit of it.  Every group of a range is reached by the
+// stride loop whatever the grid size: with few groups (fewer than the waves started) a range is shorter than one round, waves
+// beyond it leave at once, and the split then balances nothing -- nor does it cost anything.  The ratio is a property of the
+// SIMD's issue arbitration at the clock the kernel runs at, measured on 16 x 1088x1920 per launch (shares 530 ... 620 tried per
+// kernel, the best kept); a share that is off costs at most what the even split cost.
+#ifndef BALF_S1_SHARE0
+#define BALF_S1_SHARE0 580
+#endif
+#ifndef BALF_S1_SHARE1
+#define BALF_S1_SHARE1 600
+#endif
+template <int MODE> constexpr int s1_lower_share() { return MODE == 0 ? BALF_S1_SHARE0 : MODE == 1 ? BALF_S1_SHARE1 : 0; }
 template <int MODE> constexpr int s1_lds_bytes() {
     return s1_weight_bytes<MODE>() + kS1ParFloats * 4 + (MODE == 2 ? 0 : s1_waves<MODE>() * kS1BtBytes);   // (no token mix in the tail)
 }
@@ -394,8 +411,15 @@ __global__ __launch_bounds__(s1_waves<MODE>() * 64, 1) void stage1_kernel16(Stag
     const int total = A.B * per_img;
     // XCD-aware persistent schedule (speed only): workgroups b and b + 8 share an XCD (L2); hand each XCD runs of
     // consecutive groups -- neighbours read the same lines of the strided grid gather -- one group per wave per round.
-    const int nx = (gridDim.x >> 3) * NW;                        // waves per XCD (gridDim.x is a multiple of 8)
-    const int wx = (blockIdx.x >> 3) * NW + wave, xcd = blockIdx.x & 7;
+    // The lower and the upper half of a workgroup's waves walk a range of groups each (see BALF_S1_SHARE0): [0, split) and
+    // [split, total); without a split all waves walk [0, total).
+    constexpr int SHARE = s1_lower_share<MODE>(), NWR = SHARE ? NW / 2 : NW;    // NWR: waves of a workgroup on one range
+    static_assert(SHARE == 0 || NW % 2 == 0, "the work split halves the workgroup's waves");
+    const bool upper = SHARE != 0 && wave >= NWR;                // wave-uniform
+    const int split = SHARE ? (int)((long)total * SHARE / 1000) : total;
+    const int first = upper ? split : 0, lim = upper ? total : split;
+    const int nx = (gridDim.x >> 3) * NWR;                       // waves per XCD and range (gridDim.x is a multiple of 8)
+    const int wx = (blockIdx.x >> 3) * NWR + (upper ? wave - NWR : wave), xcd = blockIdx.x & 7;
 
     // group index -> (image n, gy, gx) [block (by, bx) or in-cell offset (iy, ix)], advanced incrementally by the
     // schedule's stride (two integer divisions per group would cost ~80 scalar instructions each)
@@ -493,10 +517,10 @@ __global__ __launch_bounds__(s1_waves<MODE>() * 64, 1) void stage1_kernel16(Stag
         c.gx = __builtin_amdgcn_readfirstlane(c.gx);
         return c;
     };
-    int item = xcd * nx + wx;                                    // wave-uniform
+    int item = first + xcd * nx + wx;                            // wave-uniform
     Pos nxt = decompose(item);
     unsigned raw[4] = {}, nraw[4] = {};
-    if (!U8 && !TAIL && item < total) {
+    if (!U8 && !TAIL && item < lim) {
         issue_raw(geo(nxt), nraw);
         // the first group has no older stores in front of its pixels: drain here (the counted wait in the loop assumes them)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -504,9 +528,9 @@ __global__ __launch_bounds__(s1_waves<MODE>() * 64, 1) void stage1_kernel16(Stag
     const float2 a0 = *reinterpret_cast<const float2 *>(smem_raw + kS1Conv0 + lane * 8);   // conv0's A operands (loop-invariant)
 
     unsigned long long sat = 0;                                  // (tail) lanes that saw a stage output at or beyond the largest f16
-    for (; item < total; item += stride) {
+    for (; item < lim; item += stride) {
         const Geo g = geo(nxt);
-        if (item + stride < total) nxt = advance(nxt);           // (the last group re-requests its own pixels)
+        if (item + stride < lim) nxt = advance(nxt);             // (the last group re-requests its own pixels)
         const long pix0 = g.pix0;
         if (U8 && !TAIL) load_raw_u8(g, raw);                  // (tail: right before its conv0, see below)
         // (tail) plain loads, no prefetch across groups: three waves per SIMD cover the latency, and with few stores per

@@ -43,6 +43,15 @@ constexpr int kS2C = 64, kS2Cin = 32;                             // a Linear wi
 #define BALF_S2_NW2 8
 #endif
 template <int MODE> constexpr int s2_waves() { return MODE == 0 ? BALF_S2_NW0 : MODE == 1 ? BALF_S2_NW1 : BALF_S2_NW2; }
+// Work split between the lower and the upper half of the wave pairs, as in stage 1 (stage1_f16.h: BALF_S1_SHARE0): pairs p and
+// p + NP / 2 share two SIMDs, and the older pair gets their vector issue first.
+#ifndef BALF_S2_SHARE0
+#define BALF_S2_SHARE0 555
+#endif
+#ifndef BALF_S2_SHARE1
+#define BALF_S2_SHARE1 580
+#endif
+template <int MODE> constexpr int s2_lower_share() { return MODE == 0 ? BALF_S2_SHARE0 : MODE == 1 ? BALF_S2_SHARE1 : 0; }
 template <int MODE> constexpr int s2_lut_n() { return MODE == 0 ? kGeluLutN : MODE == 1 ? kGeluLut2N : 0; }
 template <int MODE> constexpr int s2_lut_bytes() { return s2_lut_n<MODE>() ? ((s2_lut_n<MODE>() + 1) * 8 + 15) / 16 * 16 : 0; }
 
@@ -257,8 +266,15 @@ __global__ __launch_bounds__(s2_waves<MODE>() * 64, 1) void stage2_kernel16(Stag
     const int per_img = fh * fw;
     const int total = A.B * per_img;
     // XCD-aware persistent schedule, as in stage 1, in units of wave PAIRS: workgroups b and b + 8 share an XCD (L2)
-    const int npx = (gridDim.x >> 3) * NP;                       // pairs per XCD
-    const int px = (blockIdx.x >> 3) * NP + pair, xcd = blockIdx.x & 7;
+    // The lower and the upper half of a workgroup's pairs walk a range of groups each: [0, split) and [split, total).  `upper`
+    // depends on `pair` alone, so item, stride and the trip count stay pair-uniform (s2_poll's invariant).
+    constexpr int SHARE = s2_lower_share<MODE>(), NPR = SHARE ? NP / 2 : NP;    // NPR: pairs of a workgroup on one range
+    static_assert(SHARE == 0 || NP % 2 == 0, "the work split halves the workgroup's pairs");
+    const bool upper = SHARE != 0 && pair >= NPR;
+    const int split = SHARE ? (int)((long)total * SHARE / 1000) : total;
+    const int first = upper ? split : 0, lim = upper ? total : split;
+    const int npx = (gridDim.x >> 3) * NPR;                      // pairs per XCD and range
+    const int px = (blockIdx.x >> 3) * NPR + (upper ? pair - NPR : pair), xcd = blockIdx.x & 7;
 
     struct Pos { int n, gy, gx; };
     struct Geo { int n, y, x; };
@@ -306,7 +322,7 @@ __global__ __launch_bounds__(s2_waves<MODE>() * 64, 1) void stage2_kernel16(Stag
                      : "+v"(nx[0].hi), "+v"(nx[0].lo), "+v"(nx[1].hi), "+v"(nx[1].lo) : "v"(vo), "s"(xb) : "memory");
     };
 
-    int item = xcd * npx + px;                                   // wave-uniform; the same for both waves of a pair
+    int item = first + xcd * npx + px;                           // wave-uniform; the same for both waves of a pair
     Pos nxt = decompose(item);
     HL nx[2] = {};
     // (tail) x1 of the next half group as the block kernel left it -- register order: per wave half 8 KB = [tile][register quad]
@@ -325,7 +341,7 @@ __global__ __launch_bounds__(s2_waves<MODE>() * 64, 1) void stage2_kernel16(Stag
                          : "v"(lo16), "s"(rp), "s"(rp + 4096) : "memory");
         }
     };
-    if (item < total) {
+    if (item < lim) {
         issue_in(geo(nxt), nx);
         issue_x1(item);
         if constexpr (TAIL)
@@ -338,9 +354,9 @@ __global__ __launch_bounds__(s2_waves<MODE>() * 64, 1) void stage2_kernel16(Stag
     unsigned pass = 0;                                           // token-tile passes completed by this pair (wave-uniform)
 
     float rng = 0.0f;                                            // (tail) max |v| over the stage's output (status block)
-    for (; item < total; item += stride) {
+    for (; item < lim; item += stride) {
         const Geo g = geo(nxt);
-        const bool more = item + stride < total;
+        const bool more = item + stride < lim;
         if (more) nxt = advance(nxt);                            // (the last group re-requests its own pixels)
         const long pix = ((long)g.n * H + g.y) * W + g.x;
 
