@@ -1,7 +1,7 @@
 """``TrainableStage4``: all of stage 4 -- ``down4.conv.0`` (Linear 128 -> 256) and its ReLU, then the ``TrainableMixerTail`` (the
 multi-axis gated-MLP layer, the channel-attention block and the head) -- on the output of the frozen stages 1-3
 (``MLP_MA_DECODER.encode(x, level="stage3")`` -> ``x3``); forward in training mode and backward on the HIP library
-(balf_linrelu_train_forward / balf_linrelu_train_backward, include/balf_hip.h).  The output ``x0`` of this layer
+(``train_units.conv0_step``: balf_linrelu_train_forward / balf_linrelu_train_backward, include/balf_hip.h).  The output ``x0`` of this layer
 feeds the gated-MLP layer, that layer's shortcut and the block's long shortcut; ``TrainableMixerTail`` hands all three gradients to
 an ``x0`` that requires one, autograd adds them, and the sum is what this layer's backward starts from.
 
@@ -11,28 +11,10 @@ from __future__ import annotations
 
 import torch
 import torch.nn as nn
-from torch.autograd.function import once_differentiable
 
 from .. import ops
 from .mixer_train import TrainableMixerTail
-
-
-class _LinreluTrain(torch.autograd.Function):
-    """Forward keeps x3 and the output (the ReLU's derivative is taken from it); backward is one balf_linrelu_train_backward call
-    (dx only if ``x3`` requires a gradient)."""
-
-    @staticmethod
-    def forward(ctx, x3, weight, bias):
-        y = ops.linrelu_train_forward(x3, weight, bias).y
-        ctx.save_for_backward(x3, weight, y)
-        return y
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g):
-        x3, weight, y = ctx.saved_tensors
-        out = ops.linrelu_train_backward(g.contiguous(), y, x3, weight, want_dx=ctx.needs_input_grad[0])
-        return out.dx, out.dweight, out.dbias
+from .train_units import _LinreluTrain, conv0_step, copy_params             # noqa: F401  (_LinreluTrain: tests import it from here)
 
 
 _PREFIX = "down4.conv.0."
@@ -61,27 +43,17 @@ class TrainableStage4(nn.Module):
         src = model.state_dict()
         mine.to(src[_PREFIX + "weight"].device)
         mine.mixer = mixer
-        with torch.no_grad():
-            for n, p in zip(ops.LINRELU_PARAMS, mine.conv0_parameters()):
-                p.copy_(src[_PREFIX + n])
+        copy_params(mine.conv0.named_parameters(), src, _PREFIX)
         return mine
 
     def commit(self, model) -> None:
         """Write ``down4.conv.0`` and everything of the mixer and the tail back into ``model``, in place: the model's cache key sees
         the update and its next forward re-packs the weights once."""
-        dst = model.state_dict()
-        with torch.no_grad():
-            for n, p in zip(ops.LINRELU_PARAMS, self.conv0_parameters()):
-                dst[_PREFIX + n].copy_(p)
+        copy_params(self.conv0.named_parameters(), model.state_dict(), _PREFIX, back=True)
         self.mixer.commit(model)
 
     def forward(self, x3: torch.Tensor, want_prob: bool = True):
         """``x3`` = ``model.encode(x, level="stage3")`` -> what ``TrainableHead.forward`` returns.  ``train()`` mode: the result
         carries the graph when gradients are enabled and a parameter or ``x3`` requires a gradient (``dx`` is computed only for
         ``x3``).  ``eval()`` mode: the same arithmetic without a graph."""
-        weight, bias = self.conv0_parameters()
-        if self.training and torch.is_grad_enabled() and (x3.requires_grad or weight.requires_grad or bias.requires_grad):
-            x0 = _LinreluTrain.apply(x3, weight, bias)
-        else:
-            x0 = ops.linrelu_train_forward(x3.detach(), weight.detach(), bias.detach()).y
-        return self.mixer(x0, want_prob=want_prob)
+        return self.mixer(conv0_step(x3, self.conv0_parameters(), self.training), want_prob=want_prob)

@@ -713,8 +713,6 @@ def head_train_backward(dlogits: torch.Tensor, x2: torch.Tensor, w2: torch.Tenso
 
 
 RCAB_PARAMS = ("ln_g", "ln_b", "wc1", "bc1", "wc2", "bc2", "ws0", "bs0", "ws2", "bs2")
-_RCAB_PARAM_SHAPES = {"ln_g": (256,), "ln_b": (256,), "wc1": (256, 256), "bc1": (256,), "wc2": (256, 256), "bc2": (256,),
-                      "ws0": (64, 256), "bs0": (64,), "ws2": (256, 64), "bs2": (256,)}
 _RCAB_BACKWARD_READS = ("ln_g", "wc1", "wc2", "ws0", "ws2")
 TRAIN_WIDTHS = {256: 4, 128: 3}           # channels of the RCAB and the gated-MLP layer in training form -> the Down stage
 
@@ -725,13 +723,19 @@ def _train_width(channels: int, what: str) -> int:
     return channels
 
 
-def rcab_param_shapes(channels: int = 256) -> dict:
-    """The shapes of the ten ``RCAB_PARAMS`` of the channel-attention block at ``channels`` (256: stage 4's, 128: stage 3's)."""
-    c = _train_width(channels, "rcab_param_shapes")
-    if c == 256:
-        return _RCAB_PARAM_SHAPES
+def _rcab_shapes(c: int) -> dict:
     return {"ln_g": (c,), "ln_b": (c,), "wc1": (c, c), "bc1": (c,), "wc2": (c, c), "bc2": (c,), "ws0": (c // 4, c), "bs0": (c // 4,),
             "ws2": (c, c // 4), "bs2": (c,)}
+
+
+_RCAB_SHAPES = {c: _rcab_shapes(c) for c in TRAIN_WIDTHS}       # made once: every training step asks, several times
+_RCAB_PARAM_SHAPES = _RCAB_SHAPES[256]                          # stage 4's, by the name the guard tests read
+
+
+def rcab_param_shapes(channels: int = 256) -> dict:
+    """The shapes of the ten ``RCAB_PARAMS`` of the channel-attention block at ``channels`` (256: stage 4's, 128: stage 3's): one
+    dict per width, not to be modified."""
+    return _RCAB_SHAPES[_train_width(channels, "rcab_param_shapes")]
 
 
 def train_unit_sizes(unit: int, channels: int, b: int, h: int, w: int) -> Tuple[int, int]:
@@ -743,7 +747,7 @@ def train_unit_sizes(unit: int, channels: int, b: int, h: int, w: int) -> Tuple[
 
 
 class RcabTrainForward(NamedTuple):
-    x2: torch.Tensor                          # [B,Hc,Wc,256] float32: the input of down4.conv2
+    x2: torch.Tensor                          # [B,Hc,Wc,channels] float32: the block's output (stage 4: the input of down4.conv2)
     saved: torch.Tensor                       # opaque uint8 block for rcab_train_backward
 
 
@@ -758,7 +762,7 @@ class RcabTrainBackward(NamedTuple):
     dbs0: torch.Tensor
     dws2: torch.Tensor
     dbs2: torch.Tensor
-    dy: Optional[torch.Tensor]                # [B,Hc,Wc,256]
+    dy: Optional[torch.Tensor]                # [B,Hc,Wc,channels]
 
 
 def _rcab_train_checks(y, named, aligned=(), channels=256):
@@ -775,12 +779,12 @@ def _rcab_train_checks(y, named, aligned=(), channels=256):
 
 
 def rcab_train_forward(y: torch.Tensor, r: torch.Tensor, params, saved=None, *, channels: int = 256) -> RcabTrainForward:
-    """Stage 4's channel-attention block on ``y`` [B,Hc,Wc,256] with ``r`` = y + the long shortcut (``rcab_inputs`` /
-    ``MLP_MA_DECODER.encode(level="rcab")`` give both): LayerNorm, conv1, LeakyReLU, conv2, the squeeze-excite scale, ``x2 = t * s +
-    r`` (balf_rcab_train_forward in include/balf_hip.h).  ``params``: the ten tensors in ``RCAB_PARAMS`` order, float32 and
-    contiguous on y's GPU.  ``saved``: a uint8 block to reuse (at least balf_rcab_train_saved_bytes), else allocated.
-    ``channels``: the block's width, 256 (stage 4) or 128 (stage 3: balf_rcab_train_forward_c); it is stated, never taken from
-    ``y``, and every width above reads ``channels`` for 256 and ``channels // 4`` for 64."""
+    """A Down stage's channel-attention block on ``y`` [B,Hc,Wc,channels] with ``r`` = y + the long shortcut (at stage 4,
+    ``rcab_inputs`` / ``MLP_MA_DECODER.encode(level="rcab")`` give both): LayerNorm, conv1, LeakyReLU, conv2, the squeeze-excite scale
+    of ``channels // 4`` units, ``x2 = t * s + r`` (balf_rcab_train_forward_c in include/balf_hip.h).  ``params``: the ten tensors in
+    ``RCAB_PARAMS`` order (``rcab_param_shapes(channels)``), float32 and contiguous on y's GPU.  ``saved``: a uint8 block to reuse
+    (at least the saved bytes of ``train_unit_sizes``), else allocated.  ``channels``: the block's width, a key of ``TRAIN_WIDTHS``;
+    it is stated, never taken from ``y``."""
     shapes = rcab_param_shapes(channels)
     params = tuple(params)
     if len(params) != len(RCAB_PARAMS):
@@ -799,8 +803,8 @@ def rcab_train_forward(y: torch.Tensor, r: torch.Tensor, params, saved=None, *, 
 def rcab_train_backward(dx2: torch.Tensor, y: torch.Tensor, ln_g: torch.Tensor, wc1: torch.Tensor, wc2: torch.Tensor,
                         ws0: torch.Tensor, ws2: torch.Tensor, saved: torch.Tensor, want_dy=False, *,
                         channels: int = 256) -> RcabTrainBackward:
-    """The backward of ``rcab_train_forward`` (balf_rcab_train_backward): ``dx2`` [B,Hc,Wc,256] (``head_train_backward`` writes
-    it) and the ``saved`` block of that forward -> the ten parameter gradients and, with ``want_dy``, the gradient at the block's
+    """The backward of ``rcab_train_forward`` (balf_rcab_train_backward_c): ``dx2`` [B,Hc,Wc,channels] (at stage 4,
+    ``head_train_backward`` writes it) and the ``saved`` block of that forward -> the ten parameter gradients and, with ``want_dy``, the gradient at the block's
     input (``want_dy`` may be a contiguous float32 tensor of y's shape to write into).  ``channels`` as in the forward."""
     s = rcab_param_shapes(channels)
     dy = want_dy if isinstance(want_dy, torch.Tensor) else None
@@ -831,35 +835,38 @@ def rcab_inputs(precision: int, workspace: torch.Tensor, b: int, hp: int, wp: in
 
 _GMLP_BRANCH = ("norm.weight", "norm.bias", "dense1.weight", "dense1.bias", "{u}.norm.weight", "{u}.norm.bias", "{u}.dense.weight",
                 "{u}.dense.bias", "dense2.weight", "dense2.bias")
-_GMLP_BRANCH_SHAPES = ((256,), (256,), (512, 256), (512,), (256,), (256,), (64, 64), (64,), (256, 256), (256,))
-# the 26 parameters of down4.residual_split_head_multi_axis_gmlp_layer under their state-dict names, in the order of
+# the 26 parameters of a Down stage's residual_split_head_multi_axis_gmlp_layer under their state-dict names, in the order of
 # include/balf_hip.h
 GMLP_PARAMS = (("norm.weight", "norm.bias", "dense1.weight", "dense1.bias")
                + tuple(f"{layer}.{n.format(u=unit)}" for layer, unit in (("grid_gmlp_layer", "grid_gating_unit"),
                                                                          ("block_gmlp_layer", "block_gating_unit"))
                        for n in _GMLP_BRANCH)
                + ("dense2.weight", "dense2.bias"))
-_GMLP_PARAM_SHAPES = dict(zip(GMLP_PARAMS, ((256,), (256,), (512, 256), (512,)) + 2 * _GMLP_BRANCH_SHAPES + ((256, 512), (256,))))
 
 
-def gmlp_param_shapes(channels: int = 256) -> dict:
-    """The shapes of the 26 ``GMLP_PARAMS`` of the gated-MLP layer at ``channels`` (256: stage 4's, 128: stage 3's); the token
-    matrices stay [64,64]."""
-    c = _train_width(channels, "gmlp_param_shapes")
-    if c == 256:
-        return _GMLP_PARAM_SHAPES
+def _gmlp_shapes(c: int) -> dict:
     branch = ((c,), (c,), (2 * c, c), (2 * c,), (c,), (c,), (64, 64), (64,), (c, c), (c,))
     return dict(zip(GMLP_PARAMS, ((c,), (c,), (2 * c, c), (2 * c,)) + 2 * branch + ((c, 2 * c), (c,))))
 
 
+_GMLP_SHAPES = {c: _gmlp_shapes(c) for c in TRAIN_WIDTHS}       # made once, as _RCAB_SHAPES
+_GMLP_PARAM_SHAPES = _GMLP_SHAPES[256]                          # stage 4's, by the name the tests read
+
+
+def gmlp_param_shapes(channels: int = 256) -> dict:
+    """The shapes of the 26 ``GMLP_PARAMS`` of the gated-MLP layer at ``channels`` (256: stage 4's, 128: stage 3's); the token
+    matrices stay [64,64].  One dict per width, not to be modified."""
+    return _GMLP_SHAPES[_train_width(channels, "gmlp_param_shapes")]
+
+
 class GmlpTrainForward(NamedTuple):
-    y: torch.Tensor                           # [B,Hc,Wc,256] float32: the input of stage 4's RCAB
+    y: torch.Tensor                           # [B,Hc,Wc,channels] float32: the input of the stage's RCAB
     saved: torch.Tensor                       # opaque uint8 block for gmlp_train_backward
 
 
 class GmlpTrainBackward(NamedTuple):
     grads: Tuple[torch.Tensor, ...]           # the 26 gradients, in GMLP_PARAMS order
-    dx0: Optional[torch.Tensor]               # [B,Hc,Wc,256]
+    dx0: Optional[torch.Tensor]               # [B,Hc,Wc,channels]
 
 
 def _gmlp_train_checks(x0, params, others, channels=256):
@@ -885,10 +892,11 @@ def _pointer_array(tensors):
 
 
 def gmlp_train_forward(x0: torch.Tensor, params, saved=None, *, channels: int = 256) -> GmlpTrainForward:
-    """Stage 4's multi-axis gated-MLP layer on ``x0`` [B,Hc,Wc,256] (``MLP_MA_DECODER.encode(level="gmlp")`` gives it):
-    balf_gmlp_train_forward in include/balf_hip.h.  ``params``: the 26 tensors in ``GMLP_PARAMS`` order, float32 and contiguous on
-    x0's GPU.  ``saved``: a uint8 block to reuse (at least balf_gmlp_train_saved_bytes), else allocated.  ``channels``: the
-    layer's width, 256 (stage 4) or 128 (stage 3: balf_gmlp_train_forward_c); stated, never taken from ``x0``."""
+    """A Down stage's multi-axis gated-MLP layer on ``x0`` [B,Hc,Wc,channels] (at stage 4,
+    ``MLP_MA_DECODER.encode(level="gmlp")`` gives it): balf_gmlp_train_forward_c in include/balf_hip.h.  ``params``: the 26 tensors in
+    ``GMLP_PARAMS`` order (``gmlp_param_shapes(channels)``), float32 and contiguous on x0's GPU.  ``saved``: a uint8 block to reuse
+    (at least the saved bytes of ``train_unit_sizes``), else allocated.  ``channels``: the layer's width, a key of ``TRAIN_WIDTHS``;
+    stated, never taken from ``x0``."""
     b, hc, wc, params = _gmlp_train_checks(x0, params, ((saved, "saved", None),), channels)
     dev = x0.device
     ws_bytes, saved_bytes = train_unit_sizes(_lib.UNIT_GMLP, channels, b, hc, wc)
@@ -901,7 +909,7 @@ def gmlp_train_forward(x0: torch.Tensor, params, saved=None, *, channels: int = 
 
 def gmlp_train_backward(dy: torch.Tensor, x0: torch.Tensor, params, saved: torch.Tensor, want_dx0=False, *,
                         channels: int = 256) -> GmlpTrainBackward:
-    """The backward of ``gmlp_train_forward`` (balf_gmlp_train_backward): ``dy`` [B,Hc,Wc,256] (``rcab_train_backward`` writes it)
+    """The backward of ``gmlp_train_forward`` (balf_gmlp_train_backward_c): ``dy`` [B,Hc,Wc,channels] (``rcab_train_backward`` writes it)
     and the ``saved`` block of that forward -> the 26 parameter gradients and, with ``want_dx0``, the gradient at the layer's input
     through the layer (``want_dx0`` may be a contiguous float32 tensor of x0's shape to write into).  ``channels`` as in the
     forward."""

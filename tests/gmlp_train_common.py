@@ -1,7 +1,9 @@
 """Shared by tests/test_gmlp_train_host.py, tests/test_gmlp_train_gpu.py, tests/golden/make_gmlp_train_golden.py and
-tools/bench_gmlp_train.py: the fixture gmlp_train.npz, the float64 restatement of stage 4's multi-axis gated-MLP layer (include/
-balf_hip.h: balf_gmlp_train_forward) and of its backward as closed formulas, the same through float64 autograd over oracle.oracle's
-arithmetic, the float32 torch-op composition, the error measure of the gates, and the seeded case generators."""
+tools/bench_gmlp_train.py, and by the stage-3 tests through tests/stage3_train_common.py: the fixture gmlp_train.npz, the float64
+restatement of the multi-axis gated-MLP layer (include/balf_hip.h: balf_gmlp_train_forward) and of its backward as closed formulas,
+the same through float64 autograd over oracle.oracle's arithmetic, the float32 torch-op composition, the error measure of the
+gates, and the seeded case generators.  All of it at a width C: the last dimension of the input where there is one, ``c`` (256,
+stage 4's, unless stated) in the generators; the token matrices stay [64,64]."""
 import functools
 import os
 
@@ -26,7 +28,8 @@ GRADS = tuple("d:" + k for k in PARAMS) + ("dx0",)
 GATED = ("y",) + GRADS                      # the 28 outputs
 TOL_FLOOR = H.TOL_FLOOR
 LN_EPS = 1e-5
-SD_PREFIX = "down4.residual_split_head_multi_axis_gmlp_layer."
+_SD_LAYER = "residual_split_head_multi_axis_gmlp_layer."
+SD_PREFIX = "down4." + _SD_LAYER
 inputs_digest = T.inputs_digest
 
 
@@ -82,14 +85,14 @@ def _gelu_grad(h):
 
 
 def restate64(x0, p, g=None):
-    """The equations of include/balf_hip.h in float64 on the CPU.  ``x0`` [B,Hc,Wc,256]; ``p``: dict PARAMS; ``g`` = dy or None.
+    """The equations of include/balf_hip.h in float64 on the CPU.  ``x0`` [B,Hc,Wc,C]; ``p``: dict PARAMS; ``g`` = dy or None.
     -> dict of float64 tensors: y, the 26 gradients as "d:<name>", dx0, and ``S``: name -> the scale of the error measure, the
     largest sum of absolute values of the terms of that output's last reduction (y: |cat| |W2|^T + |b2| + |x0|; a bias gradient: sum
     |d|; a weight gradient: |d|^T |input|; a LayerNorm gain: sum |dn xhat|; dWt: sum over groups and channels of |dmix[p]| |cn[q]|;
     dx0: |g| + rstd times the three terms of the LayerNorm's backward, as dy of rcab_train_common)."""
-    b, hc, wc, _ = x0.shape
+    b, hc, wc, c = x0.shape
     n_pix = b * hc * wc
-    X = x0.reshape(n_pix, 256).double()
+    X = x0.reshape(n_pix, c).double()
     P = {k: p[k].double() for k in PARAMS}
     n0, xhat0, rstd0 = _ln64(X, P["norm.weight"], P["norm.bias"])
     h0 = n0 @ P["dense1.weight"].T + P["dense1.bias"]
@@ -97,26 +100,26 @@ def restate64(x0, p, g=None):
     keep, outs = [], []
     for k, (layer, unit) in enumerate(BRANCHES):
         q = lambda s: P[f"{layer}.{s}"]                         # noqa: E731
-        z = g0[:, 256 * k:256 * k + 256]
+        z = g0[:, c * k:c * k + c]
         nb, xhat_b, rstd_b = _ln64(z, q("norm.weight"), q("norm.bias"))
         hb = nb @ q("dense1.weight").T + q("dense1.bias")
         gb = hb * _phi(hb)
-        a, c = gb[:, :256], gb[:, 256:]
-        cn, xhat_g, rstd_g = _ln64(c, q(f"{unit}.norm.weight"), q(f"{unit}.norm.bias"))
+        a, cc = gb[:, :c], gb[:, c:]
+        cn, xhat_g, rstd_g = _ln64(cc, q(f"{unit}.norm.weight"), q(f"{unit}.norm.bias"))
         idx = token_index(b, hc, wc, grid=(k == 0)).to(X.device)
         wt, bt = q(f"{unit}.dense.weight"), q(f"{unit}.dense.bias")
         mix = torch.empty_like(cn)
-        mix[idx.reshape(-1)] = (torch.einsum("pq,gqc->gpc", wt, cn[idx]) + bt[None, :, None]).reshape(-1, 256)
+        mix[idx.reshape(-1)] = (torch.einsum("pq,gqc->gpc", wt, cn[idx]) + bt[None, :, None]).reshape(-1, c)
         gated = a * (mix + 1.0)
         outs.append(z + gated @ q("dense2.weight").T + q("dense2.bias"))
-        keep.append(dict(z=z, nb=nb, xhat_b=xhat_b, rstd_b=rstd_b, hb=hb, a=a, c=c, cn=cn, xhat_g=xhat_g, rstd_g=rstd_g, idx=idx,
+        keep.append(dict(z=z, nb=nb, xhat_b=xhat_b, rstd_b=rstd_b, hb=hb, a=a, c=cc, cn=cn, xhat_g=xhat_g, rstd_g=rstd_g, idx=idx,
                          mix=mix, gated=gated))
     cat = torch.cat(outs, 1)
     y = cat @ P["dense2.weight"].T + P["dense2.bias"] + X
     out = {"y": y.reshape(x0.shape), "h0": h0, "hb": [kk["hb"] for kk in keep]}
     S = {"y": float((cat.abs() @ P["dense2.weight"].abs().T + P["dense2.bias"].abs() + X.abs()).max())}
     if g is not None:
-        G = g.reshape(n_pix, 256).double()
+        G = g.reshape(n_pix, c).double()
 
         def put(name, value, scale):
             out["d:" + name], S["d:" + name] = value, float(scale.max())
@@ -128,18 +131,18 @@ def restate64(x0, p, g=None):
         for k, (layer, unit) in enumerate(BRANCHES):
             q = lambda s: P[f"{layer}.{s}"]                     # noqa: E731
             kk = keep[k]
-            dz1 = dcat[:, 256 * k:256 * k + 256]
+            dz1 = dcat[:, c * k:c * k + c]
             put(f"{layer}.dense2.bias", dz1.sum(0), dz1.abs().sum(0))
             put(f"{layer}.dense2.weight", dz1.T @ kk["gated"], dz1.abs().T @ kk["gated"].abs())
             dgated = dz1 @ q("dense2.weight")
             da, dmix = dgated * (kk["mix"] + 1.0), dgated * kk["a"]
             idx = kk["idx"]
-            dm_g, cn_g = dmix[idx], kk["cn"][idx]               # [G,64,256]
+            dm_g, cn_g = dmix[idx], kk["cn"][idx]               # [G,64,C]
             put(f"{layer}.{unit}.dense.bias", dm_g.sum((0, 2)), dm_g.abs().sum((0, 2)))
             put(f"{layer}.{unit}.dense.weight", torch.einsum("gpc,gqc->pq", dm_g, cn_g),
                 torch.einsum("gpc,gqc->pq", dm_g.abs(), cn_g.abs()))
             dcn = torch.empty_like(dmix)
-            dcn[idx.reshape(-1)] = torch.einsum("pq,gpc->gqc", q(f"{unit}.dense.weight"), dm_g).reshape(-1, 256)
+            dcn[idx.reshape(-1)] = torch.einsum("pq,gpc->gqc", q(f"{unit}.dense.weight"), dm_g).reshape(-1, c)
             dc, dgain, dbias, _ = _ln64_bwd(dcn, kk["xhat_g"], kk["rstd_g"], q(f"{unit}.norm.weight"))
             put(f"{layer}.{unit}.norm.weight", dgain, (dcn * kk["xhat_g"]).abs().sum(0))
             put(f"{layer}.{unit}.norm.bias", dbias, dcn.abs().sum(0))
@@ -168,7 +171,8 @@ def _compose(x0, leaves):
     """The layer from oracle.oracle's own arithmetic (stage_forward's lines for it) in the dtype of its arguments -> y."""
     sd = {"L." + k: v for k, v in leaves.items()}
     t = F.gelu(oracle._lin(sd, "L.dense1", oracle._ln(sd, "L.norm", x0)))
-    u, v = t[..., :256], t[..., 256:]
+    c = x0.shape[-1]
+    u, v = t[..., :c], t[..., c:]
     u = oracle._gmlp_branch(sd, "L.grid_gmlp_layer", "grid_gating_unit", u, True)
     v = oracle._gmlp_branch(sd, "L.block_gmlp_layer", "block_gating_unit", v, False)
     return oracle._lin(sd, "L.dense2", torch.cat([u, v], dim=-1)) + x0
@@ -197,36 +201,36 @@ def compose_f32(x0, p, g=None, want_dx0=True):
     return y.detach(), grads
 
 
-def params_of(sd):
-    """The layer's 26 parameters out of a detector state dict -> dict PARAMS."""
-    return {k: sd[SD_PREFIX + k].detach().clone().float() for k in PARAMS}
+def params_of(sd, stage=4):
+    """The 26 parameters of ``down<stage>``'s layer out of a detector state dict -> dict PARAMS."""
+    return {k: sd[f"down{stage}.{_SD_LAYER}{k}"].detach().clone().float() for k in PARAMS}
 
 
 # ---- seeded cases -------------------------------------------------------------------------------------------------------------
-def sweep_params(seed):
-    """General random parameters: gains around 1, small biases, dense weights ~ 1 / sqrt(fan-in), a full non-symmetric Wt."""
+def sweep_params(seed, c=256):
+    """General random parameters at width ``c``: gains around 1, small biases, dense weights ~ 1 / sqrt(fan-in), a full non-symmetric Wt."""
     g = torch.Generator().manual_seed(seed)
     p = {}
     for k in PARAMS:
         leaf = k.rsplit(".", 2)[-2:]
         if leaf[0] == "norm":
-            p[k] = 1 + 0.3 * torch.randn(256, generator=g) if leaf[1] == "weight" else 0.2 * torch.randn(256, generator=g)
+            p[k] = 1 + 0.3 * torch.randn(c, generator=g) if leaf[1] == "weight" else 0.2 * torch.randn(c, generator=g)
         elif leaf[1] == "weight":
-            shape = {"dense1": (512, 256), "dense": (64, 64), "dense2": (256, 512 if k == "dense2.weight" else 256)}[leaf[0]]
+            shape = {"dense1": (2 * c, c), "dense": (64, 64), "dense2": (c, 2 * c if k == "dense2.weight" else c)}[leaf[0]]
             p[k] = torch.randn(shape, generator=g) / shape[1] ** 0.5
         else:
-            n = {"dense1": 512, "dense": 64, "dense2": 256}[leaf[0]]
+            n = {"dense1": 2 * c, "dense": 64, "dense2": c}[leaf[0]]
             p[k] = 0.2 * torch.randn(n, generator=g)
     return p, g
 
 
-def sweep_case(shape, seed, device=None):
-    """Seeded general float32 inputs for a shape -> (x0, params, g = dy), on the CPU.  x0 >= 0 with a share of exact zeros, as the
+def sweep_case(shape, seed, device=None, c=256):
+    """Seeded general float32 inputs for a shape at width ``c`` -> (x0, params, g = dy), on the CPU.  x0 >= 0 with a share of exact zeros, as the
     ReLU in front of the layer leaves it.  GELU has no kink: nothing to keep away from.  ``device``: where the case is moved to
     after it was drawn, on the CPU generator either way."""
     b, hc, wc = shape
-    p, g = sweep_params(seed)
-    x0 = (torch.randn((b, hc, wc, 256), generator=g) * (0.5 + torch.rand((b, hc, wc, 1), generator=g)) + 0.3).clamp(min=0)
+    p, g = sweep_params(seed, c)
+    x0 = (torch.randn((b, hc, wc, c), generator=g) * (0.5 + torch.rand((b, hc, wc, 1), generator=g)) + 0.3).clamp(min=0)
     dy = torch.randn(x0.shape, generator=g) / (b * hc * wc)
     return T.to_device((x0, p, dy), device)
 
@@ -243,35 +247,36 @@ def model_inputs():
 
 LAYOUT_SHAPE = (1, 16, 24)                  # regions of 2 x 3 pixels: both maps and the orientation of Wt each change the result
 EDGES_SHAPE = (2, 8, 16)
-EDGES_CONST_ROW = (1, 2, 5)                 # the pixel of x0 whose 256 channels are all 0.5: var = 0, xhat = 0 exactly
+EDGES_CONST_ROW = (1, 2, 5)                 # the pixel of x0 whose channels are all 0.5: var = 0, xhat = 0 exactly
 EDGES_GATE0 = 37                            # the block map's token with a zero row of Wt and bt = -1: mix + 1 == 0 exactly
 EDGES_GAIN0 = 5                             # the channel with gain 0 in the three LayerNorms of the grid branch
-EDGES_SAT = ((3, 9.0), (4, -9.0), (300, 9.0), (301, -9.0))     # (channel of a dense1 output, bias): GELU saturated both ways
+# width -> (channel of a dense1 output, bias): GELU saturated both ways, one pair in each half of the 2C outputs
+EDGES_SAT = {256: ((3, 9.0), (4, -9.0), (300, 9.0), (301, -9.0)), 128: ((3, 9.0), (4, -9.0), (150, 9.0), (151, -9.0))}
 # the grid branch's c half: dense1 weight 0 and this bias -> c = gelu(9) = 9 on every channel of every pixel, exactly so in float32 and
-# in float64 (Phi(9) rounds to 1), and sums of up to 256 nines are exact in any order: the gating LayerNorm sees var = 0, xhat = 0
+# in float64 (Phi(9) rounds to 1), and sums of up to C nines are exact in any order: the gating LayerNorm sees var = 0, xhat = 0
 EDGES_C_BIAS = 9.0
 RECORD_WHOLE = 1 << 12                      # a reference result with more elements than this is recorded on some rows only
 
 
-def layout_inputs():
-    return sweep_case(LAYOUT_SHAPE, 2718)
+def layout_inputs(c=256):
+    return sweep_case(LAYOUT_SHAPE, 2718, c=c)
 
 
-def edges_inputs():
-    """Case ``edges`` -> (x0, params, g = dy): the sweep's generator on EDGES_SHAPE with the edges named above."""
-    x0, p, dy = sweep_case(EDGES_SHAPE, 4242)
+def edges_inputs(c=256):
+    """Case ``edges`` at width ``c`` -> (x0, params, g = dy): the sweep's generator on EDGES_SHAPE with the edges named above."""
+    x0, p, dy = sweep_case(EDGES_SHAPE, 4242, c=c)
     x0[EDGES_CONST_ROW] = 0.5
     gl, gu = BRANCHES[0]
     bl, bu = BRANCHES[1]
-    p[f"{gl}.dense1.weight"][256:] = 0.0
-    p[f"{gl}.dense1.bias"][256:] = EDGES_C_BIAS
+    p[f"{gl}.dense1.weight"][c:] = 0.0
+    p[f"{gl}.dense1.bias"][c:] = EDGES_C_BIAS
     p[f"{bl}.{bu}.dense.weight"][EDGES_GATE0] = 0.0
     p[f"{bl}.{bu}.dense.bias"][EDGES_GATE0] = -1.0
     for k in (f"{gl}.norm.weight", f"{gl}.{gu}.norm.weight", "norm.weight"):
         p[k][EDGES_GAIN0] = 0.0
     for k in ("dense1.bias", f"{bl}.dense1.bias"):
-        for c, v in EDGES_SAT:
-            p[k][c] = v
+        for ch, v in EDGES_SAT[c]:
+            p[k][ch] = v
     return x0, p, dy
 
 

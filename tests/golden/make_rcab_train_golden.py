@@ -33,7 +33,7 @@ from tests import rcab_train_common as R                                        
 
 def block_grads(block, y):
     own = dict(block.named_parameters())
-    out = {"d" + k: own[n].grad for k, n in R._SD_NAMES.items()}
+    out = {"d" + k: own[n].grad for k, n in R.SD_NAMES.items()}
     out["dy"] = y.grad
     return out
 
@@ -67,7 +67,7 @@ def run_edges_case():
     block = ResidualChannelAttentionBlock(256).train()
     own = dict(block.named_parameters())
     with torch.no_grad():
-        for k, n in R._SD_NAMES.items():
+        for k, n in R.SD_NAMES.items():
             own[n].copy_(p[k])
     yy = y.clone().requires_grad_()
     x2 = block(yy) + (r - y)                                   # the block adds its own shortcut y; r - y is the long one

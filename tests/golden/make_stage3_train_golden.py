@@ -36,8 +36,10 @@ sys.path.insert(0, ROOT)
 from tests.golden.make_golden import ref_model                                      # noqa: E402  (puts the reference on the path)
 from tests.golden.make_linrelu_train_golden import reference_loss                    # noqa: E402
 from balf.model.mlp_ma_decoder import ResidualChannelAttentionBlock, ResidualSplitHeadMultiAxisGmlpLayer   # noqa: E402  (reference)
+from tests import gmlp_train_common as Gc                                           # noqa: E402
 from tests import head_train_common as H                                            # noqa: E402
 from tests import linrelu_train_common as Lc                                        # noqa: E402
+from tests import rcab_train_common as Rc                                           # noqa: E402
 from tests import stage3_train_common as Sc                                         # noqa: E402
 
 
@@ -155,8 +157,8 @@ def main():
     fx["stage.pool_gap"], fx["stage.pool_moved"] = np.float64(res["pool_gap"]), np.float64(moved)
     # ---- the units at C = 128
     for unit, cases, run, restate, autograd, gated, grads in (
-            ("rcab", Sc.RCAB_CASES, run_rcab_case, Sc.rcab_restate64, Sc.rcab_autograd64, Sc.RCAB_GATED, Sc.RCAB_GRADS),
-            ("gmlp", Sc.GMLP_CASES, run_gmlp_case, Sc.gmlp_restate64, Sc.gmlp_autograd64, Sc.GMLP_GATED, Sc.GMLP_GRADS)):
+            ("rcab", Sc.RCAB_CASES, run_rcab_case, Rc.restate64, Rc.autograd64, Sc.RCAB_GATED, Sc.RCAB_GRADS),
+            ("gmlp", Sc.GMLP_CASES, run_gmlp_case, Gc.restate64, Gc.autograd64, Sc.GMLP_GATED, Sc.GMLP_GRADS)):
         d = {}
         for name in cases:
             inputs, got, seen = run(name)

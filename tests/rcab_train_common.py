@@ -1,7 +1,9 @@
 """Shared by tests/test_rcab_train_host.py, tests/test_rcab_train_gpu.py, tests/golden/make_rcab_train_golden.py and
-tools/bench_tail_train.py: the fixture rcab_train.npz, the float64 restatement of stage 4's channel-attention block (LayerNorm ->
-conv1 -> LeakyReLU(0.2) -> conv2 -> squeeze-excite scale, x2 = t * s + r) and of its backward as closed formulas, the same through
-float64 autograd, the float32 torch-op composition, the error measure of the gates, and the seeded case generators."""
+tools/bench_tail_train.py, and by the stage-3 tests through tests/stage3_train_common.py: the fixture rcab_train.npz, the float64
+restatement of the channel-attention block (LayerNorm -> conv1 -> LeakyReLU(0.2) -> conv2 -> squeeze-excite scale, x2 = t * s + r)
+and of its backward as closed formulas, the same through float64 autograd, the float32 torch-op composition, the error measure of
+the gates, and the seeded case generators.  All of it at a width C: the last dimension of the input where there is one, ``c``
+(256, stage 4's, unless stated) in the generators; the squeeze-excite has C / 4 units."""
 import functools
 import os
 
@@ -26,8 +28,8 @@ SLOPE = 0.2
 # the image are seeded -- and its closest h lies at 4.9e-6, where torch's float32 moved it by 1.5e-8.
 KINK_MARGIN = 4e-6
 SWEEP_MARGIN = 1e-3                         # the sweep's inputs keep every h and every SE pre-activation this far from 0
-_SD_PREFIX = "down4.residual_channel_attention_block."
-_SD_NAMES = dict(zip(PARAMS, ("norm.weight", "norm.bias", "conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias",
+_SD_BLOCK = "residual_channel_attention_block."
+SD_NAMES = dict(zip(PARAMS, ("norm.weight", "norm.bias", "conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias",
                               "calayer.excite.0.weight", "calayer.excite.0.bias", "calayer.excite.2.weight",
                               "calayer.excite.2.bias")))
 err, inputs_digest = T.err, T.inputs_digest
@@ -38,13 +40,13 @@ def fixture():
 
 
 def restate64(y, r, p, g=None):
-    """The equations of include/balf_hip.h in float64 on the CPU.  ``y``, ``r`` [B,Hc,Wc,256]; ``p``: dict PARAMS; ``g`` = dx2 or
+    """The equations of include/balf_hip.h in float64 on the CPU.  ``y``, ``r`` [B,Hc,Wc,C]; ``p``: dict PARAMS; ``g`` = dx2 or
     None.  -> dict of float64 tensors: x2, the intermediates, the eleven gradients, and ``S``: name -> the scale of the error
     measure, the largest sum of absolute values of the terms of that output's last reduction (for x2 and dy the terms that
     follow the reduction are carried along: t * s + r, and rstd times the three terms of the LayerNorm's backward)."""
-    b, hc, wc, _ = y.shape
+    b, hc, wc, c = y.shape
     hw, n_pix = hc * wc, b * hc * wc
-    Y, R = y.reshape(n_pix, 256).double(), r.reshape(n_pix, 256).double()
+    Y, R = y.reshape(n_pix, c).double(), r.reshape(n_pix, c).double()
     ln_g, ln_b, wc1, bc1, wc2, bc2, ws0, bs0, ws2, bs2 = (p[k].double() for k in PARAMS)
     mean = Y.mean(1, keepdim=True)
     rstd = 1.0 / torch.sqrt(((Y - mean) ** 2).mean(1, keepdim=True) + LN_EPS)
@@ -53,17 +55,17 @@ def restate64(y, r, p, g=None):
     h = n @ wc1.T + bc1
     a = torch.where(h > 0, h, SLOPE * h)
     t = a @ wc2.T + bc2
-    m = t.reshape(b, hw, 256).mean(1)
+    m = t.reshape(b, hw, c).mean(1)
     pre = m @ ws0.T + bs0
     e = pre.clamp(min=0)
     s = torch.sigmoid(e @ ws2.T + bs2)
-    sp = s.repeat_interleave(hw, dim=0)                     # [N,256]
+    sp = s.repeat_interleave(hw, dim=0)                     # [N,C]
     out = {"xhat": xhat, "rstd": rstd, "n": n, "h": h, "a": a, "t": t, "m": m, "se_pre": pre, "e": e, "s": s,
            "x2": (t * sp + R).reshape(y.shape)}
     S = {"x2": float((((a.abs() @ wc2.abs().T) + bc2.abs()) * sp + R.abs()).max())}
     if g is not None:
-        G = g.reshape(n_pix, 256).double()
-        ds = (G * t).reshape(b, hw, 256).sum(1)
+        G = g.reshape(n_pix, c).double()
+        ds = (G * t).reshape(b, hw, c).sum(1)
         dq = ds * s * (1 - s)
         de = (dq @ ws2) * (pre > 0)
         dm = de @ ws0
@@ -93,7 +95,7 @@ def _compose(y, r, leaves):
     """The block from torch's own ops in the dtype of its arguments -> x2.  ``r`` - y, the long shortcut, is a constant; the
     block's own shortcut y carries a gradient."""
     x0 = (r - y).detach()
-    n = F.layer_norm(y, (256,), leaves["ln_g"], leaves["ln_b"], LN_EPS)
+    n = F.layer_norm(y, (y.shape[-1],), leaves["ln_g"], leaves["ln_b"], LN_EPS)
     t = F.linear(F.leaky_relu(F.linear(n, leaves["wc1"], leaves["bc1"]), SLOPE), leaves["wc2"], leaves["bc2"])
     s = torch.sigmoid(F.linear(F.relu(F.linear(t.mean(dim=(1, 2)), leaves["ws0"], leaves["bs0"])), leaves["ws2"], leaves["bs2"]))
     return t * s[:, None, None, :] + y + x0
@@ -128,27 +130,28 @@ def kink_distances(res):
     return H.kink_distance(res["h"]), H.kink_distance(res["se_pre"])
 
 
-def params_of(sd):
-    """The block's ten parameters out of a detector state dict -> dict PARAMS."""
-    return {k: sd[_SD_PREFIX + n].detach().clone().float() for k, n in _SD_NAMES.items()}
+def params_of(sd, stage=4):
+    """The ten parameters of ``down<stage>``'s block out of a detector state dict -> dict PARAMS."""
+    return {k: sd[f"down{stage}.{_SD_BLOCK}{n}"].detach().clone().float() for k, n in SD_NAMES.items()}
 
 
 # ---- the shape sweep --------------------------------------------------------------------------------------------------------
-def sweep_params(seed):
+def sweep_params(seed, c=256):
     g = torch.Generator().manual_seed(seed)
     rn = lambda *s: torch.randn(s, generator=g)            # noqa: E731
-    return {"ln_g": 1 + 0.3 * rn(256), "ln_b": 0.2 * rn(256), "wc1": rn(256, 256) / 16, "bc1": 0.2 * rn(256),
-            "wc2": rn(256, 256) / 16, "bc2": 0.2 * rn(256), "ws0": rn(64, 256) / 8, "bs0": 0.3 * rn(64), "ws2": rn(256, 64) / 4,
-            "bs2": 0.5 * rn(256)}, g
+    h = c // 4
+    return {"ln_g": 1 + 0.3 * rn(c), "ln_b": 0.2 * rn(c), "wc1": rn(c, c) / c ** 0.5, "bc1": 0.2 * rn(c), "wc2": rn(c, c) / c ** 0.5,
+            "bc2": 0.2 * rn(c), "ws0": rn(h, c) / (c / 4) ** 0.5, "bs0": 0.3 * rn(h), "ws2": rn(c, h) / (h / 4) ** 0.5,
+            "bs2": 0.5 * rn(c)}, g
 
 
 def _h64(rows, p):
-    n = F.layer_norm(rows.double(), (256,), p["ln_g"].double(), p["ln_b"].double(), LN_EPS)
+    n = F.layer_norm(rows.double(), (rows.shape[-1],), p["ln_g"].double(), p["ln_b"].double(), LN_EPS)
     return n @ p["wc1"].double().T + p["bc1"].double()
 
 
 def redraw_rows_near_kink(y, p, draw, margin=SWEEP_MARGIN, rounds=64):
-    """``y`` [N,256] with every row whose h (float64) has an element within ``margin`` of 0 drawn again by ``draw(count)``,
+    """``y`` [N,C] with every row whose h (float64) has an element within ``margin`` of 0 drawn again by ``draw(count)``,
     until none is left.  LayerNorm makes h a function of the row alone.  -> (y, rows redrawn in each round)."""
     counts = []
     for _ in range(rounds):
@@ -161,8 +164,8 @@ def redraw_rows_near_kink(y, p, draw, margin=SWEEP_MARGIN, rounds=64):
     raise AssertionError("rows near the LeakyReLU kink remain")
 
 
-def sweep_case(shape, seed, device=None):
-    """Seeded general float32 inputs for a shape -> (y, r, params, g = dx2), on the CPU.  No h within SWEEP_MARGIN of 0 (rows
+def sweep_case(shape, seed, device=None, c=256):
+    """Seeded general float32 inputs for a shape at width ``c`` -> (y, r, params, g = dx2), on the CPU.  No h within SWEEP_MARGIN of 0 (rows
     redrawn), no SE pre-activation within SWEEP_MARGIN of 0 (bs0 redrawn; asserted): a float32 rounding of a pre-activation
     across 0 would change a slope by 0.8 (LeakyReLU) or 1 (ReLU) of a whole term at any tolerance, and float32 moves h by
     3.3e-6 at most here.
@@ -172,21 +175,21 @@ def sweep_case(shape, seed, device=None):
     of tens of thousands of pixels)."""
     b, hc, wc = shape
     n_pix = b * hc * wc
-    p, g = sweep_params(seed)
+    p, g = sweep_params(seed, c)
     p = T.to_device(p, device)
     on = lambda t: T.to_device(t, device)                  # noqa: E731
 
     def draw(k):
-        return on(torch.randn((k, 256), generator=g) * (0.5 + torch.rand((k, 1), generator=g)) + 0.3 * torch.randn((k, 1), generator=g))
+        return on(torch.randn((k, c), generator=g) * (0.5 + torch.rand((k, 1), generator=g)) + 0.3 * torch.randn((k, 1), generator=g))
 
     y, _ = redraw_rows_near_kink(draw(n_pix), p, draw)
-    y = y.reshape(b, hc, wc, 256)
+    y = y.reshape(b, hc, wc, c)
     r = y + on(torch.randn(y.shape, generator=g)).clamp(min=0)
     dx2 = on(torch.randn(y.shape, generator=g) / n_pix)
     for _ in range(64):
         if float(restate64(y, r, p)["se_pre"].abs().min()) >= SWEEP_MARGIN:
             break
-        p["bs0"] = on(0.3 * torch.randn((64,), generator=g))
+        p["bs0"] = on(0.3 * torch.randn((c // 4,), generator=g))
     assert float(restate64(y, r, p)["se_pre"].abs().min()) >= SWEEP_MARGIN
     return y, r, p, dx2
 
@@ -202,31 +205,32 @@ def model_inputs():
 
 EDGES_SHAPE = (3, 3, 5)
 EDGES_LN_G0 = 5                             # the channel with ln_g = 0
-EDGES_CONST_ROW = (1, 2, 3)                 # the pixel whose 256 channels are all 0.5: var = 0, xhat = 0, rstd = 1 / sqrt(eps)
+EDGES_CONST_ROW = (1, 2, 3)                 # the pixel whose channels are all 0.5: var = 0, xhat = 0, rstd = 1 / sqrt(eps)
 EDGES_H0 = 8                                # ln_b = 0 and bc1 = 0 on channels 0..7: h == 0 exactly there on the constant row
 EDGES_E0 = 7                                # the SE hidden unit with ws0 row and bs0 zero: e == 0 exactly
 EDGES_SAT = ((11, 30.0), (12, -30.0))       # (channel, bs2): the saturated sigmoids
 RECORD_WHOLE = 1 << 14                      # a reference result with more elements than this is recorded on some rows only
 
 
-def edges_inputs():
-    """Case ``edges`` -> (y, r, params, g = dx2): the sweep's generator on EDGES_SHAPE with the edges named above."""
-    p, g = sweep_params(4242)
+def edges_inputs(c=256):
+    """Case ``edges`` at width ``c`` -> (y, r, params, g = dx2): the sweep's generator on EDGES_SHAPE with the edges named above
+    (the same places at every width; all lie below 32)."""
+    p, g = sweep_params(4242, c)
     p["ln_g"][EDGES_LN_G0] = 0.0
     p["ln_b"][:] = 0.0
     p["bc1"][:EDGES_H0] = 0.0
     p["ws0"][EDGES_E0] = 0.0
     p["bs0"][EDGES_E0] = 0.0
-    for c, v in EDGES_SAT:
-        p["bs2"][c] = v
+    for ch, v in EDGES_SAT:
+        p["bs2"][ch] = v
     b, hc, wc = EDGES_SHAPE
     n_pix = b * hc * wc
 
     def draw(k):
-        return 4 * torch.randn((k, 256), generator=g) + torch.randn((k, 1), generator=g)
+        return 4 * torch.randn((k, c), generator=g) + torch.randn((k, 1), generator=g)
 
     y, _ = redraw_rows_near_kink(draw(n_pix), p, draw)
-    y = y.reshape(b, hc, wc, 256)
+    y = y.reshape(b, hc, wc, c)
     y[EDGES_CONST_ROW] = 0.5
     r = y + torch.randn(y.shape, generator=g).clamp(min=0)
     dx2 = torch.randn(y.shape, generator=g) / n_pix

@@ -128,7 +128,7 @@ def test_restatement_edges(cases):
     for k in (f"d:{gl}.norm.weight", "d:norm.weight"):          # the gradient of a zero gain is no zero
         assert float(res[k][G.EDGES_GAIN0].abs()) > 1e-3 * res["S"][k], k
     h0, hb = res["h0"], res["hb"][1]
-    for c, v in G.EDGES_SAT:                                    # saturated both ways, inside the normal range
+    for c, v in G.EDGES_SAT[256]:                                    # saturated both ways, inside the normal range
         for h in (h0, hb):
             assert bool((h[:, c] > 3).all()) if v > 0 else bool((h[:, c] < -3).all())
             assert float(h[:, c].abs().max()) > 9 and float(h.abs().max()) < 40

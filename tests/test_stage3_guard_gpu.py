@@ -21,7 +21,7 @@ class Rcab128(Rcab):
     name = "rcab128"
 
     def case(self, shape):
-        return Sc.rcab_sweep_case(shape, self.seed(shape), device=DEV)
+        return R.sweep_case(shape, self.seed(shape), device=DEV, c=C3)
 
     def outputs(self, shape):
         act = tuple(shape) + (C3,)
@@ -55,7 +55,7 @@ class Gmlp128(Gmlp):
     name = "gmlp128"
 
     def case(self, shape):
-        return Sc.gmlp_sweep_case(shape, self.seed(shape), device=DEV)
+        return G.sweep_case(shape, self.seed(shape), device=DEV, c=C3)
 
     def outputs(self, shape):
         act = tuple(shape) + (C3,)

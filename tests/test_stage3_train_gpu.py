@@ -2,7 +2,8 @@
 (balf_rcab_train_*_c, balf_gmlp_train_*_c, ops.*(channels=128)), the 2 x 2 max-pool (balf_pool_train_*, ops.pool_train_*),
 model.stage3_train.TrainableStage3, MLP_MA_DECODER.encode(level="stage2") and utils.train_utils.train_head with it, against
 tests/golden/stage3_train.npz -- the reference's own modules and autograd, recorded by tests/golden/make_stage3_train_golden.py
--- and the float64 restatements of tests/stage3_train_common.py.  Every output T of the two units and of the whole stage is
+-- and the float64 restatements of the units (tests/rcab_train_common.py, tests/gmlp_train_common.py at c = 128) and of the
+stage (tests/stage3_train_common.py).  Every output T of the two units and of the whole stage is
 gated by err(T) = max |T - T64| / S_T <= tol_T = max(4 * d_T, 1.1e-6), d_T the reference's own float32 distance from the
 restatement; the pool is exact: the bits of torch's CPU max_pool2d and of its autograd."""
 import ctypes as C
@@ -91,7 +92,7 @@ def test_rcab_fixture_cases(fx, name):
     y, r, p, g = Sc.rcab_case(name)
     assert T.inputs_digest(y, r, p, g) == str(fx[f"rcab.{name}.inputs_sha256"])
     out = run_rcab(y, r, p, g)
-    check_against(out, Sc.rcab_restate64(y, r, p, g), fx, "rcab", f"rcab128 {name}", R.GATED)
+    check_against(out, R.restate64(y, r, p, g), fx, "rcab", f"rcab128 {name}", R.GATED)
     lean = run_rcab(y, r, p, g, want_dy=False)
     assert lean["dy"] is None and all(bits_equal(out[k], lean[k]) for k in R.GATED[:-1])     # dy not requested: the same bits
     if name == "edges":
@@ -102,9 +103,9 @@ def test_rcab_fixture_cases(fx, name):
 @pytest.mark.parametrize("shape", RCAB_SWEEP)
 def test_rcab_sweep(fx, shape):
     big = shape[0] * shape[1] * shape[2] > 4096
-    y, r, p, g = Sc.rcab_sweep_case(shape, 100 + sum(shape), device=DEV if big else None)
+    y, r, p, g = R.sweep_case(shape, 100 + sum(shape), device=DEV if big else None, c=C3)
     out = run_rcab(y, r, p, g)
-    check_against(out, Sc.rcab_restate64(y, r, p, g), fx, "rcab", f"rcab128 {shape}", R.GATED)
+    check_against(out, R.restate64(y, r, p, g), fx, "rcab", f"rcab128 {shape}", R.GATED)
     again = run_rcab(y, r, p, g, want_dy=False)
     assert all(bits_equal(out[k], again[k]) for k in R.GATED[:-1])
 
@@ -115,7 +116,7 @@ def test_gmlp_fixture_cases(fx, name):
     x0, p, g = Sc.gmlp_case(name)
     assert T.inputs_digest(x0, p, g) == str(fx[f"gmlp.{name}.inputs_sha256"])
     out = run_gmlp(x0, p, g)
-    res = Sc.gmlp_restate64(x0, p, g)
+    res = G.restate64(x0, p, g)
     check_against(out, res, fx, "gmlp", f"gmlp128 {name}", G.GATED)
     lean = run_gmlp(x0, p, g, want_dx0=False)
     assert lean["dx0"] is None and all(bits_equal(out[k], lean[k]) for k in G.GATED[:-1])    # dx0 not requested: the same bits
@@ -124,18 +125,18 @@ def test_gmlp_fixture_cases(fx, name):
         (gl, gu), (bl, bu) = G.BRANCHES
         swapped = dict(p)
         swapped[f"{gl}.{gu}.dense.weight"] = p[f"{gl}.{gu}.dense.weight"].T.contiguous()
-        assert Sc.err(Sc.gmlp_restate64(x0, swapped)["y"], res["y"], res["S"]["y"]) > 1e-3
+        assert Sc.err(G.restate64(x0, swapped)["y"], res["y"], res["S"]["y"]) > 1e-3
         for k in ("dense.weight", "dense.bias"):
             swapped = dict(p)
             swapped[f"{gl}.{gu}.{k}"], swapped[f"{bl}.{bu}.{k}"] = p[f"{bl}.{bu}.{k}"], p[f"{gl}.{gu}.{k}"]
-            assert Sc.err(Sc.gmlp_restate64(x0, swapped)["y"], res["y"], res["S"]["y"]) > 1e-3
+            assert Sc.err(G.restate64(x0, swapped)["y"], res["y"], res["S"]["y"]) > 1e-3
 
 
 @pytest.mark.parametrize("shape", GMLP_SWEEP)
 def test_gmlp_sweep(fx, shape):
-    x0, p, g = Sc.gmlp_sweep_case(shape, 200 + sum(shape))
+    x0, p, g = G.sweep_case(shape, 200 + sum(shape), c=C3)
     out = run_gmlp(x0, p, g)
-    check_against(out, Sc.gmlp_restate64(x0, p, g), fx, "gmlp", f"gmlp128 {shape}", G.GATED)
+    check_against(out, G.restate64(x0, p, g), fx, "gmlp", f"gmlp128 {shape}", G.GATED)
     again = run_gmlp(x0, p, g, want_dx0=False)
     assert all(bits_equal(out[k], again[k]) for k in G.GATED[:-1])
 
@@ -248,7 +249,7 @@ def test_pool_argument_errors():
 def test_graph_capture_of_the_pool_and_the_rcab():
     """Forward and backward of the pool and of the block at C = 128, captured once and replayed on new inputs."""
     shape = (2, 6, 10)
-    cases = [Sc.rcab_sweep_case(shape, 60 + i) for i in range(3)]
+    cases = [R.sweep_case(shape, 60 + i, c=C3) for i in range(3)]
     y, r, p, g = cases[0]
     static = {"y": y.to(DEV), "r": r.to(DEV), "g": g.to(DEV), **{k: v.to(DEV) for k, v in p.items()}}
     gp = torch.randn((2, 3, 5, C3), generator=torch.Generator().manual_seed(9)).to(DEV)

@@ -1,7 +1,7 @@
 """What stage 3's training adds, without a GPU: balf_train_unit_sizes against the existing size queries and against a Python
 restatement of the layouts, its error codes, the ops' argument checks at channels=128, the parameter shapes and counts,
-TrainableStage3's state handling, the float64 restatements of tests/stage3_train_common.py against float64 autograd over torch's
-own ops, and the fixture against the restatements."""
+TrainableStage3's state handling, the units' float64 restatements at C = 128 and that of the stage (tests/stage3_train_common.py)
+against float64 autograd over torch's own ops, and the fixture against the restatements."""
 import ctypes as C
 import os
 
@@ -138,7 +138,7 @@ def test_param_shapes_and_counts():
 
 
 def test_ops_argument_errors_at_128():
-    y, r, p, g = Sc.rcab_sweep_case((1, 2, 3), 1)
+    y, r, p, g = R.sweep_case((1, 2, 3), 1, c=C3)
     params = [p[k] for k in R.PARAMS]
     with pytest.raises(_lib.BalfHipError, match="GPU"):                      # right in every respect but the device
         ops.rcab_train_forward(y, r, params, channels=128)
@@ -157,7 +157,7 @@ def test_ops_argument_errors_at_128():
                                 channels=128)
     with pytest.raises(_lib.BalfHipError, match="GPU"):
         ops.rcab_train_backward(g, y, p["ln_g"], p["wc1"], p["wc2"], p["ws0"], p["ws2"], torch.zeros(8, dtype=torch.uint8), channels=128)
-    x0, gp, dy = Sc.gmlp_sweep_case((1, 8, 8), 2)
+    x0, gp, dy = G.sweep_case((1, 8, 8), 2, c=C3)
     gparams = [gp[k] for k in G.PARAMS]
     with pytest.raises(_lib.BalfHipError, match="GPU"):
         ops.gmlp_train_forward(x0, gparams, channels=128)
@@ -242,19 +242,14 @@ def test_trainable_stage3_state():
 
 # ---- the restatements and the fixture ------------------------------------------------------------------------------------------
 def test_restatements_at_128_against_autograd():
-    y, r, p, g = Sc.rcab_sweep_case((2, 3, 5), 3)
-    res, ag = Sc.rcab_restate64(y, r, p, g), Sc.rcab_autograd64(y, r, p, g)
+    y, r, p, g = R.sweep_case((2, 3, 5), 3, c=C3)
+    res, ag = R.restate64(y, r, p, g), R.autograd64(y, r, p, g)
     assert all(Sc.err(ag[k], res[k], res["S"][k]) <= 1e-12 for k in R.GRADS)
-    x0, gp, dy = Sc.gmlp_sweep_case(G.LAYOUT_SHAPE, 4)
-    res, ag = Sc.gmlp_restate64(x0, gp, dy), Sc.gmlp_autograd64(x0, gp, dy)
+    x0, gp, dy = G.sweep_case(G.LAYOUT_SHAPE, 4, c=C3)
+    res, ag = G.restate64(x0, gp, dy), G.autograd64(x0, gp, dy)
     assert all(Sc.err(ag[k], res[k], res["S"][k]) <= 1e-12 for k in G.GRADS)
-    # at 256 they are the siblings' restatements
-    y, r, p, g = R.sweep_case((1, 2, 3), 5)
-    a, b = Sc.rcab_restate64(y, r, p, g), R.restate64(y, r, p, g)
-    assert all(torch.equal(a[k], b[k]) for k in R.GATED) and a["S"] == b["S"]
-    x0, gp, dy = G.sweep_case((1, 8, 8), 6)
-    a, b = Sc.gmlp_restate64(x0, gp, dy), G.restate64(x0, gp, dy)
-    assert all(torch.equal(a[k], b[k]) for k in G.GATED) and a["S"] == b["S"]
+    # the width is the input's: the stage's own copies of these restatements are gone, and the one statement serves both widths
+    assert res["y"].shape[-1] == C3 and R.restate64(*R.sweep_case((1, 2, 3), 5))["x2"].shape[-1] == 256
 
 
 def test_pool_reference_rule():
@@ -292,8 +287,8 @@ def test_fixture_against_the_restatements(fx):
     for name, h in res["kinks"].items():
         nz = h[h != 0].abs().min()
         assert float(nz) == float(fx[f"stage.kink.{name}"]) > float(fx[f"stage.moved.{name}"]), name
-    for unit, cases, case, restate, gated in (("rcab", Sc.RCAB_CASES, Sc.rcab_case, Sc.rcab_restate64, R.GATED),
-                                              ("gmlp", Sc.GMLP_CASES, Sc.gmlp_case, Sc.gmlp_restate64, G.GATED)):
+    for unit, cases, case, restate, gated in (("rcab", Sc.RCAB_CASES, Sc.rcab_case, R.restate64, R.GATED),
+                                              ("gmlp", Sc.GMLP_CASES, Sc.gmlp_case, G.restate64, G.GATED)):
         worst = {k: 0.0 for k in gated}
         for name in cases:
             inputs = case(name)
@@ -306,6 +301,6 @@ def test_fixture_against_the_restatements(fx):
             assert worst[k] <= float(fx[f"{unit}.d_{k}"]) * (1 + 1e-9), (unit, k)
     # case edges holds its edges
     y, r, p, g = Sc.rcab_case("edges")
-    res = Sc.rcab_restate64(y, r, p, g)
+    res = R.restate64(y, r, p, g)
     assert bool((res["h"].reshape(3, 3, 5, C3)[R.EDGES_CONST_ROW][:R.EDGES_H0] == 0).all())
     assert float(res["se_pre"][:, R.EDGES_E0].abs().max()) == 0.0 and float(res["dws0"][R.EDGES_E0].abs().max()) == 0.0
