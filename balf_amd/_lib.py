@@ -18,6 +18,7 @@ MAX_NMS_SIZE, MAX_TOPK = 32, 16384
 PYR_SRC_U8, PYR_SRC_F32, PYR_SRC_LEVEL = 0, 1, 2                   # include/balf_hip.h: balf_pyramid_level
 PYR_MAX_RADIUS, MAX_PYRAMID_LEVELS = 8, 32
 VAL_LEG_GREEDY, VAL_LEG_WINDOW = 0, 1                              # include/balf_hip.h: balf_val_points
+NMS_MAP_GREEDY, NMS_MAP_BOX, NMS_MAP_MAX_RADIUS = 0, 1, 16         # include/balf_hip.h: balf_nms_score_map
 STATUS_SCORE, STATUS_RANGE, STATUS_SE, STATUS_WORDS = 0, 1, 2, 4      # include/balf_hip.h: balf_forward_status
 UNIT_RCAB, UNIT_GMLP, UNIT_POOL = 0, 1, 2                          # include/balf_hip.h: balf_train_unit_sizes
 OPTIM_MAX_TENSORS = 64                                             # include/balf_hip.h: balf_adam_step / balf_sgd_step
@@ -52,6 +53,8 @@ PROTOTYPES = {
     "balf_greedy_nms_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "balf_greedy_nms": (_i, [_fp, _i, _i, _i, _i, _i, _i, _i, _i, C.c_float, _i, _i, _i, _vp, _fp, _fp, _vp, _vp, _vp,
                             _sz, _vp]),
+    "balf_nms_score_map_sizes": (_i, [_i, _i, _i, _i, C.POINTER(_sz)]),
+    "balf_nms_score_map": (_i, [_fp, _i, _i, _i, _i, C.c_float, _i, C.POINTER(C.c_uint64), _i, _i, _fp, _vp, _vp, _sz, _vp]),
     "balf_hardnet_num_state_tensors": (_i, []),
     "balf_hardnet_state_tensor_name": (C.c_char_p, [_i]),
     "balf_hardnet_state_tensor_numel": (_sz, [_i]),

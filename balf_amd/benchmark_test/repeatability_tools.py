@@ -5,6 +5,8 @@ become one call into ``balf_repeatability`` (include/balf_hip.h); float64 throug
 ``compute_repeatability_batch`` is the same for P pairs in one stream-ordered call (``balf_repeatability_batch``).
 
 ``apply_nms`` of the same reference module (:19-23) is the window-max NMS: use ``balf_amd.utils.test_utils.apply_nms``.
+Its other NMS protocols as score maps -- ``apply_nms_fast`` (:25-79), ``get_nms_score_map_from_score_map`` (:82-100) and
+``box_nms`` (:227-255) -- are here under their names, with batched forms that stay on the device (``balf_nms_score_map``).
 """
 from __future__ import annotations
 
@@ -121,6 +123,57 @@ def compute_repeatability_batch(src, ns, dst, nd, overlap_err=0.4, eps=1e-6, dis
            float(overlap_err), float(eps), float(dist_match_thresh), float(radious_size), int(max_edges), rep, cnt, Workspace(ws))
     return RepeatabilityBatch(rep[:, 0], rep[:, 1], rep[:, 2], rep[:, 3], cnt[:, 0], cnt[:, 1], cnt[:, 2], cnt[:, 3],
                               cnt[:, 4], cnt[:, 5])
+
+
+# ---- NMS score maps (reference repeatability_tools.py:25-100, 227-255) --------------------------------------------------------
+def box_nms_batch(prob, size=4, iou=0.1, min_prob=0.015, keep_top_k=-1):
+    """:func:`box_nms` of every map of ``prob`` [B,H,W] (float32, on the GPU) in one stream-ordered call -> [B,H,W] on the same
+    device.  Nothing is read back."""
+    return ops.nms_score_map(prob, "box", conf_thresh=min_prob, size=size, iou=iou, keep_top_k=keep_top_k)[0]
+
+
+def nms_fast_score_map_batch(prob, dist_thresh, conf_thresh=0.015):
+    """:func:`apply_nms_fast` of every map of ``prob`` [B,H,W] (float32, on the GPU) in one stream-ordered call -> [B,H,W] on
+    the same device.  Nothing is read back."""
+    return ops.nms_score_map(prob, "greedy", conf_thresh=conf_thresh, dist_thresh=dist_thresh)[0]
+
+
+def box_nms(prob, size=4, iou=0.1, min_prob=0.015, keep_top_k=-1):
+    """The reference's ``box_nms`` (repeatability_tools.py:227-255) on the GPU: ``prob`` a [1,H,W] float32 tensor -> the [1,H,W]
+    map of the boxes that torchvision's NMS keeps (each pixel >= ``min_prob`` is a ``size x size`` box around itself), on the
+    input's device.  The IoU test is a footprint of pixel offsets computed once on the host (``ops.box_footprint``: ``2 * size``
+    must be a positive integer, ``size <= 17``, ``0 <= iou < 1``, ``min_prob > 0``; ValueError otherwise).  Among equal scores,
+    also at the ``keep_top_k`` cut, the lower raster index comes first."""
+    if not isinstance(prob, torch.Tensor) or prob.dim() != 3 or prob.shape[0] != 1:
+        raise BalfHipError("prob must be a [1,H,W] tensor")
+    if not prob.is_cuda:
+        raise BalfHipError(f"balf_amd has no CPU path: box_nms needs prob on the GPU (got device {prob.device})")
+    return box_nms_batch(prob, size, iou, min_prob, keep_top_k)
+
+
+def _score_map_on_gpu(score_map, what):
+    m = np.ascontiguousarray(score_map, dtype=np.float32)
+    if m.ndim != 2:
+        raise ValueError(f"{what}: score map must be [H, W]")
+    if not torch.cuda.is_available():
+        raise BalfHipError(f"balf_amd has no CPU path: {what} needs the GPU")
+    return torch.from_numpy(m).to(_device()).unsqueeze(0)
+
+
+def apply_nms_fast(score_map, dist_thresh, conf_thresh=0.015):
+    """The reference's ``apply_nms_fast`` (repeatability_tools.py:25-79) on the GPU: NumPy [H,W] map in, NumPy float32 map out.
+    The greedy ``(2 dist_thresh + 1)^2`` sweep over ALL pixels in descending score order, survivors >= ``conf_thresh`` kept: a
+    pixel below the threshold only suppresses pixels that are dropped anyway, so this is the greedy NMS of the candidates
+    >= ``conf_thresh``.  1 <= ``dist_thresh`` <= 16, ``conf_thresh`` > 0; equal scores: the lower raster index
+    first."""
+    return nms_fast_score_map_batch(_score_map_on_gpu(score_map, "apply_nms_fast"), dist_thresh, conf_thresh)[0].cpu().numpy()
+
+
+def get_nms_score_map_from_score_map(heatmap, conf_thresh=0.015, nms_size=15):
+    """The reference's function of this name (repeatability_tools.py:82-100): the same map as
+    ``apply_nms_fast(heatmap, nms_size, conf_thresh)``."""
+    t = _score_map_on_gpu(heatmap, "get_nms_score_map_from_score_map")
+    return nms_fast_score_map_batch(t, nms_size, conf_thresh)[0].cpu().numpy()
 
 
 def check_common_points(kpts, mask):

@@ -37,6 +37,7 @@
 
 #include "block_ops.h"
 #include "common.h"
+#include "nms_key.h"
 #include "prof.h"
 
 int balf_topk_select_launch(const int2 *surv, const int *counts, long cap, int B, int K, int zero_fallback,
@@ -55,7 +56,6 @@ constexpr int RS = TW + 2 * GD_MAX + 1;      // LDS row stride in keys: 97 = 194
 constexpr int RH_MAX = TH + 2 * GD_MAX;      // 64 region rows
 constexpr int NS = 512;                      // pairwise mode up to this many candidates in the halo region
 constexpr int ROUNDS_DEFAULT = 12;           // rounds enqueued as launches of their own before the per-image tail (score maps need 7-9)
-constexpr unsigned KEY_BIAS = 0x00100000u;   // keeps a key's high word out of the double's denormal range
 constexpr int ALIVE_FOREVER = 0x7f7f7f7f;    // dead_round of a tile with candidates
 
 struct GreedyArgs {
@@ -89,15 +89,8 @@ __device__ __forceinline__ float g_score(const GreedyArgs &a, const float *img, 
     return img[(long)(a.crop_y + y) * a.Ws + (a.crop_x + x)];
 }
 
-__device__ __forceinline__ double make_key(float v, int idx) {
-    const u64 k = ((u64)(__float_as_uint(v) + KEY_BIAS) << 32) | (u64)(0xffffffffu - (unsigned)idx);
-    return __longlong_as_double((long long)k);
-}
-// maximum of two keys (positive normal doubles or +0) = the unsigned maximum of their bit patterns, in one instruction
-__device__ __forceinline__ double kmax(double x, double y) {
-    asm("v_max_f64 %0, %0, %1" : "+v"(x) : "v"(y));      // ("+v": the repo-wide rule for inline-asm VALU, test_build_invariants.py)
-    return x;
-}
+using balf::make_key;                                // the candidates' priority and its one-instruction maximum: nms_key.h
+using balf::kmax;
 
 // workgroup barrier that waits for the LDS traffic only: the score values requested for the next tile stay in flight
 // (__syncthreads() drains vmcnt too).  One asm statement with a memory clobber, so nothing moves across it.
@@ -761,24 +754,14 @@ extern "C" size_t balf_greedy_nms_workspace_bytes(int B, int H, int W, int K) {
     return layout(B, H, W).total;
 }
 
-extern "C" int balf_greedy_nms(const float *prob_dev, int B, int Hp, int Wp, int crop_y, int crop_x, int H, int W,
-                               int border, float conf_thresh, int dist_thresh, int K, int subpixel_patch,
-                               int32_t *idx_dev, float *score_dev, float *xy_dev, int32_t *count_dev,
-                               int32_t *total_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
-    if (!prob_dev || !idx_dev || !score_dev || !count_dev || !workspace_dev) return BALF_ERR_ARG;
-    if (B <= 0 || H <= 0 || W <= 0 || K <= 0 || K > BALF_MAX_TOPK || border < 0) return BALF_ERR_ARG;
-    if (B > 65535) return BALF_ERR_ARG;                       // blockIdx.y
-    if (!(conf_thresh > 0.0f) || dist_thresh < 0 || dist_thresh > GD_MAX) return BALF_ERR_ARG;
-    if (subpixel_patch < 0 || subpixel_patch > 16 || (subpixel_patch > 0 && !xy_dev)) return BALF_ERR_ARG;
-    if (crop_y < 0 || crop_x < 0 || crop_y + H > Hp || crop_x + W > Wp) return BALF_ERR_SHAPE;
-    if ((long)H * W > 0x7fffffffL) return BALF_ERR_SHAPE;
-    if ((long)balf_ceil_div(W, TW) * balf_ceil_div(H, TH) * B > 0x7fffffffL) return BALF_ERR_SHAPE;
+namespace {
+// The rounds and the tail: the uncapped kept list a.surv [B, H*W] and a.counts [B] on `st`.  Arguments checked by the caller.
+int greedy_rounds(const float *prob_dev, int B, int Hp, int Wp, int crop_y, int crop_x, int H, int W, int border,
+                  float conf_thresh, int dist_thresh, int32_t *total_dev, void *workspace_dev, hipStream_t st, GreedyArgs &a) {
     const Layout l = layout(B, H, W, workspace_dev);
-    if (workspace_bytes < l.total) return BALF_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
     const int ntx = balf_ceil_div(W, TW), nty = balf_ceil_div(H, TH), tiles = ntx * nty;
 
-    GreedyArgs a{prob_dev, Hp, Wp, crop_y, crop_x, H, W, border, conf_thresh, dist_thresh, B, ntx, nty,
+    a = GreedyArgs{prob_dev, Hp, Wp, crop_y, crop_x, H, W, border, conf_thresh, dist_thresh, B, ntx, nty,
                  getenv("BALF_GREEDY_NOSKIP") != nullptr,
                  l.alive, l.kept, l.dead, l.chg, l.keptr, l.list, l.dlist, l.ctr, l.surv, l.counts, total_dev};
     // (fill kernels, not hipMemsetAsync: see balf_fill_u32 in common.h)
@@ -822,9 +805,43 @@ extern "C" int balf_greedy_nms(const float *prob_dev, int B, int Hp, int Wp, int
     BALF_PROF(balf_prof::kGreedyKill, st,
               hipLaunchKernelGGL(greedy_tail_kernel, dim3(B), dim3(KTHREADS), tail_lds, st, a, rounds + 1));
     BALF_LAUNCH_CHECK();
+    return BALF_OK;
+}
+}  // namespace
+
+// shared with balf_nms_score_map (nms_map.hip): the kept list alone.  The workspace is balf_greedy_survivors_bytes(B, H, W) long
+// (= balf_greedy_nms_workspace_bytes); 0 <= dist_thresh <= 16, conf_thresh > 0 and the shape limits are the caller's to check.
+size_t balf_greedy_survivors_bytes(int B, int H, int W) { return layout(B, H, W).total; }
+
+int balf_greedy_survivors_launch(const float *prob_dev, int B, int H, int W, float conf_thresh, int dist_thresh, void *workspace_dev,
+                                 hipStream_t st, const int2 **surv, const int **counts) {
+    GreedyArgs a;
+    const int rc = greedy_rounds(prob_dev, B, H, W, 0, 0, H, W, /*border=*/0, conf_thresh, dist_thresh, nullptr, workspace_dev, st, a);
+    *surv = a.surv;
+    *counts = a.counts;
+    return rc;
+}
+
+extern "C" int balf_greedy_nms(const float *prob_dev, int B, int Hp, int Wp, int crop_y, int crop_x, int H, int W,
+                               int border, float conf_thresh, int dist_thresh, int K, int subpixel_patch,
+                               int32_t *idx_dev, float *score_dev, float *xy_dev, int32_t *count_dev,
+                               int32_t *total_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
+    if (!prob_dev || !idx_dev || !score_dev || !count_dev || !workspace_dev) return BALF_ERR_ARG;
+    if (B <= 0 || H <= 0 || W <= 0 || K <= 0 || K > BALF_MAX_TOPK || border < 0) return BALF_ERR_ARG;
+    if (B > 65535) return BALF_ERR_ARG;                       // blockIdx.y
+    if (!(conf_thresh > 0.0f) || dist_thresh < 0 || dist_thresh > GD_MAX) return BALF_ERR_ARG;
+    if (subpixel_patch < 0 || subpixel_patch > 16 || (subpixel_patch > 0 && !xy_dev)) return BALF_ERR_ARG;
+    if (crop_y < 0 || crop_x < 0 || crop_y + H > Hp || crop_x + W > Wp) return BALF_ERR_SHAPE;
+    if ((long)H * W > 0x7fffffffL) return BALF_ERR_SHAPE;
+    if ((long)balf_ceil_div(W, TW) * balf_ceil_div(H, TH) * B > 0x7fffffffL) return BALF_ERR_SHAPE;
+    if (workspace_bytes < layout(B, H, W).total) return BALF_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    GreedyArgs a;
+    int rc = greedy_rounds(prob_dev, B, Hp, Wp, crop_y, crop_x, H, W, border, conf_thresh, dist_thresh, total_dev, workspace_dev, st, a);
+    if (rc != BALF_OK) return rc;
     // the K best kept points by score, sorted (score desc, index asc); count_dev = rows returned (<= K)
-    int rc = balf_topk_select_launch(a.surv, a.counts, (long)H * W, B, K, /*zero_fallback=*/0, idx_dev, score_dev,
-                                     count_dev, st, /*thr_explicit=*/0u);
+    rc = balf_topk_select_launch(a.surv, a.counts, (long)H * W, B, K, /*zero_fallback=*/0, idx_dev, score_dev,
+                                 count_dev, st, /*thr_explicit=*/0u);
     if (rc != BALF_OK) return rc;
     if (subpixel_patch > 0) {
         hipLaunchKernelGGL(subpixel_kernel, dim3(balf_ceil_div(K, 256), B), dim3(256), 0, st, a, idx_dev, count_dev, K,

@@ -102,6 +102,76 @@ def greedy_nms(prob: torch.Tensor, crop_y: int, crop_x: int, h: int, w: int, bor
     return idx, score, xy, count, total
 
 
+# ---- NMS score maps (benchmark_test/repeatability_tools.py and utils/train_utils.py drive these) -----------------------------
+NMS_MAP_PROTOCOLS = {"greedy": _lib.NMS_MAP_GREEDY, "box": _lib.NMS_MAP_BOX}
+
+
+def box_footprint(size, iou) -> Tuple[int, Tuple[int, ...]]:
+    """The suppression footprint of ``box_nms(size=size, iou=iou)`` -> ``(radius, rows)``: ``rows[dr + radius]`` has bit
+    ``dc + radius`` set iff two ``size x size`` boxes whose centres lie ``(dr, dc)`` apart have IoU > ``iou``, with the float32
+    operations of the reference's ``box_iou`` (balf/benchmark_test/repeatability_tools.py:271-291 there) and its
+    comparison with ``float32(iou)``.  ``2 * size`` must be a positive integer: every box coordinate is then exact in float32
+    and the IoU depends on the offset alone.  ``radius = ceil(size) - 1`` (boxes further apart do not overlap) must not exceed
+    16; ``0 <= iou < 1``.  ValueError otherwise."""
+    size, iou = float(size), float(iou)
+    if not (size > 0.0) or 2.0 * size != np.floor(2.0 * size):
+        raise ValueError(f"box_footprint: 2 * size must be a positive integer, got size={size}")
+    if not (0.0 <= iou < 1.0):
+        raise ValueError(f"box_footprint: iou must lie in [0, 1), got {iou}")
+    radius = int(np.ceil(size)) - 1
+    if radius > _lib.NMS_MAP_MAX_RADIUS:
+        raise ValueError(f"box_footprint: size={size} gives radius {radius}, above {_lib.NMS_MAP_MAX_RADIUS}")
+    f32 = np.float32
+    half = f32(size / 2.0)
+    d = np.arange(-radius, radius + 1, dtype=np.float32)
+    lo, hi = d - half, d + half                                      # the moved box along one axis; the other one is (-half, half)
+    side = np.maximum(np.minimum(hi, half) - np.maximum(lo, -half), f32(0)).astype(np.float32)
+    inter = (side[:, None] * side[None, :]).astype(np.float32)
+    area = f32((half - -half) * (half - -half))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        val = (inter / ((area + area).astype(np.float32) - inter)).astype(np.float32)
+    inside = val > f32(iou)
+    rows = tuple(int(sum(1 << c for c in range(2 * radius + 1) if inside[r, c])) for r in range(2 * radius + 1))
+    return radius, rows
+
+
+def nms_score_map(prob: torch.Tensor, protocol: str, *, conf_thresh: float, dist_thresh: Optional[int] = None, size=None, iou=None,
+                  keep_top_k: int = -1) -> Tuple[torch.Tensor, torch.Tensor]:
+    """NMS score maps of a batch (balf_nms_score_map in include/balf_hip.h): ``prob`` [B,H,W] float32 on the GPU -> (map [B,H,W]
+    float32: a survivor keeps its score, everything else is +0.0; count [B] int32 survivors).  ``protocol='greedy'``: the
+    reference's ``apply_nms_fast(prob[b], dist_thresh, conf_thresh)``; ``protocol='box'``: its ``box_nms(prob[b:b+1], size, iou,
+    min_prob=conf_thresh, keep_top_k)`` with the footprint of :func:`box_footprint`.  Among equal scores the lower raster index
+    comes first.  ``keep_top_k <= 0``: all survivors.  Nothing is read back."""
+    if protocol not in NMS_MAP_PROTOCOLS:
+        raise ValueError(f"protocol must be one of {sorted(NMS_MAP_PROTOCOLS)}, got {protocol!r}")
+    if not isinstance(prob, torch.Tensor) or prob.dtype != torch.float32 or prob.dim() != 3:
+        raise BalfHipError("prob must be a [B,H,W] float32 tensor")
+    require_gpu_tensor(prob, "prob")
+    if not (float(conf_thresh) > 0.0):
+        raise ValueError(f"conf_thresh must be positive, got {conf_thresh}")
+    radius, rows, dist = 0, None, 0
+    if protocol == "greedy":
+        if dist_thresh is None or int(dist_thresh) != dist_thresh or not (1 <= int(dist_thresh) <= _lib.NMS_MAP_MAX_RADIUS):
+            raise ValueError(f"dist_thresh must be an integer in 1..{_lib.NMS_MAP_MAX_RADIUS}, got {dist_thresh}")
+        dist = int(dist_thresh)
+    else:
+        if size is None or iou is None:
+            raise ValueError("protocol 'box' needs size and iou")
+        radius, table = box_footprint(size, iou)
+        rows = (C.c_uint64 * len(table))(*table)
+    b, h, w = prob.shape
+    dev = prob.device
+    code = NMS_MAP_PROTOCOLS[protocol]
+    nbytes = C.c_size_t(0)
+    check(lib().balf_nms_score_map_sizes(b, h, w, code, C.byref(nbytes)), "balf_nms_score_map_sizes")
+    out = torch.empty_like(prob)
+    count = torch.empty((b,), dtype=torch.int32, device=dev)
+    ws = _workspace("nms_map", dev, nbytes.value)
+    launch("balf_nms_score_map", dev, prob, b, h, w, code, float(conf_thresh), dist, rows, radius, int(keep_top_k), out, count,
+           Workspace(ws))
+    return out, count
+
+
 def profile_begin() -> None:
     check(lib().balf_profile_begin(), "balf_profile_begin")
 

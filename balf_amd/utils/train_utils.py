@@ -13,8 +13,9 @@ Adam / SGD for GPU parameters), ``build_scheduler``, ``WarmRestart``, ``LinearDe
   detected once and in batches and all pairs evaluated by the batched core (``benchmark_test.evaluate``).
 * ``check_val_repeatability`` (train_utils.py:205-306): the per-epoch validation on synthetic-homography pairs that the
   reference selects checkpoints by (train.py:87,113), pairs forwarded in batches and both of its evaluations (greedy NMS
-  and window NMS) run by the batched core from the same forward.  Its tensorboard logging -- and with it
-  ``prob_to_score_maps_tensor_batch`` / ``apply_nms_fast`` (train_utils.py:162-168) -- is not ported.
+  and window NMS) run by the batched core from the same forward.  Its tensorboard logging is not ported.
+* ``prob_to_score_maps_tensor_batch`` (train_utils.py:162-168): the maps that logging draws, ``apply_nms_fast`` of a batch in
+  one call on the GPU.  The validations do not call it.
 * ``check_val_anchor_loss``: the quantity ``train_model`` logs as ``total_loss`` (train_utils.py:104-120), evaluated over a
   validation loader without gradients.  The reference has no such function: it only sees the loss while training.
 * ``train_head``: one epoch of ``train_model``'s step (train_utils.py:104-124) for the head alone, encoder frozen.
@@ -44,6 +45,13 @@ def compute_repeatability_with_maximum_filter(src_scores_np, dst_scores_np, homo
     r = repeatability_tools.compute_repeatability(src_pts_nms, dst_to_src_pts_nms)
     return ([r['rep_single_scale']], [r['rep_multi_scale']], [r['error_overlap_single_scale']],
             [r['error_overlap_multi_scale']], [r['possible_matches']])
+
+
+def prob_to_score_maps_tensor_batch(prob_outputs, nms_size):
+    """``apply_nms_fast(prob_outputs[b], nms_size)`` for every map of ``prob_outputs`` [B,H,W] (float32, on the GPU) in one
+    launch -> [B,1,H,W] float32 ON THE INPUT'S DEVICE.  The reference (train_utils.py:162-168) loops over the batch on the
+    host and returns a CPU tensor: call ``.cpu()`` on the result where a host tensor is needed."""
+    return repeatability_tools.nms_fast_score_map_batch(prob_outputs.detach(), nms_size).unsqueeze(1)
 
 
 _REP_FIELDS = ('rep_single_scale', 'rep_multi_scale', 'error_overlap_single_scale', 'error_overlap_multi_scale',

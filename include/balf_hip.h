@@ -240,6 +240,33 @@ int balf_greedy_nms(const float *prob_dev, int B, int Hp, int Wp, int crop_y, in
                     float *score_dev, float *xy_dev, int32_t *count_dev, int32_t *total_dev, void *workspace_dev,
                     size_t workspace_bytes, void *stream);
 
+/* ---- NMS score maps: box_nms and apply_nms_fast of the evaluation configs, batched ---------------------
+ * prob_dev [B,H,W] fp32 -> out_dev [B,H,W]: EVERY element is written, a survivor gets its score and every other element
+ * +0.0f (the caller clears nothing); count_dev [B] = survivors per image after keep_top_k (may be NULL).
+ *   BALF_NMS_MAP_GREEDY  apply_nms_fast(score_map, dist_thresh, conf_thresh) = get_nms_score_map_from_score_map(heatmap,
+ *                        conf_thresh, nms_size = dist_thresh), benchmark_test/repeatability_tools.py:25-100: the kept list of
+ *                        balf_greedy_nms on the candidates >= conf_thresh, 1 <= dist_thresh <= 16; footprint / radius ignored.
+ *   BALF_NMS_MAP_BOX     box_nms(prob, size, iou, min_prob = conf_thresh, keep_top_k), :227-255: candidates >= conf_thresh,
+ *                        visited in descending score order; one is kept iff no kept candidate lies at an offset (dr, dc) of
+ *                        the FOOTPRINT = the offsets at which two size x size boxes have IoU > iou.  footprint (HOST memory,
+ *                        copied into the kernels' argument block: nothing is uploaded) holds 2 * radius + 1 row words, bit
+ *                        dc + radius of word dr + radius; 0 <= radius <= BALF_NMS_MAP_MAX_RADIUS; it must hold the centre, be
+ *                        symmetric under (dr, dc) -> (-dr, -dc) and set no bit beyond 2 * radius.  dist_thresh ignored.
+ * Equal scores, in both protocols and at the keep_top_k cut: the lower raster index first (the reference's order there is
+ * whatever an unstable sort gives).  keep_top_k <= 0: all survivors.  conf_thresh > 0.  Stream-ordered, nothing synchronised
+ * or read back, capturable; the number of rounds depends on the data and is finished by a per-image kernel as in
+ * balf_greedy_nms.  BALF_ERR_ARG: an unknown protocol, B outside 1..65535, H or W < 1, conf_thresh <= 0 or NaN, dist_thresh
+ * / radius / footprint outside the above, a NULL prob_dev, out_dev or workspace_dev; BALF_ERR_SHAPE: H * W >= 2^31;
+ * BALF_ERR_WORKSPACE: fewer bytes than balf_nms_score_map_sizes gives (its output is written only with BALF_OK).  Every
+ * refusal comes before any launch: the outputs are untouched. */
+#define BALF_NMS_MAP_GREEDY 0
+#define BALF_NMS_MAP_BOX 1
+#define BALF_NMS_MAP_MAX_RADIUS 16
+int balf_nms_score_map_sizes(int B, int H, int W, int protocol, size_t *workspace_bytes);
+int balf_nms_score_map(const float *prob_dev, int B, int H, int W, int protocol, float conf_thresh, int dist_thresh,
+                       const uint64_t *footprint, int radius, int keep_top_k, float *out_dev, int32_t *count_dev,
+                       void *workspace_dev, size_t workspace_bytes, void *stream);
+
 /* ---- HardNet patch descriptor of the demo path ----------------------------------------
  * Replaces HardNet.load_state_dict / HardNet.forward, third_party/hardnet/hardnet_pytorch.py:31-72, as called by
  * demo/demo_match.py:72-93,131-134.  The 21 floating-point state tensors in state_dict() order are, per
